@@ -8,21 +8,31 @@ A "step" is ONE DDIM step of the hot path over one batch of synthetic input: pac
 Default workload (N = 1): BASELINE.json configs[2], the largest configuration of BASELINE's list that one GPU runs -- a
 32-frame 512x512 clip (latent 64x64), 50-step DDIM schedule, frequency-spectrum attention interpolation (fusion "fft" on the
 input-block attn1 modules), 96 samples per step -- on synthetic latents / conditioning / weights (name-keyed deterministic
-fill; there are no checkpoints on the GPU box).  configs[1] (8 frames, "replace": the headline of rounds 1-4) and the
-16-frame flow_fix share are timed in the same process as `extra`.
+fill: no checkpoint is read); the same arguments give the same inputs in every run.
 Inputs are resident in HBM when the timed region starts.  With --gpus N every rank runs the same per-GPU
 workload on its own frames (weak scaling); `--fusion flow_fix` adds the FSAI + flow path, whose one-neighbour
 boundary exchange runs over RCCL.
+
+A plain run does only what the headline needs: set up, W warm-up steps (at least 3 in graph mode: capture and the
+engine's launch-sequence choice happen there), exactly K timed steps, the outputs (--dump-outputs DIR), the JSON line.
+Everything else moves behind --full (off by default): the DDIM-inversion timing, the instrumented kernel-by-kernel pass
+behind `roofline` and the bit comparison against it, the other workloads (`extra`: configs[1] = 8 frames "replace", the
+headline of rounds 1-4; the flow_fix shares; 768x768), the dead-branch and end-to-end figures and the CPU baseline.  In a
+plain run those keys of the line are null.
+
+--dump-outputs DIR writes what the last timed step handed its caller (DDIMSampler.p_sample_ddim_with_inverse: x_prev and
+pred_x0, this rank's frames) as DIR/<name>.npy in float32; an array above its share of 64 MB is written as a fixed, seeded
+sample of its elements instead.
 
 With --gpus N > 1 the defaults change to what north_star asks the multi-GPU run to measure: the shipped hook
 schedule (`--fusion flow_fix`) at BASELINE config 4's per-GPU share (16 frames per GPU), so the one-neighbour halo
 exchange over RCCL is inside the timed region, and the line carries `exchange: {mode, bytes_per_step,
 wait_ms_per_step}`, `ranks_seen` (an all-reduce of 1 over the group) and `scaling_anchor`: the like-for-like
-single-GPU figure of that workload is `python bench.py --gpus 1 --fusion flow_fix --frames 16` (= the flow_fix extra of the
-default N = 1 line), not the default N = 1 `value` (configs[2]: fft, 32 frames).  Every wait on a peer is bounded
+single-GPU figure of that workload is `python bench.py --gpus 1 --fusion flow_fix --frames 16` (= the flow_fix extra of an
+N = 1 line with --full), not the default N = 1 `value` (configs[2]: fft, 32 frames).  Every wait on a peer is bounded
 (VFACE_EXCHANGE_TIMEOUT_S, default 120 s): a rank whose neighbour never sends exits non-zero naming it.
 
-Also reported on the same JSON line:
+With --full, also reported on the same JSON line:
   roofline     -- the kernel family with the largest share of the step (by HIP events on the launch stream around
                   every launch, recorded in an instrumented kernel-by-kernel pass of the same W + K steps right after
                   the timed region): FLOPs per launch / mean launch duration against the dense 16-bit MFMA peak
@@ -63,7 +73,7 @@ def parse(argv=None):
     ap.add_argument("--fusion", default=None, help="replace | fft | flow_fix | none (default: fft at --gpus 1; flow_fix -- the "
                                                    "shipped schedule, ddim_w_inv.py:303-305, with its halo exchange -- at --gpus N > 1)")
     ap.add_argument("--exchange", default="p2p", choices=["p2p", "allgather"], help="halo exchange form at --gpus N > 1")
-    ap.add_argument("--inv-steps", type=int, default=3, help="DDIM-inversion steps timed after the run (0 = skip)")
+    ap.add_argument("--inv-steps", type=int, default=3, help="DDIM-inversion steps timed after the run (--full only; 0 = skip)")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -77,6 +87,12 @@ def parse(argv=None):
     ap.add_argument("--eager", action="store_true",
                     help="timed region launches kernel by kernel (default: the UNet forward of a step replayed from a hipGraph, "
                          "falling back to kernel-by-kernel launches by itself where a graph cannot be captured)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: inversion timing, the instrumented pass (roofline), the extra "
+                         "workloads, dead-branch and end-to-end figures, the CPU baseline (--no-extras / --no-cpu-baseline / "
+                         "--inv-steps 0 still drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (x_prev, pred_x0) as DIR/<name>.npy, float32, at most 64 MB in all")
     return resolve_defaults(ap.parse_args(argv))
 
 
@@ -399,6 +415,23 @@ def traffic_from_profiles(prefixes, workload_ok):
             f"command on kernel sources {want}), not measured in this run")
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays, share_bytes):
+    """--dump-outputs: every array as <path>/<name>.npy in float32, whole while it fits in `share_bytes`; above that a fixed,
+    seeded sample of its elements (flattened, indices ascending), so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        v = t.detach().to(torch.float32).cpu().numpy()
+        if v.nbytes > share_bytes:
+            keep = max(1, (share_bytes - 4096) // 4)
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), v)
+    log(f"outputs of the last timed step: {', '.join(sorted(arrays))} -> {path}")
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -495,18 +528,17 @@ def main():
             s_ = steps[i % len(steps)]
             sampler._register_step_hooks(flow)
             ts = torch.full((F_,), s_, device=dev, dtype=torch.long)
-            img, _ = sampler.p_sample_ddim_with_inverse(img, c, ts, index=len(steps) - 1 - (i % len(steps)),
-                                                        target_conditioning=tc, inverse_results_dir=inv,
-                                                        unconditional_guidance_scale=3.0, flow=flow,
-                                                        unconditional_conditioning=uc, test_model_kwargs=kw)
-            return img
+            return sampler.p_sample_ddim_with_inverse(img, c, ts, index=len(steps) - 1 - (i % len(steps)),
+                                                      target_conditioning=tc, inverse_results_dir=inv,
+                                                      unconditional_guidance_scale=3.0, flow=flow,
+                                                      unconditional_conditioning=uc, test_model_kwargs=kw)
 
         with torch.no_grad():
             img = x_T
             # (graph mode: capture happens in the first step, the two-stream overlap check in the second, and a fall-back to one
             # launch sequence would capture again in the third -- none of that may land in the timed region, however small --warmup is)
             for i in range(max(n_warm, 3 if graph else 0)):
-                img = one_step(img, i)
+                img, _ = one_step(img, i)
             img = x_T
             fence()
             if eng.exchange_events is not None:
@@ -521,7 +553,7 @@ def main():
                     # kept so that the bit comparison between the timed region and the kernel-by-kernel pass covers every step
                     done_clips.append(img)
                     img = x_T
-                img = one_step(img, i)
+                img, pred_x0 = one_step(img, i)
             t_enq = time.perf_counter() - t0      # host time to enqueue the steps (the GPU runs behind)
             fence()
             el = time.perf_counter() - t0
@@ -584,6 +616,7 @@ def main():
         eng.exchange_events = None
         sampler.drop_dead_branches = False
         return {"final_latents": torch.cat([t.detach() for t in done_clips] + [img.detach()]).clone(),
+                "outputs": {"x_prev": img, "pred_x0": pred_x0},      # what the last timed step handed its caller
                 "ms_step": el / n_steps * 1e3, "enqueue_ms": t_enq / n_steps * 1e3, "inv_ms": inv_ms, "elapsed": el,
                 "launch": launch, "exchange": exch, "h": h}
 
@@ -591,31 +624,36 @@ def main():
     h = a.res // 8
     log("weights resident; warm-up ...")
     # Timed region: W + K DDIM steps with NO instrumentation inside -- the UNet forward of a step replayed from a hipGraph,
-    # the product default (one host call instead of ~1200).  The per-launch HIP events behind `roofline` are recorded in a
-    # second, kernel-by-kernel pass of the same W + K steps right after it (events cannot be recorded inside a captured
-    # graph); that pass's own step time is reported beside.
-    r = run_workload(F_, a.fusion, a.steps, a.warmup, False, a.inv_steps, graph=not a.eager)
+    # the product default (one host call instead of ~1200).  With --full the per-launch HIP events behind `roofline` are
+    # recorded in a second, kernel-by-kernel pass of the same W + K steps right after it (events cannot be recorded inside a
+    # captured graph); that pass's own step time is reported beside.
+    r = run_workload(F_, a.fusion, a.steps, a.warmup, False, a.inv_steps if a.full else 0, graph=not a.eager)
     launch_mode = r["launch"] + ("" if (a.eager or r["launch"] != "kernel by kernel") else " (no graph captured: capture failed)")
     ms_step, inv_ms = r["ms_step"], r["inv_ms"]
     if inv_ms is not None:
         log(f"inversion: {inv_ms:.2f} ms/step (2F = {2 * F_} unhooked sample-forwards)")
     log(f"timed {a.steps} steps: {ms_step:.2f} ms/step (host enqueue {r['enqueue_ms']:.2f} ms/step; {launch_mode})")
-    log("instrumented pass (kernel by kernel, HIP events around every GEMM / conv / attention / norm launch) ...")
-    timer.reset()
-    ri = run_workload(F_, a.fusion, a.steps, a.warmup, True, 0, graph=False)
-    el = ri["elapsed"]
-    log(f"  {ri['ms_step']:.2f} ms/step (host enqueue {ri['enqueue_ms']:.2f} ms/step)")
-    # the timed region (hipGraph replay, two launch streams where they apply) and this pass (kernel by kernel, one launch sequence)
-    # walked the same K steps from the same x_T: their latents must be the same bits
-    same_bits = bool(torch.equal(r["final_latents"], ri["final_latents"]))
-    log(f"  latents after {a.steps} steps: timed region {'==' if same_bits else '!='} kernel-by-kernel pass")
+    if a.dump_outputs:
+        outs = r["outputs"] if world == 1 else {f"{k}_rank{rank}": v for k, v in r["outputs"].items()}
+        dump_outputs(a.dump_outputs, outs, DUMP_LIMIT_BYTES // (len(outs) * world))
+    ri, same_bits, fam = None, None, {}
+    if a.full:
+        log("instrumented pass (kernel by kernel, HIP events around every GEMM / conv / attention / norm launch) ...")
+        timer.reset()
+        ri = run_workload(F_, a.fusion, a.steps, a.warmup, True, 0, graph=False)
+        el = ri["elapsed"]
+        log(f"  {ri['ms_step']:.2f} ms/step (host enqueue {ri['enqueue_ms']:.2f} ms/step)")
+        # the timed region (hipGraph replay, two launch streams where they apply) and this pass (kernel by kernel, one launch sequence)
+        # walked the same K steps from the same x_T: their latents must be the same bits
+        same_bits = bool(torch.equal(r["final_latents"], ri["final_latents"]))
+        log(f"  latents after {a.steps} steps: timed region {'==' if same_bits else '!='} kernel-by-kernel pass")
+        fam = timer.summary()
     fps = (F_ * world) / (a.ddim_steps * ms_step / 1e3)
-    fam = timer.summary()
     unet_gflop = UNET_GFLOP.get(h)
 
     # the other single-GPU BASELINE configurations, same process and build, outside the timed region of the headline run
     extras = []
-    if world == 1 and not a.no_extras and a.res == 512:
+    if world == 1 and a.full and not a.no_extras and a.res == 512:
         for name, f2, fus, res2 in (
                 ("BASELINE configs[1]: 8-frame 512x512 clip, structure attention injection only (the headline of rounds 1-4)", 8, "replace", 512),
                 ("BASELINE configs[2]: 32-frame 512x512 clip + frequency-spectrum attention interpolation", 32, "fft", 512),
@@ -658,7 +696,7 @@ def main():
     # defines a swapped frame as 50 x 3 sample-forwards; the sampler drops the recon branch's x_prev and the inversion's source
     # half, so the same outputs (bit-identical: tests/test_unet_gpu.py::test_drop_recon_is_bit_identical) need 2 + 1 of 3 + 2
     dead = None
-    if world == 1 and not a.no_extras and a.res == 512:
+    if world == 1 and a.full and not a.no_extras and a.res == 512:
         log(f"extra: dead-branch elimination ({F_} frames, fusion={a.fusion}: sampling on [uncond;cond], inversion on the target half) ...")
         e = run_workload(F_, a.fusion, a.extra_steps, 2, False, a.inv_steps, graph=not a.eager, drop=True)
         dead = {"note": "sampler.drop_dead_branches: sampling on [uncond ; cond] (2F samples per step: the recon third's x_prev is dropped "
@@ -674,7 +712,7 @@ def main():
     # the widened pipeline end to end, outside the metric: VAE encode -> RAFT-shaped flow -> 50-step DDIM inversion
     # -> 50-step sampling with the shipped flow_fix schedule -> VAE decode -> paste-back, through the CLI's own code path
     e2e = None
-    if world == 1 and not a.no_extras and a.res == 512 and a.dtype == "fp16":
+    if world == 1 and a.full and not a.no_extras and a.res == 512 and a.dtype == "fp16":
         try:
             from vface_amd.scripts import VFace_inference_batch as cli
             log("extra: end-to-end pipeline (encode, flow, inversion, sampling, decode, paste-back), 2 x 8 frames ...")
@@ -720,53 +758,76 @@ def main():
             e2e = {"error": f"{type(ex).__name__}: {ex}"}
             log(f"  end-to-end extra failed: {e2e['error']}")
     if rank == 0:
-        step_ms_i = el * 1e3                     # the instrumented pass, all K steps
         unet_tflops = 3 * F_ * unet_gflop * 1e9 / (ms_step * 1e-3) / 1e12 if unet_gflop else None
+        instrumented, roofline, attn1_kernel = None, None, None
+        if a.full:
+            step_ms_i = el * 1e3                     # the instrumented pass, all K steps
 
-        def fam_total(name):
-            d = fam.get(name, {})
-            ms = sum(c["ms"] for c in d.values())
-            fl = sum(c["flops"] for c in d.values())
-            by = sum(c["bytes"] for c in d.values())
-            n = sum(c["launches"] for c in d.values())
-            o = {"launches": n, "ms": ms, "ms_per_step": ms / a.steps, "share_of_step_time": ms / step_ms_i if step_ms_i else 0.0,
-                 "by_kernel": {k: {kk: vv for kk, vv in c.items() if kk not in ("flops", "bytes") and not (kk == "gbps" and not c["bytes"])
-                                   and not (kk == "tflops" and not c["flops"])} for k, c in sorted(d.items())}}
-            if fl:
-                o["tflops"] = fl / (ms * 1e-3) / 1e12 if ms else 0.0
-                o["frac"] = o["tflops"] / MFMA_PEAK_TFLOPS
-                o["tflop_per_step"] = fl / a.steps / 1e12
-            if by:
-                o["gbps"] = by / (ms * 1e-3) / 1e9 if ms else 0.0
-                o["frac_of_8TBps"] = o["gbps"] / 8000.0
-            return o
+            def fam_total(name):
+                d = fam.get(name, {})
+                ms = sum(c["ms"] for c in d.values())
+                fl = sum(c["flops"] for c in d.values())
+                by = sum(c["bytes"] for c in d.values())
+                n = sum(c["launches"] for c in d.values())
+                o = {"launches": n, "ms": ms, "ms_per_step": ms / a.steps, "share_of_step_time": ms / step_ms_i if step_ms_i else 0.0,
+                     "by_kernel": {k: {kk: vv for kk, vv in c.items() if kk not in ("flops", "bytes") and not (kk == "gbps" and not c["bytes"])
+                                       and not (kk == "tflops" and not c["flops"])} for k, c in sorted(d.items())}}
+                if fl:
+                    o["tflops"] = fl / (ms * 1e-3) / 1e12 if ms else 0.0
+                    o["frac"] = o["tflops"] / MFMA_PEAK_TFLOPS
+                    o["tflop_per_step"] = fl / a.steps / 1e12
+                if by:
+                    o["gbps"] = by / (ms * 1e-3) / 1e9 if ms else 0.0
+                    o["frac_of_8TBps"] = o["gbps"] / 8000.0
+                return o
 
-        by_family = {k: fam_total(k) for k in ("gemm", "conv", "attention", "norm")}
-        by_family["gemm"]["kernel"] = "gemm_kernel<T, MODE_PLAIN, NT, DB, PERSIST, RM> (gemm.hip): every Linear / 1x1 conv, + ffn_fused_kernel<T, C> (ffn.hip): the level-0 FeedForward in one launch + st_front_kernel<T, C> (stfront.hip): GroupNorm-apply, proj_in, LayerNorm and the attn1 projection of a level-0 block in one launch; FLOPs as executed (2 M N K)"
-        by_family["conv"]["kernel"] = "conv_patch_kernel<T, NT, KH, KW, ..> (conv.hip) + gemm_kernel<T, MODE_CONV_*> (im2col); FLOPs as executed"
-        by_family["attention"]["kernel"] = "attn_kernel<T, DH, QT, G, LAZY> (attention.hip); algorithmic FLOPs 4 n nk dh per (output sample, head)"
-        by_family["norm"]["kernel"] = "layernorm_kernel, gn_apply_kernel, gn_finalize_cols, flow_warp_kernel (pointwise.hip): HBM-bound, algorithmic bytes"
-        covered = sum(by_family[k]["ms"] for k in by_family)
-        # north_star's "fraction of the attention-GEMM roofline", as a KERNEL figure: the launches that compute attn1's
-        # q|k|v projections and softmax(QK^T)V -- the attention kernels, the plain / dual-source (FSAI-folded) projection GEMMs of the 640- /
-        # 1280-channel blocks, and the level-0 front kernel (which also holds proj_in: its FLOPs as executed are counted with it) -- FLOPs
-        # as executed over their own event-timed duration, against the dense MFMA peak
-        def _is_qkv(key):
-            m = key.split("+")[0].split("x")
-            return len(m) == 3 and all(v.isdigit() for v in m) and (int(m[1]) == 3 * int(m[2]) or "+a2" in key)
-        a1 = [c for k, c in fam.get("gemm", {}).items() if k == "st_front" or _is_qkv(k)] + list(fam.get("attention", {}).values())
-        a1_ms, a1_fl = sum(c["ms"] for c in a1), sum(c["flops"] for c in a1)
-        attn1_kernel = None if not a1_ms else {
-            "tflops": a1_fl / (a1_ms * 1e-3) / 1e12, "frac": a1_fl / (a1_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, "ms_per_step": a1_ms / a.steps,
-            "tflop_per_step": a1_fl / a.steps / 1e12,
-            "kernels": "attn_kernel (all head dims) + the attn1 projection GEMMs (M x 3d x d and the dual-source FSAI-folded M x 2d x 2d) + "
-                       "st_front_kernel (level 0: GroupNorm-apply, proj_in, LayerNorm and the q|k|v projection in one launch, all of its FLOPs)"}
-        mfma_fams = ("gemm", "conv", "attention")
-        dom = max(mfma_fams, key=lambda k: by_family[k]["ms"])
-        d = by_family[dom]
-        prefixes = {"gemm": ("gemm_kernel<F16, 0,", "gemm_kernel<BF16, 0,", "ffn_fused_kernel", "st_front_kernel"), "conv": ("conv_patch_kernel", "gemm_kernel<F16, 1,", "gemm_kernel<F16, 2,"),
-                    "attention": ("attn_kernel",)}[dom]
-        traffic, traffic_src = traffic_from_profiles(prefixes, F_ == 32 and h == 64 and a.fusion == "fft" and a.dtype == "fp16" and world == 1)
+            by_family = {k: fam_total(k) for k in ("gemm", "conv", "attention", "norm")}
+            by_family["gemm"]["kernel"] = "gemm_kernel<T, MODE_PLAIN, NT, DB, PERSIST, RM> (gemm.hip): every Linear / 1x1 conv, + ffn_fused_kernel<T, C> (ffn.hip): the level-0 FeedForward in one launch + st_front_kernel<T, C> (stfront.hip): GroupNorm-apply, proj_in, LayerNorm and the attn1 projection of a level-0 block in one launch; FLOPs as executed (2 M N K)"
+            by_family["conv"]["kernel"] = "conv_patch_kernel<T, NT, KH, KW, ..> (conv.hip) + gemm_kernel<T, MODE_CONV_*> (im2col); FLOPs as executed"
+            by_family["attention"]["kernel"] = "attn_kernel<T, DH, QT, G, LAZY> (attention.hip); algorithmic FLOPs 4 n nk dh per (output sample, head)"
+            by_family["norm"]["kernel"] = "layernorm_kernel, gn_apply_kernel, gn_finalize_cols, flow_warp_kernel (pointwise.hip): HBM-bound, algorithmic bytes"
+            covered = sum(by_family[k]["ms"] for k in by_family)
+            # north_star's "fraction of the attention-GEMM roofline", as a KERNEL figure: the launches that compute attn1's
+            # q|k|v projections and softmax(QK^T)V -- the attention kernels, the plain / dual-source (FSAI-folded) projection GEMMs of the 640- /
+            # 1280-channel blocks, and the level-0 front kernel (which also holds proj_in: its FLOPs as executed are counted with it) -- FLOPs
+            # as executed over their own event-timed duration, against the dense MFMA peak
+            def _is_qkv(key):
+                m = key.split("+")[0].split("x")
+                return len(m) == 3 and all(v.isdigit() for v in m) and (int(m[1]) == 3 * int(m[2]) or "+a2" in key)
+            a1 = [c for k, c in fam.get("gemm", {}).items() if k == "st_front" or _is_qkv(k)] + list(fam.get("attention", {}).values())
+            a1_ms, a1_fl = sum(c["ms"] for c in a1), sum(c["flops"] for c in a1)
+            attn1_kernel = None if not a1_ms else {
+                "tflops": a1_fl / (a1_ms * 1e-3) / 1e12, "frac": a1_fl / (a1_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, "ms_per_step": a1_ms / a.steps,
+                "tflop_per_step": a1_fl / a.steps / 1e12,
+                "kernels": "attn_kernel (all head dims) + the attn1 projection GEMMs (M x 3d x d and the dual-source FSAI-folded M x 2d x 2d) + "
+                           "st_front_kernel (level 0: GroupNorm-apply, proj_in, LayerNorm and the q|k|v projection in one launch, all of its FLOPs)"}
+            mfma_fams = ("gemm", "conv", "attention")
+            dom = max(mfma_fams, key=lambda k: by_family[k]["ms"])
+            d = by_family[dom]
+            prefixes = {"gemm": ("gemm_kernel<F16, 0,", "gemm_kernel<BF16, 0,", "ffn_fused_kernel", "st_front_kernel"), "conv": ("conv_patch_kernel", "gemm_kernel<F16, 1,", "gemm_kernel<F16, 2,"),
+                        "attention": ("attn_kernel",)}[dom]
+            traffic, traffic_src = traffic_from_profiles(prefixes, F_ == 32 and h == 64 and a.fusion == "fft" and a.dtype == "fp16" and world == 1)
+            instrumented = {"launch": "kernel by kernel, ONE launch sequence over the whole batch, HIP events around every GEMM / convolution / "
+                                      "attention / norm launch (what `roofline` is computed from; vface_attn1_forward's launches issued call "
+                                      "by call, bit-identical).  With launch_streams = 2 the timed region runs the same kernels as two "
+                                      "half-batch sequences at once: its step time is below this pass's sum of launch durations by what the "
+                                      "overlap wins (profiles/r04_n)",
+                            "ms_per_step": ri["ms_step"], "host_enqueue_ms_per_step": ri["enqueue_ms"], "steps": a.steps, "warmup": a.warmup,
+                            "event_covered_share": covered / step_ms_i if step_ms_i else None}
+            # the kernel family with the largest share of the step's kernel time (VERDICT r2: by family the plain GEMM, not the
+            # convolution, is the largest and the furthest below the roofline); the others are in by_family
+            roofline = {"bound": "mfma", "kernel": d["kernel"], "family": dom,
+                        "achieved": d["tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": d["tflops"] / MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                        "launches": d["launches"], "mean_launch_us": d["ms"] * 1e3 / max(d["launches"], 1),
+                        "share_of_step_time": d["share_of_step_time"],
+                        "timing": "HIP events on the launch stream around every launch of this family, recorded in the instrumented pass: the same "
+                                  "W + K steps launched kernel by kernel right after the timed region (events cannot be recorded inside a "
+                                  "captured graph); share_of_step_time is relative to that pass",
+                        "note": "peak is the datasheet 2.5 PFLOP/s; an MFMA-only loop sustains ~1.5 PFLOP/s on this chip (it clocks ~1.6 GHz "
+                                "under matrix load: DESIGN.md 4).  whole-UNet check: sum over by_family of ms_per_step = the kernel time of a step; "
+                                "config.unet_algorithmic_tflops_per_gpu = 3F x 796.94 GFLOP / ms_per_step",
+                        "by_family": by_family}
         baseline_cfg = {(8, "replace", 512): "BASELINE configs[1]: ", (32, "fft", 512): "BASELINE configs[2] (the largest single-GPU configuration): ",
                         (16, "flow_fix", 512): "BASELINE configs[3]'s per-GPU share (64 frames / 4 GPUs): ",
                         (32, "flow_fix", 768): "BASELINE configs[4]'s per-GPU share (256 frames / 8 GPUs): "}.get((F_, a.fusion, a.res), "")
@@ -812,7 +873,7 @@ def main():
             # the N > 1 default the shipped schedule at config 4's share (16 frames per GPU, flow_fix)
             "scaling_anchor": None if world == 1 else (
                 f"N=1 anchor of this workload: `python bench.py --gpus 1 --fusion {a.fusion} --frames {F_}` (also reported by the "
-                f"default N=1 run among `extra` when fusion=flow_fix, frames=16); the default N=1 `value` is configs[2] "
+                f"N=1 run with --full among `extra` when fusion=flow_fix, frames=16); the default N=1 `value` is configs[2] "
                 f"(fft, 32 frames) and is NOT the same workload"),
             "inversion": None if inv_ms is None else {
                 "ms_per_step": inv_ms, "steps_timed": a.inv_steps,
@@ -822,29 +883,10 @@ def main():
             "extra": extras,
             "dead_branch_elimination": dead,
             "end_to_end": e2e,
-            "instrumented_pass": {"launch": "kernel by kernel, ONE launch sequence over the whole batch, HIP events around every GEMM / convolution / "
-                                            "attention / norm launch (what `roofline` is computed from; vface_attn1_forward's launches issued call "
-                                            "by call, bit-identical).  With launch_streams = 2 the timed region runs the same kernels as two "
-                                            "half-batch sequences at once: its step time is below this pass's sum of launch durations by what the "
-                                            "overlap wins (profiles/r04_n)",
-                                  "ms_per_step": ri["ms_step"], "host_enqueue_ms_per_step": ri["enqueue_ms"], "steps": a.steps, "warmup": a.warmup,
-                                  "event_covered_share": covered / step_ms_i if step_ms_i else None},
-            # the kernel family with the largest share of the step's kernel time (VERDICT r2: by family the plain GEMM, not the
-            # convolution, is the largest and the furthest below the roofline); the others are in by_family
-            "roofline": {"bound": "mfma", "kernel": d["kernel"], "family": dom,
-                         "achieved": d["tflops"], "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": d["tflops"] / MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "launches": d["launches"], "mean_launch_us": d["ms"] * 1e3 / max(d["launches"], 1),
-                         "share_of_step_time": d["share_of_step_time"],
-                         "timing": "HIP events on the launch stream around every launch of this family, recorded in the instrumented pass: the same "
-                                   "W + K steps launched kernel by kernel right after the timed region (events cannot be recorded inside a "
-                                   "captured graph); share_of_step_time is relative to that pass",
-                         "note": "peak is the datasheet 2.5 PFLOP/s; an MFMA-only loop sustains ~1.5 PFLOP/s on this chip (it clocks ~1.6 GHz "
-                                 "under matrix load: DESIGN.md 4).  whole-UNet check: sum over by_family of ms_per_step = the kernel time of a step; "
-                                 "config.unet_algorithmic_tflops_per_gpu = 3F x 796.94 GFLOP / ms_per_step",
-                         "by_family": by_family},
+            "instrumented_pass": instrumented,
+            "roofline": roofline,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_forwards, a.ddim_steps, a.fusion)
         else:
             out["cpu_baseline"] = None

@@ -283,6 +283,27 @@ def test_bench_multi_gpu_command_line_defaults_to_the_shipped_schedule():
     assert (a.fusion, a.frames, a.exchange) == ("replace", 8, "allgather")
 
 
+def test_bench_plain_run_is_lean_and_dumps_bounded_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only (everything else is behind --full), and
+    --dump-outputs writes float32 arrays: whole while they fit in their share of the byte budget, else the same seeded sample."""
+    import numpy as np
+    bench = _bench_module()
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    big = torch.linspace(-1, 1, 10000)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big}, 4096 + 4 * 100)
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big}, 4096 + 4 * 100)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and (s == small.float().numpy()).all()
+    b = np.load(tmp_path / "a" / "big.npy")
+    assert b.dtype == np.float32 and b.shape == (100,) and (np.diff(b) > 0).all()
+    assert (b == np.load(tmp_path / "b" / "big.npy")).all()
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 2 ** 20
+
+
 def test_bench_refuses_a_traffic_summary_from_other_kernel_sources(tmp_path, monkeypatch):
     """roofline.traffic is quoted from profiles/*_hbm_traffic.json only when that summary records the kernel sources this
     tree is built from (VERDICT r2 weak #10: it used to go stale silently)."""

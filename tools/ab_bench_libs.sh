@@ -5,7 +5,7 @@ base=$1; out=$2; rounds=${3:-2}; shift 3 2>/dev/null || shift 2
 for r in $(seq 1 $rounds); do
   for which in base new; do
     if [ $which = base ]; then export VFACE_HIP_LIB=$base; else unset VFACE_HIP_LIB; fi
-    python bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline --inv-steps 0 "$@" > ${out}_${which}_$r.json 2>> ${out}.err || exit 1
+    python bench.py --full --steps 20 --warmup 3 --no-extras --no-cpu-baseline --inv-steps 0 "$@" > ${out}_${which}_$r.json 2>> ${out}.err || exit 1
     python - <<PY
 import json
 d=json.loads(open("${out}_${which}_$r.json").read().strip().splitlines()[-1])

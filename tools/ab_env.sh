@@ -4,7 +4,7 @@
 var=$1; va=$2; vb=$3; out=$4; shift 4
 for r in 1 2; do
   for v in "$va" "$vb"; do
-    env $var=$v python bench.py --steps 20 --warmup 3 --no-extras --no-cpu-baseline --inv-steps 0 "$@" > ${out}_${v}_$r.json 2>> ${out}.err || exit 1
+    env $var=$v python bench.py --full --steps 20 --warmup 3 --no-extras --no-cpu-baseline --inv-steps 0 "$@" > ${out}_${v}_$r.json 2>> ${out}.err || exit 1
     python - <<PY
 import json
 d=json.loads(open("${out}_${v}_$r.json").read().strip().splitlines()[-1])

@@ -2,17 +2,19 @@
 # HBM traffic of the dominant kernel (implicit-GEMM conv) per launch, as MI355X_MICROARCH.md "HBM" prescribes:
 # separate --pmc passes (FETCH_SIZE, WRITE_SIZE; kernel-trace only), FETCH_SIZE doubled on gfx950 for 16-B-per-lane reads.
 # usage (on the GPU box, from the repo root): bash tools/traffic.sh <out-prefix> <bench args...>
+# The bench runs with --full: its instrumented kernel-by-kernel pass is part of what the counters see.
 export TMPDIR=/tmp; R=$PWD; out=$1; shift
+P=$(mktemp -d)   # the two counter passes' output and logs
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf $R/gpurun_out/pmc_$c
-  (cd /tmp && rocprofv3 --kernel-trace --pmc $c --output-format csv -d $R/gpurun_out/pmc_$c -- python3 $R/bench.py "$@" > $R/gpurun_out/pmc_$c.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --pmc $c --output-format csv -d $P/pmc_$c -- python3 $R/bench.py --full "$@" > $P/pmc_$c.log 2>&1)
 done
-python3 - "$R" "$out" <<'PY'
+echo "counter passes: $P"
+python3 - "$R" "$out" "$P" <<'PY'
 import csv, glob, json, re, sys, collections
-R, out = sys.argv[1], sys.argv[2]
+R, out, P = sys.argv[1], sys.argv[2], sys.argv[3]
 res = {}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    f = glob.glob(f"{R}/gpurun_out/pmc_{c}/*/*counter_collection.csv")[0]
+    f = glob.glob(f"{P}/pmc_{c}/*/*counter_collection.csv")[0]
     agg = collections.defaultdict(list)
     for r in csv.DictReader(open(f)):
         if r["Counter_Name"] != c:
