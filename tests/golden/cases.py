@@ -22,3 +22,14 @@ def make_flows(h=64, w=64):
         "oob": np.stack([xs - 80.0 + 0.25, 90.0 - ys]).astype(np.float32),
         "smooth": synth.synth_flow(1, h, w, seed=7)[0].numpy(),
     }
+
+
+# whole-network bound of the small UNet against the oracle (tests/test_unet_gpu.py), and the unit of tests/test_oracle_golden.py's
+# defect separations.  Small UNet / DDIM loop / config 1: measured 1.36-1.39e-3 / 5.1e-4 / 9.4e-4 (the reference's own autocast:
+# 2.06e-3)
+SMALL_BOUND = 1.5e-3
+
+# tiny_unet_f5.npz keeps every sample and channel but only a token subset (committed files stay under 1 MiB): the output's
+# columns 0, 2, 4, ... at 32 x 32, and every other row and column at 64 x 64.
+F5_KEEP = {32: (slice(None), slice(None), slice(None), slice(None, None, 2)),
+           64: (slice(None), slice(None), slice(None, None, 2), slice(None, None, 2))}

@@ -73,7 +73,7 @@ def save(name, **arrs):
     sys.stdout.write(f"wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)\n")
 
 
-from cases import make_flows as _make_flows  # noqa: E402
+from cases import F5_KEEP, make_flows as _make_flows  # noqa: E402
 
 
 def make_flows(pairs, h, w):
@@ -238,6 +238,40 @@ def gen_tiny_unet():
                                     output_blocks=True, attn_component="attn1", chunks=2, block_indices=[0, 1, 2])
     out["chunks2"] = unet(x[:4], t[:4], context=ctx[:4])
     save("tiny_unet", **out)
+
+
+@torch.no_grad()
+def gen_tiny_unet_f5():
+    """The tiny UNet on a FIVE-frame clip: the smallest clip with a frame whose whole +-2 temporal window lies inside it (frame 2),
+    odd, so no even-half assumption hides.  The frame-coupled hooks on the input-block attn1: flow_fix at 64 x 64 (the reference's
+    flow gate needs n = 4096), temporal / adaIn / fft_vfixed / chunks2 at 32 x 32, and fft at 32 x 32 as the per-frame control."""
+    import ldm.models.pnp_utils as pnp
+    unet = ref_unet(32)
+    sampler, dd = make_sampler(unet)
+    F_ = 5
+    out = {}
+
+    def off():
+        pnp.register_spa_attn_injection(sampler, 1, switch_on=False, input_blocks=True, middle_block=True,
+                                        output_blocks=True, attn_component="attn1", chunks=3)
+
+    for fusion, h in (("flow_fix", 64), ("temporal", 32), ("adaIn", 32), ("fft_vfixed", 32), ("fft", 32)):
+        x, ctx = unet_inputs(F_, h, h, f"tiny5_{h}")
+        t = torch.full((3 * F_,), 481, dtype=torch.long)
+        flow = [synth.synth_flow(F_ - 1, h, h)[i][None] for i in range(F_ - 1)]
+        off()
+        pnp.register_spa_attn_injection(sampler, 1, switch_on=True, input_blocks=True, middle_block=False,
+                                        output_blocks=False, attn_component="attn1", flow=flow, chunks=3,
+                                        block_indices=list(range(9)), fusion=fusion, split_ratio_fft=0.8, alpha=0.8)
+        out[f"in_{fusion}"] = unet(x, t, context=ctx)[F5_KEEP[h]]
+    # chunks == 2 (inversion-time variant, pnp_utils.py:259-262): the batch [target ; source] of 2F
+    x, ctx = unet_inputs(F_, 32, 32, "tiny5_32")
+    t = torch.full((2 * F_,), 481, dtype=torch.long)
+    off()
+    pnp.register_spa_attn_injection(sampler, 1, switch_on=True, input_blocks=True, middle_block=False,
+                                    output_blocks=True, attn_component="attn1", chunks=2, block_indices=[0, 1, 2])
+    out["chunks2"] = unet(x[:2 * F_], t, context=ctx[:2 * F_])[F5_KEEP[32]]
+    save("tiny_unet_f5", **out)
 
 
 @torch.no_grad()
@@ -555,7 +589,7 @@ if __name__ == "__main__":
     install_stubs()
     import builtins
     _print = builtins.print
-    gens = {"fsai": gen_fsai, "warp": gen_warp, "warp_cuda": gen_warp_cuda_form, "attn": gen_attn_module, "tiny": gen_tiny_unet, "ddim": gen_ddim,
+    gens = {"fsai": gen_fsai, "warp": gen_warp, "warp_cuda": gen_warp_cuda_form, "attn": gen_attn_module, "tiny": gen_tiny_unet, "tiny_f5": gen_tiny_unet_f5, "ddim": gen_ddim,
             "vae": gen_vae, "paste": gen_paste}
     gens["lowp"] = lambda: gen_lowp(a.full)
     if a.full:

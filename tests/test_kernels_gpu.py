@@ -1550,3 +1550,206 @@ def test_attention_wave_count_and_query_tiling_do_not_change_bits(dh, n, B):
         for variant, out in outs.items():
             assert torch.isfinite(out).all(), (name, variant)
             assert rel_l2(out.float().cpu(), ref) < (1e-3 if name == "plain" else 3e-3), (name, variant)
+
+
+# ------------------------------------------------------------------ the frame-mixing kernels of the staged hook modes
+# Buffers laid out as engine.staged_attn1 lays them: one qkv buffer [3 F n, 3d], q|k = C_ = 2d columns at ld = 3d, frame stride
+# n 3d, chunk k at rows [k F n, (k + 1) F n).  The whole buffer starts as a sentinel pattern, so a write outside the q|k columns
+# of the target chunks shows.
+U32 = 2.0 ** -24                                   # fp32 unit roundoff
+MANT = {torch.float16: (10, -14), torch.bfloat16: (7, -126)}     # explicit mantissa bits, smallest normal exponent
+
+
+def ulp(ref64, dt):
+    """One unit in the last place of ``dt`` at each element of the fp64 ``ref64`` (the subnormal spacing below the normals)."""
+    p, emin = MANT[dt]
+    _, e = torch.frexp(ref64.abs())                # |r| = m 2^e, m in [0.5, 1): floor(log2 |r|) = e - 1
+    e = torch.where(ref64 == 0, torch.full_like(e, emin + 1), e)
+    return torch.exp2((torch.clamp(e - 1, min=emin) - p).double())
+
+
+def sentinel(rows, cols, dt):
+    """-63.5 .. 63.5 in steps of 0.25 along the flat index, period 509 (built in the 16-bit type: the buffers reach 0.75 GB)."""
+    period = ((torch.arange(509, dtype=torch.float32) - 254) * 0.25).to(dt)
+    return period.repeat(-(-rows * cols // 509))[:rows * cols].reshape(rows, cols)
+
+
+# (the largest clips at the largest maps are trimmed to ~0.2 GB of buffer, except the level-0 pairing n = 4096, d = 320 at every F,
+# which at F = 32 is the headline clip's own temporal shape, 0.75 GB)
+TEMPORAL_CASES = [(F_, n, d) for F_ in (1, 2, 3, 5, 7, 32) for n in (64, 1000, 4096) for d in (32, 320, 1280)
+                  if F_ * n * d <= 11_000_000 or (n, d) == (4096, 320)]
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("F_,n,d", TEMPORAL_CASES)
+def test_temporal_gauss(dt, F_, n, d):
+    """fusion="temporal": chunk 1 and chunk 2 q|k = the window-5 Gaussian over the frames of chunk 0's q|k, renormalised at the clip
+    ends (oracle.hooks.temporal_attention, pnp_utils.py:59-90), evaluated in fp64 on the exact 16-bit inputs.
+    Bound per element: one rounding to the output type, 0.5 ulp(ref), plus the kernel's fp32 arithmetic -- at most 5 products and
+    5 sums for the weighted sum and the weight total, one division, and weights that are fp32 roundings of exp(-0.5 o^2) / sum
+    (the oracle's as well as the kernel's): 16 u S with u = 2^-24 and S = sum_o w_o |x_o| / sum_o w_o, the scale of the terms
+    (it only matters where the weighted sum cancels towards zero)."""
+    h = hip()
+    Fn, C3 = F_ * n, 3 * d
+    host = sentinel(3 * Fn, C3, dt)
+    x = rnd((Fn, 2 * d), 1000 * F_ + d + n, dt)
+    host[:Fn, :2 * d] = x
+    ref = ohooks_temporal(x.double().reshape(F_, n, 2 * d)).reshape(Fn, 2 * d)
+    scale = ohooks_temporal(x.double().abs().reshape(F_, n, 2 * d)).reshape(Fn, 2 * d)
+    bound = 0.5 * ulp(ref, dt) + 16 * U32 * scale
+    for with_dst2 in (True, False):
+        buf = host.to(DEV)
+        h.temporal_gauss(buf, buf[Fn:], buf[2 * Fn:] if with_dst2 else None, F=F_, n=n, C_=2 * d, ld_src=C3, fs_src=n * C3,
+                         ld_dst=C3, fs_dst=n * C3)
+        got = buf.cpu()
+        assert torch.equal(got[:Fn], host[:Fn]), "chunk 0 must not change"
+        assert torch.equal(got[:, 2 * d:], host[:, 2 * d:]), "the v columns must not change"
+        for ch in ((1, 2) if with_dst2 else (1,)):
+            g = got[ch * Fn:(ch + 1) * Fn, :2 * d].double()
+            err = (g - ref).abs()
+            worst = int(torch.argmax(err / bound))
+            assert bool((err <= bound).all()), (f"chunk {ch}, dst2={with_dst2}: {int((err > bound).sum())} elements out of bound; worst "
+                                                f"frame {worst // (2 * d) // n}: got {float(g.flatten()[worst])} ref {float(ref.flatten()[worst])}")
+        if not with_dst2:
+            assert torch.equal(got[2 * Fn:], host[2 * Fn:]), "dst2 = None: chunk 2 must not change"
+
+
+def ohooks_temporal(x):
+    from oracle import hooks as ohooks
+    return ohooks.temporal_attention(x)
+
+
+def test_temporal_gauss_rejects_unaligned_channels():
+    h = hip()
+    buf = torch.zeros(3 * 2 * 64, 3 * 36, dtype=torch.float16, device=DEV)
+    with pytest.raises(h.VFaceHipError):
+        h.temporal_gauss(buf, buf[128:], buf[256:], F=2, n=64, C_=36, ld_src=3 * 36, fs_src=64 * 3 * 36, ld_dst=3 * 36,
+                         fs_dst=64 * 3 * 36)
+
+
+ADAIN_CASES = [(rows, C) for rows in (2, 3, 5, 1023, 5 * 4096, 32 * 4096) for C in (8, 320, 512, 520, 1280, 2048)
+               if rows * C <= 32 * 4096 * 320]  # (up to the production level-0 batch of a 32-frame clip: 32 x 4096 rows of 320)
+
+
+def _adain_bound(dt, a64, b64):
+    """Reference and per-element bound of adain_fusion on the exact 16-bit rows ``a64``, ``b64`` [rows, C] (fp64).
+    Reference: oracle.hooks.adain_fusion_for_attn(normalized=True) in fp64.
+    Bound per element, u = 2^-24.  The kernel keeps a row in registers, one wave per row: each lane sums 8 ceil(C / 512) values in
+    order and a 6-level tree folds the lanes, so every fp32 row sum is off by at most L u (sum of |terms|), L = 8 ceil(C/512) + 8.
+      mean_a, mean_b  off by  L u mean|a|,  L u mean|b|  (mean_a exact for a constant row: <= 2048 copies of an 11-bit
+        significand sum exactly in fp32's 24 bits, and the division by C returns the value)
+      k = std_b / (std_a + 1e-5)  relative  (L + 8) u  (two sums of squares, two square roots, one division)
+      o = (a - mean_a) k + mean_b  off by  dO = k L u mean|a| + L u mean|b| + (L + 10) u |k (a - mean_a)| + u |o|
+        (k's error and the roundings of the subtraction and the product scale k (a - mean_a); the final sum rounds o)
+      the global factor 1 / (std(o) + 1e-5), where std(o) is taken of the kernel's own fp32 fused values:
+        each row's mean m_r = sum_r / C is off by d_r <= (L + 1) u mean_r|o|; the row's centred M2_r = sum (o - m_r)^2 is off by
+        (L + 3) u relative (the subtraction, the square, L sums), and by exactly C d_r^2 from the mean's error; Chan's fold in fp64,
+        M2 = sum_r M2_r + C sum_r (m_r - mean)^2, adds a cross term 2 C sum_r (m_r - mean) d_r <= 2 rho M2 (Cauchy-Schwarz) and
+        C sum_r d_r^2 <= rho^2 M2 twice, rho = rms_r(d_r) / std(o).  So the std is off by (L + 3) u / 2 + rho + rho^2 relative, and
+        the square root, the + 1e-5, the division and the fp32 conversion add 4 u.  A row mean far above the spread does not
+        enter: there is no sum o^2 - N mean^2 to cancel;
+        plus what the fused values' own errors can move the std by, rms(dO) / std(o)
+      the output o / (std + 1e-5): one rounding to the 16-bit type, 0.5 ulp(ref)."""
+    from oracle import hooks as ohooks
+    C = a64.shape[1]
+    ref = ohooks.adain_fusion_for_attn(a64, b64, normalized=True)
+    ma, mb = a64.mean(-1, keepdim=True), b64.mean(-1, keepdim=True)
+    k = b64.std(-1, keepdim=True) / (a64.std(-1, keepdim=True) + 1e-5)
+    o = (a64 - ma) * k + mb
+    g = 1.0 / (o.std() + 1e-5)
+    L = 8 * -(-C // 512) + 8
+    const = (a64 == a64[:, :1]).all(-1, keepdim=True)     # (a constant 16-bit row sums exactly in fp32: its mean is exact)
+    d_o = k * L * U32 * a64.abs().mean(-1, keepdim=True) * ~const + L * U32 * b64.abs().mean(-1, keepdim=True) \
+        + (L + 10) * U32 * (k * (a64 - ma)).abs() + U32 * o.abs()
+    rho = float(((L + 1) * U32 * o.abs().mean(-1)).pow(2).mean().sqrt() / o.std())
+    rel_g = ((L + 3) / 2 + 4) * U32 + rho + rho ** 2 + float(d_o.pow(2).mean().sqrt() / o.std())
+    return ref, 0.5 * ulp(ref, dt) + g * d_o + rel_g * ref.abs()
+
+
+def _adain_case(dt, rows, C, a, b):
+    """The engine's call (engine.staged_attn1): a = chunk 0's q (or k) columns, b = dst = chunk k's, in place, ld = 3C, in a buffer
+    [2 rows, 3C] that starts as a sentinel pattern; the fused slot is the k slot (columns [C, 2C)).  Bound: _adain_bound."""
+    h = hip()
+    host = sentinel(2 * rows, 3 * C, dt)
+    host[:rows, C:2 * C] = a.to(dt)
+    host[rows:, C:2 * C] = b.to(dt)
+    ref, bound = _adain_bound(dt, host[:rows, C:2 * C].double(), host[rows:, C:2 * C].double())
+    buf = host.to(DEV)
+    own = buf[rows:, C:2 * C]
+    h.adain_fusion(buf[:rows, C:2 * C], own, own, rows=rows, C_=C, lda=3 * C, ldb=3 * C, ldd=3 * C)
+    got = buf.cpu()
+    assert torch.equal(got[:rows], host[:rows]), "chunk 0 must not change"
+    assert torch.equal(got[rows:, :C], host[rows:, :C]) and torch.equal(got[rows:, 2 * C:], host[rows:, 2 * C:]), \
+        "columns outside the fused slot must not change"
+    out = got[rows:, C:2 * C].double()
+    assert bool(torch.isfinite(out).all())
+    err = (out - ref).abs()
+    worst = int(torch.argmax(err / bound))
+    assert bool((err <= bound).all()), (f"{int((err > bound).sum())} of {err.numel()} out of bound; worst row {worst // C}: got "
+                                        f"{float(out.flatten()[worst])} ref {float(ref.flatten()[worst])} (bound {float(bound.flatten()[worst]):.3e})")
+    return out, ref, err
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("rows,C", ADAIN_CASES)
+def test_adain_fusion(dt, rows, C):
+    """fusion="adaIn": per row, the AdaIN of chunk 0's row to chunk k's over the channels, then the whole tensor divided by its
+    GLOBAL unbiased std (face_swap_utils.py:372-389).  Rows cross the 4-rows-per-block tail and reach the production row count of
+    the one-block fp64 reduce; C crosses each 512-channel register boundary.  Row 1 of ``a`` is constant: its std is 0, so its
+    fused row is b's row mean, times the global factor."""
+    a = rnd((rows, C), 11 * rows + C, torch.float32)
+    b = rnd((rows, C), 13 * rows + C, torch.float32, 2.0) + 0.5
+    a[1] = 0.75
+    out, ref, _ = _adain_case(dt, rows, C, a, b)
+    b1 = b[1].to(dt).double()
+    assert torch.equal(ref[1], ref[1, :1].expand(C)) and bool(torch.isfinite(out[1]).all())
+    assert float((out[1] - ref[1]).abs().max()) <= float(ulp(ref[1, :1], dt)), (out[1, :4], b1.mean())
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("rows,C", [(2, 320), (5, 2048), (1023, 520), (5 * 4096, 320), (32 * 4096, 320)])
+def test_adain_fusion_offset_rows(dt, rows, C):
+    """Row means far above the spread (b ~ 50 + N(0,1), a ~ -30 + N(0,1)): the fused tensor is ~50 +- 1.  Its global variance formed
+    as (sum o^2 - N mean^2) / (N - 1) from fp32 row sums would lose digits in proportion to mean^2 / var (~2500 here, a std off by
+    up to ~1e-3 relative at 2 rows of 320); from centred row partials folded with Chan's formula it keeps the bound above."""
+    a = rnd((rows, C), 17 * rows + C, torch.float32) - 30.0
+    b = rnd((rows, C), 19 * rows + C, torch.float32) + 50.0
+    _, ref, err = _adain_case(dt, rows, C, a, b)
+    print(f"adaIn offset {dt} rows={rows} C={C}: max |err| {float(err.max()):.3e} at |ref| ~ {float(ref.abs().mean()):.1f}")
+
+
+def test_adain_fusion_rejects_wide_rows():
+    h = hip()
+    C = 2056
+    a = torch.zeros(4, C, dtype=torch.float16, device=DEV)
+    with pytest.raises(h.VFaceHipError):
+        h.adain_fusion(a, a, a, rows=4, C_=C, lda=C, ldb=C, ldd=C)
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("dh,n", [(40, 1024), (8, 256), (160, 64)])
+def test_attention_engine_v_fixed_map_five_frames(dt, dh, n):
+    """fusion="fft_vfixed" with the engine's own sample map (engine.sample_map("v_fixed"), what UNetEngine._map caches on the device)
+    at B = 3 x 5: chunk 0 keeps its own v,
+    every frame of chunk k >= 1 attends with the v of chunk k's FIRST frame.  The reference v is built from the reference's own
+    expression (pnp_utils.py:255-256: v[c:2c] = v[c].repeat(c), v[2c:] = v[2c].repeat(c)), not from the map; fp64."""
+    from vface_amd.engine import sample_map
+    h = hip()
+    B, heads, c = 15, 8, 5
+    d = heads * dh
+    qkv = rnd((B, n, 3 * d), 23 + dh, dt)
+    v_map = sample_map("v_fixed", B, c).to(DEV)
+    out = torch.empty(B, n, d, dtype=dt, device=DEV)
+    qd = qkv.to(DEV)
+    scale = dh ** -0.5
+    h.attention(qd, qd[:, :, d:], qd[:, :, 2 * d:], out, B=B, heads=heads, n=n, nk=n, dh=dh, ldq=3 * d, ldk=3 * d,
+                ldv=3 * d, bsq=n * 3 * d, bsk=n * 3 * d, bsv=n * 3 * d, ldo=d, bso=n * d, scale=scale, v_map=v_map)
+    v = qkv[..., 2 * d:].double().clone()
+    v[c:2 * c] = v[c].repeat(c, 1, 1)
+    v[2 * c:] = v[2 * c].repeat(c, 1, 1)
+    sp = lambda t: t.reshape(B, n, heads, dh).permute(0, 2, 1, 3).double()
+    s_ = sp(qkv[..., :d]) @ sp(qkv[..., d:2 * d]).transpose(-1, -2) * scale
+    ref = (torch.softmax(s_, -1) @ sp(v)).permute(0, 2, 1, 3).reshape(B, n, d)
+    got = out.cpu().double()
+    per = [rel_l2(got[i], ref[i]) for i in range(B)]
+    assert max(per) < TOL[dt], [f"{e:.1e}" for e in per]

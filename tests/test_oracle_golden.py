@@ -155,6 +155,136 @@ def test_tiny_unet_modes(mode):
         assert torch.equal(g["off"], g["plain"])  # switch_on=False == unpatched forward (reference fact)
 
 
+
+# ------------------------------------------------------------------ tiny UNet, five frames: the frame-coupled hooks past F = 2
+import functools  # noqa: E402
+import sys  # noqa: E402
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+from cases import F5_KEEP, SMALL_BOUND  # noqa: E402
+
+F5_MODES = {"in_flow_fix": 64, "in_temporal": 32, "in_adaIn": 32, "in_fft_vfixed": 32, "in_fft": 32, "chunks2": 32}
+
+
+def _frames(t, F_, keep):
+    """The first ``keep`` frames of every chunk of a batch laid out [chunk 0 ; chunk 1 ; ...] with F_ frames per chunk."""
+    return torch.cat([t[k * F_:k * F_ + keep] for k in range(t.shape[0] // F_)])
+
+
+def _tiny_clip(mode, frames=5):
+    """The oracle on make_golden.py::gen_tiny_unet_f5's inputs; ``frames`` < 5 keeps the first frames of every chunk and flow
+    field (the same clip cut short).  Output cut to the tokens the fixture keeps."""
+    F_, h = 5, F5_MODES[mode]
+    x = synth.synth_normal(f"tiny5_{h}.x", (3 * F_, 9, h, h))
+    ctx = synth.synth_normal(f"tiny5_{h}.ctx", (3 * F_, 1, 768))
+    flow = [synth.synth_flow(F_ - 1, h, h)[i][None] for i in range(F_ - 1)][:frames - 1]
+    names = ounet.attn1_names(TINY)
+    reg = {}
+    ohooks.register_spa_attn_injection(reg, names, 1, switch_on=False, input_blocks=True, middle_block=True,
+                                       output_blocks=True, chunks=3)
+    if mode == "chunks2":
+        x, ctx = x[:2 * F_], ctx[:2 * F_]
+        ohooks.register_spa_attn_injection(reg, names, 1, switch_on=True, input_blocks=True, middle_block=False,
+                                           output_blocks=True, chunks=2, block_indices=[0, 1, 2])
+    else:
+        ohooks.register_spa_attn_injection(reg, names, 1, switch_on=True, input_blocks=True, middle_block=False,
+                                           output_blocks=False, flow=flow, chunks=3, block_indices=list(range(9)),
+                                           fusion=mode[3:], split_ratio_fft=0.8, alpha=0.8)
+    x, ctx = _frames(x, F_, frames), _frames(ctx, F_, frames)
+    t = torch.full((x.shape[0],), 481, dtype=torch.long)
+    return ounet.unet_forward(tiny_sd(), TINY, x, t, ctx, reg)[F5_KEEP[h]]
+
+
+@pytest.mark.parametrize("mode", list(F5_MODES))
+def test_tiny_unet_five_frames(mode):
+    """F = 5 is the smallest clip in which a frame (frame 2) has its whole +-2 temporal window inside the clip, where v_fixed's
+    "first frame" and "previous frame" differ and flow_fix's "previous frame" is not frame 0."""
+    g = load_golden("tiny_unet_f5")
+    out = _tiny_clip(mode)
+    assert out.shape == g[mode].shape
+    assert rel_l2(out, g[mode]) < 1e-5, mode
+
+
+def _temporal_window3(orig):
+    """The window-5 weights, taps at -1..1 only (a loop bound off by one): renormalised over the taps that are there, as the
+    clip ends are -- so at F = 2 it performs the very operations of the correct window."""
+    def temporal_attention(x, window_size=5, sigma=1.0):
+        offs = torch.arange(-2, 3, dtype=torch.float32)
+        g = torch.exp(-0.5 * (offs / sigma) ** 2)
+        g = g / g.sum()
+        out = torch.zeros_like(x)
+        for t in range(x.shape[0]):
+            acc, wt = 0.0, 0.0
+            for i, o in enumerate(offs):
+                j = t + int(o.item())
+                if abs(int(o.item())) <= 1 and 0 <= j < x.shape[0]:
+                    acc, wt = acc + g[i] * x[j], wt + g[i]
+            out[t] = acc / wt
+        return out
+    return temporal_attention
+
+
+def _vfixed_previous_frame(orig):
+    def apply_fusion(q, k, v, cfg, spatial_hw=None):
+        v0 = v.clone()
+        q, k, v = orig(q, k, v, cfg, spatial_hw)
+        if cfg.switch_on and cfg.chunks == 3 and cfg.fusion == "fft_vfixed":
+            c = q.shape[0] // 3
+            for ch in (1, 2):
+                for i in range(c):
+                    v[ch * c + i] = v0[ch * c + max(i - 1, 0)]
+        return q, k, v
+    return apply_fusion
+
+
+def _flow_from_frame0(orig):
+    from oracle.flow import warp_image
+
+    def align_by_flow(x, flow, alpha):
+        out = x.clone()
+        for i in range(x.shape[0] - 1):
+            f = flow[i].reshape(2, flow[i].shape[-2], flow[i].shape[-1]).float()
+            out[i + 1] = (alpha * x[i + 1] + (1.0 - alpha) * warp_image(x[0].float(), f)).to(x.dtype)
+        return out
+    return align_by_flow
+
+
+def _adain_per_frame_std(orig):
+    def adain(a, b, alpha=0.71, normalized=True):
+        fused = orig(a, b, alpha, normalized=False) / alpha
+        return fused / (fused.std(dim=tuple(range(1, fused.dim())), keepdim=True) + 1e-5)
+    return adain
+
+
+# defect: (module, attribute, patch, hook mode, blind at F = 2, asserted F = 5 separation in units of SMALL_BOUND)
+TEETH = {"vfixed_previous_frame": (ohooks, "apply_fusion", _vfixed_previous_frame, "in_fft_vfixed", True, 5.0),
+         "flow_fix_from_frame_0": (oflow, "align_by_flow", _flow_from_frame0, "in_flow_fix", True, 5.0),
+         # measured 2.3 x SMALL_BOUND (3.4e-3): the +-2 taps carry 2 x 0.054 of the weight, and only q, k of chunks 1 and 2 move.
+         # Whole-network tests at F = 5 still see it; test_kernels_gpu.py::test_temporal_gauss holds the kernel to 1 ulp.
+         "temporal_window_3": (ohooks, "temporal_attention", _temporal_window3, "in_temporal", True, 2.0),
+         # measured 0.6 x SMALL_BOUND (9.4e-4): below what a whole-network comparison can see;
+         # test_kernels_gpu.py::test_adain_fusion holds the kernel's global std to the reference's.
+         "adain_per_frame_std": (ohooks, "adain_fusion_for_attn", _adain_per_frame_std, "in_adaIn", False, 0.5)}
+
+
+@pytest.mark.parametrize("defect", list(TEETH))
+def test_five_frame_fixture_has_teeth(defect, monkeypatch):
+    """Each defect is a plausible misreading of a frame-coupled hook that a two-frame clip cannot see: at F = 2 it computes the
+    correct oracle's output bit for bit, at F = 5 it lands outside the whole-network bound of the GPU tests from the reference's
+    own output (5 x SMALL_BOUND where it reaches that; the measured figure otherwise, see TEETH).  A per-frame std in adaIn
+    differs from the global one already at F = 2; only its F = 5 separation is asserted."""
+    mod, attr, make, mode, blind_at_2, sep = TEETH[defect]
+    g = load_golden("tiny_unet_f5")
+    ok2 = _tiny_clip(mode, frames=2)
+    monkeypatch.setattr(mod, attr, make(getattr(mod, attr)))
+    bad2, bad5 = _tiny_clip(mode, frames=2), _tiny_clip(mode)
+    e2, e5 = rel_l2(bad2, ok2), rel_l2(bad5, g[mode])
+    print(f"{defect}: F = 2 {e2:.2e} from the correct oracle, F = 5 {e5:.2e} from the fixture ({e5 / SMALL_BOUND:.1f} x SMALL_BOUND)")
+    if blind_at_2:
+        assert e2 < 1e-6, (defect, e2)
+    assert e5 >= sep * SMALL_BOUND, (defect, e5)
+
+
 # ------------------------------------------------------------------ DDIM schedule, sampling loop, inversion
 @pytest.mark.parametrize("S", [50, 20, 25])
 def test_schedule(S):

@@ -427,8 +427,10 @@ __global__ __launch_bounds__(256) void temporal_gauss_kernel(const typename TT::
 
 // fusion="adaIn" (face_swap_utils.py:372-389 with normalized=True): per token, AdaIN of the structure row `a`
 // to the own row `b` over the channel axis (unbiased std), then the whole tensor is divided by its GLOBAL
-// unbiased std.  Pass 1: one wave per token row writes the fused row (fp32) and block partial (sum, sumsq);
-// pass 2 (adain_scale) folds the partials in fp64 and writes fused / (std + 1e-5) in the 16-bit type.
+// unbiased std.  Pass 1: one wave per token row writes the fused row (fp32) and the row's partial (sum, centred sum of
+// squares M2); the reduce folds the partials in fp64 with Chan's formula, M2 = sum_r M2_r + C sum_r (mean_r - mean)^2, so a
+// row mean far above the spread costs no digits (sum o^2 - N mean^2 would cancel them); adain_scale writes
+// fused / (std + 1e-5) in the 16-bit type.
 template <class TT, int CH8>
 __global__ __launch_bounds__(256) void adain_rows_kernel(const typename TT::elem* __restrict__ a, long lda,
                                                          const typename TT::elem* __restrict__ b, long ldb,
@@ -436,10 +438,8 @@ __global__ __launch_bounds__(256) void adain_rows_kernel(const typename TT::elem
                                                          double* __restrict__ partial) {
     using E = typename TT::elem;
     using V8 = typename TT::v8;
-    __shared__ double red[8];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wv;
-    double bs = 0.0, bq = 0.0;
     if (row < rows) {
         float va[CH8][8], vb[CH8][8];
         float sa = 0.f, sb = 0.f;
@@ -471,42 +471,57 @@ __global__ __launch_bounds__(256) void adain_rows_kernel(const typename TT::elem
         }
         const float sda = sqrtf(wave_sum(qa) / (float)(C - 1)), sdb = sqrtf(wave_sum(qb) / (float)(C - 1));
         const float k = sdb / (sda + 1e-5f);
-        float s = 0.f, q = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int i = 0; i < CH8; ++i) {
             const int c = (i * 64 + lane) * 8;
             if (c < C) {
-                float o[8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { o[j] = (va[i][j] - ma) * k + mb; s += o[j]; q += o[j] * o[j]; }
-                *reinterpret_cast<float4*>(fused + (long)row * ldf + c) = make_float4(o[0], o[1], o[2], o[3]);
-                *reinterpret_cast<float4*>(fused + (long)row * ldf + c + 4) = make_float4(o[4], o[5], o[6], o[7]);
+                for (int j = 0; j < 8; ++j) { va[i][j] = (va[i][j] - ma) * k + mb; s += va[i][j]; }   // va now holds the fused row
+                *reinterpret_cast<float4*>(fused + (long)row * ldf + c) = make_float4(va[i][0], va[i][1], va[i][2], va[i][3]);
+                *reinterpret_cast<float4*>(fused + (long)row * ldf + c + 4) = make_float4(va[i][4], va[i][5], va[i][6], va[i][7]);
             }
         }
-        bs = (double)wave_sum(s); bq = (double)wave_sum(q);
-    }
-    if (lane == 0) { red[2 * wv] = bs; red[2 * wv + 1] = bq; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = red[0] + red[2] + red[4] + red[6];
-        partial[2 * blockIdx.x + 1] = red[1] + red[3] + red[5] + red[7];
+        const float so = wave_sum(s), mo = so / (float)C;
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < CH8; ++i) {
+            const int c = (i * 64 + lane) * 8;
+            if (c < C) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { const float e = va[i][j] - mo; q += e * e; }
+            }
+        }
+        const float m2 = wave_sum(q);
+        if (lane == 0) { partial[2 * (long)row] = (double)so; partial[2 * (long)row + 1] = (double)m2; }
     }
 }
 
-__global__ void adain_reduce_kernel(const double* __restrict__ partial, int nblocks, double count, float* __restrict__ inv) {
+// Chan's parallel variance over the row partials (sum_r, M2_r), C values per row, all in fp64.
+__global__ void adain_reduce_kernel(const double* __restrict__ partial, int rows, int C, float* __restrict__ inv) {
     __shared__ double ss[256], qq[256];
-    double s = 0.0, q = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 256) { s += partial[2 * i]; q += partial[2 * i + 1]; }
-    ss[threadIdx.x] = s; qq[threadIdx.x] = q;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < rows; i += 256) s += partial[2 * (long)i];
+    ss[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { ss[threadIdx.x] += ss[threadIdx.x + o]; qq[threadIdx.x] += qq[threadIdx.x + o]; }
+        if (threadIdx.x < o) ss[threadIdx.x] += ss[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double count = (double)rows * C, mean = ss[0] / count;
+    double q = 0.0;
+    for (int i = threadIdx.x; i < rows; i += 256) {
+        const double dm = partial[2 * (long)i] / C - mean;
+        q += partial[2 * (long)i + 1] + C * dm * dm;
+    }
+    qq[threadIdx.x] = q;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) qq[threadIdx.x] += qq[threadIdx.x + o];
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const double mean = ss[0] / count;
-        double var = (qq[0] - count * mean * mean) / (count - 1.0);  // unbiased, as torch.std
-        if (var < 0.0) var = 0.0;
+        const double var = qq[0] / (count - 1.0);  // unbiased, as torch.std
         inv[0] = (float)(1.0 / (sqrt(var) + 1e-5));
     }
 }
@@ -971,8 +986,7 @@ int vf_launch_temporal_gauss(const void* src, long ld_src, long fs_src, void* ds
 }
 
 size_t vf_adain_workspace_bytes(long rows, int C) {
-    const long nblocks = (rows + 3) / 4;
-    return (size_t)rows * C * sizeof(float) + (size_t)nblocks * 2 * sizeof(double) + 256;
+    return (size_t)rows * C * sizeof(float) + (size_t)rows * 2 * sizeof(double) + 256;
 }
 
 int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst, long ldd, long rows, int C, void* ws,
@@ -984,7 +998,7 @@ int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst,
     float* fused = (float*)ws;
     const long nblocks = (rows + 3) / 4;
     double* partial = (double*)((char*)ws + (((size_t)rows * C * sizeof(float) + 15) & ~(size_t)15));
-    float* inv = (float*)(partial + 2 * nblocks);
+    float* inv = (float*)(partial + 2 * rows);
     const int ch8 = (C + 511) / 512;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
@@ -995,7 +1009,7 @@ int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst,
             case 3: hipLaunchKernelGGL((adain_rows_kernel<TT, 3>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
             default: hipLaunchKernelGGL((adain_rows_kernel<TT, 4>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
         }
-        hipLaunchKernelGGL(adain_reduce_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, (int)nblocks, (double)rows * C, inv);
+        hipLaunchKernelGGL(adain_reduce_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, (int)rows, C, inv);
         hipLaunchKernelGGL((adain_scale_kernel<TT>), dim3(grid_for(rows * (C / 8))), dim3(256), 0, stream, (const float*)fused, (long)C,
                            (const float*)inv, (E*)dst, ldd, rows, C);
     });

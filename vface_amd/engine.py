@@ -168,6 +168,22 @@ def plan_fusion(cfg: Optional[HookCfg], N: int, n: int, clip_flow_hw=None, live:
     return pl
 
 
+def sample_map(kind: str, B: int, c: int) -> torch.Tensor:
+    """The attention kernel's per-sample source map (int32 on the CPU) for a batch of B samples in chunks of c frames."""
+    idx = torch.arange(B, dtype=torch.int32)
+    if kind == "qk_replace":
+        return idx % c
+    if kind in ("share_qk", "share_v"):
+        # _st_front_shared with a warp: slot 0 = chunk 1's warped q|k, slot 1 = chunk 0's q|k and the v of chunks 0, 1
+        m = torch.where(idx < c, idx + c, idx)            # chunk 0 reads slot 1 (q|k and v)
+        if kind == "share_qk":
+            m = torch.where((idx >= c) & (idx < 2 * c), idx - c, m)      # chunk 1's q|k: slot 0 (its v stays in slot 1 = itself)
+        return m
+    if kind == "v_fixed":  # chunk 0 identity, chunk k >= 1 -> its first frame
+        return torch.where(idx < c, idx, (idx // c) * c)
+    raise ValueError(kind)
+
+
 def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, rowbias=None, residual=None,
                  residual32=None, out32=None, chunks: int = 3):
     """Hooked attn1 for fusion modes that edit q,k with their own kernels ("temporal", "adaIn"; pnp_utils.py:145-160):
@@ -637,18 +653,7 @@ class UNetEngine:
     def _map(self, kind: str, B: int, c: int) -> torch.Tensor:
         key = (kind, B, c)
         if key not in self._maps:
-            if kind == "qk_replace":
-                m = torch.arange(B, dtype=torch.int32) % c
-            elif kind in ("share_qk", "share_v"):
-                # _st_front_shared with a warp: slot 0 = chunk 1's warped q|k, slot 1 = chunk 0's q|k and the v of chunks 0, 1
-                idx = torch.arange(B, dtype=torch.int32)
-                m = torch.where(idx < c, idx + c, idx)            # chunk 0 reads slot 1 (q|k and v)
-                if kind == "share_qk":
-                    m = torch.where((idx >= c) & (idx < 2 * c), idx - c, m)      # chunk 1's q|k: slot 0 (its v stays in slot 1 = itself)
-            else:  # v_fixed: chunk 0 identity, chunk k >= 1 -> its first frame
-                idx = torch.arange(B, dtype=torch.int32)
-                m = torch.where(idx < c, idx, (idx // c) * c)
-            self._maps[key] = m.to(self.device)
+            self._maps[key] = sample_map(kind, B, c).to(self.device)
         return self._maps[key]
 
     # ------------------------------------------------------------------ primitive steps
