@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VFACE_ABI_VERSION 7   /* 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
+#define VFACE_ABI_VERSION 7   /* 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
 
 #define VFACE_OK 0
 #define VFACE_ERR_ARG (-1)
@@ -399,6 +399,27 @@ int vface_temporal_gauss(const void* src, int64_t ld_src, int64_t fs_src, void* 
 size_t vface_adain_workspace_bytes(int64_t rows, int C);
 int vface_adain_fusion(const void* a, int64_t lda, const void* b, int64_t ldb, void* dst, int64_t ldd, int64_t rows, int C,
                        void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* The two frame-coupled modes on a FRAME SHARD (parallel.FrameShard: this rank holds global frames [first, first + F) of a clip
+ * of F_total frames; the forward exchanges what the edit needs from the other ranks between these launches).
+ * vface_temporal_gauss on the shard: window frames outside it are read from prev (global frames first-2, first-1 at slab 0, 1)
+ * and next (global first+F, first+F+1 at slab 0, 1), slab s / token t / channel c at base[s*fs_halo + t*ld_halo + c]; the
+ * window still ends only at the clip's real ends (0, F_total).  prev may be NULL iff first == 0, next iff first + F == F_total;
+ * slabs whose frame lies outside the clip are not read.  The shard's rows equal vface_temporal_gauss's rows of the whole clip
+ * bit for bit (same taps, order and weights).  No workspace; capturable. */
+int vface_temporal_gauss_halo(const void* src, int64_t ld_src, int64_t fs_src, const void* prev, const void* next, int64_t ld_halo,
+                              int64_t fs_halo, void* dst1, void* dst2, int64_t ld_dst, int64_t fs_dst, int F, int first, int F_total,
+                              int n, int C, int dtype, void* stream);
+/* vface_adain_fusion in two launches around a cross-rank gather.  vface_adain_rows: the per-row AdaIN of this shard's rows into
+ * the workspace (fp32) and each row's partial (sum, centred sum of squares) into partial [rows][2] (fp64).
+ * vface_adain_reduce_scale: the global unbiased std from partial [partial_rows][2] -- every rank's partials in global row order,
+ * the array vface_adain_fusion reduces over -- then dst [rows][C] = fused / (std + 1e-5) from the workspace vface_adain_rows
+ * filled (same rows, C).  Rows + reduce_scale over the whole array equal vface_adain_fusion bit for bit.  Capturable. */
+size_t vface_adain_rows_workspace_bytes(int64_t rows, int C);
+int vface_adain_rows(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t rows, int C, double* partial, void* workspace,
+                     size_t workspace_bytes, int dtype, void* stream);
+int vface_adain_reduce_scale(const double* partial, int64_t partial_rows, int C, void* workspace, size_t workspace_bytes, void* dst,
+                             int64_t ldd, int64_t rows, int dtype, void* stream);
 
 /* Small ops */
 /* util.py:151-171 timestep_embedding: out[N][dim] = [cos(t f_i) | sin(t f_i)] */

@@ -431,6 +431,25 @@ int vface_adain_fusion(const void* a, int64_t lda, const void* b, int64_t ldb, v
     if (rows > 0 && C > 0 && workspace_bytes < vf_adain_workspace_bytes(rows, C)) return VFACE_ERR_WORKSPACE;
     return vf_launch_adain(a, lda, b, ldb, dst, ldd, rows, C, workspace, dtype, S(stream));
 }
+int vface_temporal_gauss_halo(const void* src, int64_t ld_src, int64_t fs_src, const void* prev, const void* next, int64_t ld_halo,
+                              int64_t fs_halo, void* dst1, void* dst2, int64_t ld_dst, int64_t fs_dst, int F, int first, int F_total,
+                              int n, int C, int dtype, void* stream) {
+    return vf_launch_temporal_gauss_halo(src, ld_src, fs_src, prev, next, ld_halo, fs_halo, dst1, dst2, ld_dst, fs_dst, F, first,
+                                         F_total, n, C, dtype, S(stream));
+}
+size_t vface_adain_rows_workspace_bytes(int64_t rows, int C) {
+    return rows > 0 && C > 0 ? vf_adain_rows_workspace_bytes(rows, C) : 0;
+}
+int vface_adain_rows(const void* a, int64_t lda, const void* b, int64_t ldb, int64_t rows, int C, double* partial, void* workspace,
+                     size_t workspace_bytes, int dtype, void* stream) {
+    if (rows > 0 && C > 0 && workspace_bytes < vf_adain_rows_workspace_bytes(rows, C)) return VFACE_ERR_WORKSPACE;
+    return vf_launch_adain_rows(a, lda, b, ldb, rows, C, partial, workspace, dtype, S(stream));
+}
+int vface_adain_reduce_scale(const double* partial, int64_t partial_rows, int C, void* workspace, size_t workspace_bytes, void* dst,
+                             int64_t ldd, int64_t rows, int dtype, void* stream) {
+    if (rows > 0 && C > 0 && workspace_bytes < vf_adain_rows_workspace_bytes(rows, C)) return VFACE_ERR_WORKSPACE;
+    return vf_launch_adain_reduce_scale(partial, partial_rows, C, workspace, dst, ldd, rows, dtype, S(stream));
+}
 
 int vface_timestep_embedding(const int64_t* t, void* out, int N, int dim, int dtype, void* stream) {
     return vf_launch_timestep_embedding(reinterpret_cast<const long long*>(t), out, N, dim, dtype, S(stream));

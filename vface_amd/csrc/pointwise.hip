@@ -425,6 +425,51 @@ __global__ __launch_bounds__(256) void temporal_gauss_kernel(const typename TT::
     }
 }
 
+// temporal_gauss_kernel on a FRAME SHARD: local frame f is global frame first + f of a clip of Ftot frames; window frames
+// outside the shard come from prev ([2] slabs: global first-2, first-1) and next ([2] slabs: global first+F, first+F+1).
+// Same taps in the same order with the same fp32 weights and the same skips at the clip's real ends as the unsharded kernel,
+// so a shard's rows are that kernel's rows bit for bit.
+template <class TT>
+__global__ __launch_bounds__(256) void temporal_gauss_halo_kernel(const typename TT::elem* __restrict__ src, long ld_src,
+                                                                  long fs_src, const typename TT::elem* __restrict__ prev,
+                                                                  const typename TT::elem* __restrict__ next, long ld_h, long fs_h,
+                                                                  typename TT::elem* __restrict__ dst1,
+                                                                  typename TT::elem* __restrict__ dst2, long ld_dst,
+                                                                  long fs_dst, int F, int first, int Ftot, int n, int C) {
+    using E = typename TT::elem;
+    using V8 = typename TT::v8;
+    const float g1 = 0.60653065971263342f, g2 = 0.13533528323661270f;  // exp(-0.5), exp(-2)
+    const float gs = 1.0f + 2.0f * g1 + 2.0f * g2;
+    const float w[5] = {g2 / gs, g1 / gs, 1.0f / gs, g1 / gs, g2 / gs};
+    const int c8 = C / 8, f = blockIdx.y;
+    const long total = (long)n * c8;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long tok = i / c8;
+        const int cc = (int)(i - tok * c8) * 8;
+        float acc[8], wt = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+#pragma unroll
+        for (int o = -2; o <= 2; ++o) {
+            const int gf = first + f + o;
+            if (gf < 0 || gf >= Ftot) continue;
+            const int lf = f + o;
+            const E* p = lf < 0 ? prev + (long)(lf + 2) * fs_h + tok * ld_h
+                       : lf >= F ? next + (long)(lf - F) * fs_h + tok * ld_h
+                                 : src + (long)lf * fs_src + tok * ld_src;
+            const V8 v = *reinterpret_cast<const V8*>(p + cc);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] += w[o + 2] * to_f32(v[j]);
+            wt += w[o + 2];
+        }
+        V8 o8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o8[j] = from_f32<E>(acc[j] / wt);
+        *reinterpret_cast<V8*>(dst1 + (long)f * fs_dst + tok * ld_dst + cc) = o8;
+        if (dst2) *reinterpret_cast<V8*>(dst2 + (long)f * fs_dst + tok * ld_dst + cc) = o8;
+    }
+}
+
 // fusion="adaIn" (face_swap_utils.py:372-389 with normalized=True): per token, AdaIN of the structure row `a`
 // to the own row `b` over the channel axis (unbiased std), then the whole tensor is divided by its GLOBAL
 // unbiased std.  Pass 1: one wave per token row writes the fused row (fp32) and the row's partial (sum, centred sum of
@@ -985,8 +1030,71 @@ int vf_launch_temporal_gauss(const void* src, long ld_src, long fs_src, void* ds
     return ok();
 }
 
+int vf_launch_temporal_gauss_halo(const void* src, long ld_src, long fs_src, const void* prev, const void* next, long ld_h,
+                                  long fs_h, void* dst1, void* dst2, long ld_dst, long fs_dst, int F, int first, int Ftot, int n,
+                                  int C, int dtype, hipStream_t stream) {
+    if (!src || !dst1 || F <= 0 || n <= 0 || C <= 0 || first < 0 || Ftot < first + F) return VF_ERR_ARG;
+    if ((first > 0 && !prev) || (first + F < Ftot && !next)) return VF_ERR_ARG;   // a window frame with no slab to read
+    if ((prev || next) && (ld_h < C || fs_h < (long)n * ld_h)) return VF_ERR_SHAPE;
+    if ((C & 7) || (ld_src & 7) || (ld_dst & 7) || (fs_src & 7) || (fs_dst & 7) || (ld_h & 7) || (fs_h & 7)) return VF_ERR_ALIGN;
+    if (((uintptr_t)src | (uintptr_t)dst1 | (uintptr_t)dst2 | (uintptr_t)prev | (uintptr_t)next) & 15) return VF_ERR_ALIGN;
+    const long total = (long)n * (C / 8);
+    dim3 grid(grid_for(total, 256, 2048), F);
+    DISPATCH_DTYPE(dtype, {
+        using E = typename TT::elem;
+        hipLaunchKernelGGL((temporal_gauss_halo_kernel<TT>), grid, dim3(256), 0, stream, (const E*)src, ld_src, fs_src, (const E*)prev,
+                           (const E*)next, ld_h, fs_h, (E*)dst1, (E*)dst2, ld_dst, fs_dst, F, first, Ftot, n, C);
+    });
+    return ok();
+}
+
 size_t vf_adain_workspace_bytes(long rows, int C) {
     return (size_t)rows * C * sizeof(float) + (size_t)rows * 2 * sizeof(double) + 256;
+}
+
+// adaIn in two launches around a cross-rank gather of the row partials: rows (fused row into the workspace + partial), then
+// reduce over a [partial_rows][2] array (every rank's partials in global row order) and scale.  The kernels vf_launch_adain runs.
+size_t vf_adain_rows_workspace_bytes(long rows, int C) {
+    return (((size_t)rows * C * sizeof(float) + 15) & ~(size_t)15) + 256;
+}
+
+int vf_launch_adain_rows(const void* a, long lda, const void* b, long ldb, long rows, int C, double* partial, void* ws,
+                         int dtype, hipStream_t stream) {
+    if (!a || !b || !partial || !ws || rows <= 0 || C <= 1) return VF_ERR_ARG;
+    if ((C & 7) || (lda & 7) || (ldb & 7)) return VF_ERR_ALIGN;
+    if (((uintptr_t)a | (uintptr_t)b | (uintptr_t)ws | (uintptr_t)partial) & 15) return VF_ERR_ALIGN;
+    if (C > 2048 || rows > 0x7fffffffL) return VF_ERR_SHAPE;
+    float* fused = (float*)ws;
+    const long nblocks = (rows + 3) / 4;
+    const int ch8 = (C + 511) / 512;
+    DISPATCH_DTYPE(dtype, {
+        using E = typename TT::elem;
+        dim3 g((unsigned)nblocks);
+        switch (ch8) {
+            case 1: hipLaunchKernelGGL((adain_rows_kernel<TT, 1>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
+            case 2: hipLaunchKernelGGL((adain_rows_kernel<TT, 2>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
+            case 3: hipLaunchKernelGGL((adain_rows_kernel<TT, 3>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
+            default: hipLaunchKernelGGL((adain_rows_kernel<TT, 4>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
+        }
+    });
+    return ok();
+}
+
+int vf_launch_adain_reduce_scale(const double* partial, long partial_rows, int C, void* ws, void* dst, long ldd, long rows,
+                                 int dtype, hipStream_t stream) {
+    if (!partial || !ws || !dst || partial_rows <= 0 || rows <= 0 || C <= 1) return VF_ERR_ARG;
+    if (rows > partial_rows || partial_rows > 0x7fffffffL || C > 2048) return VF_ERR_SHAPE;
+    if ((C & 7) || (ldd & 7)) return VF_ERR_ALIGN;
+    if (((uintptr_t)dst | (uintptr_t)ws | (uintptr_t)partial) & 15) return VF_ERR_ALIGN;
+    const float* fused = (const float*)ws;
+    float* inv = (float*)((char*)ws + (((size_t)rows * C * sizeof(float) + 15) & ~(size_t)15));
+    DISPATCH_DTYPE(dtype, {
+        using E = typename TT::elem;
+        hipLaunchKernelGGL(adain_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, (int)partial_rows, C, inv);
+        hipLaunchKernelGGL((adain_scale_kernel<TT>), dim3(grid_for(rows * (C / 8))), dim3(256), 0, stream, fused, (long)C,
+                           (const float*)inv, (E*)dst, ldd, rows, C);
+    });
+    return ok();
 }
 
 int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst, long ldd, long rows, int C, void* ws,

@@ -243,3 +243,11 @@ int vf_launch_temporal_gauss(const void* src, long ld_src, long fs_src, void* ds
 size_t vf_adain_workspace_bytes(long rows, int C);
 int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst, long ldd, long rows, int C, void* ws,
                     int dtype, hipStream_t stream);
+int vf_launch_temporal_gauss_halo(const void* src, long ld_src, long fs_src, const void* prev, const void* next, long ld_h,
+                                  long fs_h, void* dst1, void* dst2, long ld_dst, long fs_dst, int F, int first, int Ftot, int n,
+                                  int C, int dtype, hipStream_t stream);
+size_t vf_adain_rows_workspace_bytes(long rows, int C);
+int vf_launch_adain_rows(const void* a, long lda, const void* b, long ldb, long rows, int C, double* partial, void* ws,
+                         int dtype, hipStream_t stream);
+int vf_launch_adain_reduce_scale(const double* partial, long partial_rows, int C, void* ws, void* dst, long ldd, long rows,
+                                 int dtype, hipStream_t stream);

@@ -185,15 +185,18 @@ def sample_map(kind: str, B: int, c: int) -> torch.Tensor:
 
 
 def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, rowbias=None, residual=None,
-                 residual32=None, out32=None, chunks: int = 3):
+                 residual32=None, out32=None, chunks: int = 3, edit: Optional[Callable] = None):
     """Hooked attn1 for fusion modes that edit q,k with their own kernels ("temporal", "adaIn"; pnp_utils.py:145-160):
-    full projection -> edit chunk 1 / chunk 2 q,k in the qkv buffer -> attention -> out-projection."""
+    full projection -> edit chunk 1 / chunk 2 q,k in the qkv buffer -> attention -> out-projection.
+    ``edit(qkv, F)``: replaces the built-in edit (a frame-sharded forward: ``UNetEngine._staged_sharded_edit``)."""
     dev, dt = x16.device, x16.dtype
     c = B // chunks          # (chunks < 3: the batch came without its last chunk(s), plan_fusion `live`)
     Fn = c * n
     qkv = torch.empty(B * n, 3 * d, dtype=dt, device=dev)
     hip.gemm(x16, wqkv, qkv, M=B * n, N=3 * d, K=x16.shape[1], lda=x16.stride(0), ldc=3 * d)
-    if mode == "temporal" and chunks > 1:
+    if edit is not None:
+        edit(qkv, c)
+    elif mode == "temporal" and chunks > 1:
         hip.temporal_gauss(qkv, qkv[Fn:], qkv[2 * Fn:] if chunks > 2 else None, F=c, n=n, C_=2 * d, ld_src=3 * d, fs_src=n * 3 * d,
                            ld_dst=3 * d, fs_dst=n * 3 * d)
     elif mode == "temporal":
@@ -315,6 +318,7 @@ class _GraphSegments:
         # what the engine reads from its exchange object
         if inner is not None:
             self.rank, self.world, self.first, self.count = inner.rank, inner.world, inner.first, inner.count
+            self.total = getattr(inner, "total", None)
 
     def begin(self):
         self.cur = torch.cuda.CUDAGraph()
@@ -354,14 +358,25 @@ class _GraphSegments:
         self.index = int(k)
 
     def start_exchange(self, tail: torch.Tensor):
+        recv = torch.empty_like(tail) if self.inner.rank > 0 else None      # (allocated in the shared pool: lives with the graphs)
+        return self._start("start_exchange", tail, recv)
+
+    def start_temporal(self, edges: torch.Tensor):
+        """The temporal halo (``FrameShard.start_temporal``): every rank receives (frames on both sides)."""
+        return self._start("start_temporal", edges, torch.empty_like(edges))
+
+    def start_gather(self, part: torch.Tensor):
+        """The adaIn row-partial gather (``FrameShard.start_gather``): the gathered array lands in a persistent buffer."""
+        return self._start("start_gather", part, torch.empty(self.inner.gather_shape(part), dtype=part.dtype, device=part.device))
+
+    def _start(self, method: str, tail: torch.Tensor, recv: Optional[torch.Tensor]):
         inner, state, k = self.inner, {}, self.index
-        recv = torch.empty_like(tail) if inner.rank > 0 else None      # (allocated in the shared pool: lives with the graphs)
         self.keep += [tail, recv, state]
 
         def op():
             if hasattr(inner, "set_index"):
                 inner.set_index(k)                 # (the replayed host call states the same ordinal as the captured forward did)
-            state["h"] = inner.start_exchange(tail, recv=recv)
+            state["h"] = getattr(inner, method)(tail, recv=recv)
         self.end(op)
         op()                       # the capture pass exchanges for real too (garbage slabs): the ranks' calls stay paired
         self.n_started += 1
@@ -400,6 +415,7 @@ class _CountingExchange:
     def __init__(self, inner):
         self.inner, self.tails = inner, []
         self.rank, self.world, self.first, self.count = inner.rank, inner.world, inner.first, inner.count
+        self.total = getattr(inner, "total", None)
 
     def set_index(self, k: int) -> None:
         if hasattr(self.inner, "set_index"):
@@ -408,6 +424,14 @@ class _CountingExchange:
     def start_exchange(self, tail, recv=None):
         self.tails.append(tail)
         return self.inner.start_exchange(tail, recv=recv) if recv is not None else self.inner.start_exchange(tail)
+
+    def start_temporal(self, edges, recv=None):
+        self.tails.append(("temporal", edges))
+        return self.inner.start_temporal(edges, recv=recv)
+
+    def start_gather(self, part, recv=None):
+        self.tails.append(("gather", part))
+        return self.inner.start_gather(part, recv=recv)
 
     def finish_exchange(self, handle):
         return self.inner.finish_exchange(handle)
@@ -788,12 +812,12 @@ class UNetEngine:
         res_kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid, "ldr": resid.stride(0)}
         pl = plan_fusion(cfg, N, n, self.halo_hw if self.halo_exchange is not None else None, self.live_chunks)
         if pl["staged"]:
-            if self.halo_exchange is not None:
-                raise NotImplementedError(f"fusion={pl['staged']!r} couples frames beyond one neighbour (temporal: +-2 "
-                                          "frames; adaIn: a global std) and is not sharded across GPUs")
+            # frames sharded across ranks: the edit exchanges what it needs from the other ranks (temporal: +-2 frames; adaIn:
+            # the row partials of the global std) between the projection and the attention
+            edit = self._staged_sharded_edit(pl["staged"], n, d, pl["chunks"]) if self.halo_exchange is not None else None
             kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid}
             return staged_attn1(xln, p["wqkv"], p["wo"]["w"], p["wo"]["b"], out, B=N, n=n, d=d, heads=heads,
-                                mode=pl["staged"], rowbias=a2vec, chunks=pl["chunks"], **kw)
+                                mode=pl["staged"], rowbias=a2vec, chunks=pl["chunks"], edit=edit, **kw)
         fusion, chunks, flow, alpha, v_fixed = pl["fusion"], pl["chunks"], pl["flow"], pl["alpha"], pl["v_fixed"]
         wlin = self._wlin(p, *pl["wlin"]) if pl["wlin"] else None
         qk_map = self._map("qk_replace", N, N // chunks) if fusion == hip.FUSION_REPLACE else None
@@ -1171,14 +1195,71 @@ class UNetEngine:
                                         o32[r0:] if o32 is not None else None, cs[r0 // 64:] if cs is not None else None,
                                         M=rows, C_=c, rows_per_sample=n)
 
-    def _halo_start(self, tail: torch.Tensor):
-        """``halo_exchange.start_exchange`` with the exchange's ordinal inside this forward stated first (FrameShard.set_index)."""
+    def _halo_start(self, tail: torch.Tensor, kind: str = "exchange"):
+        """``halo_exchange.start_exchange`` (``kind`` "temporal" / "gather": ``start_temporal`` / ``start_gather``) with the
+        exchange's ordinal inside this forward stated first (FrameShard.set_index)."""
         ex = self.halo_exchange
         k = getattr(self, "_halo_k", 0)
         self._halo_k = k + 1
         if hasattr(ex, "set_index"):
             ex.set_index(k)
-        return ex.start_exchange(tail)
+        return getattr(ex, "start_" + kind)(tail)
+
+    def _halo_finish(self, handle):
+        """``halo_exchange.finish_exchange``, timed with HIP events when ``exchange_events`` asks for it."""
+        ev = self.exchange_events if not isinstance(self.halo_exchange, _GraphSegments) else None
+        if ev is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        got = self.halo_exchange.finish_exchange(handle)
+        if ev is not None:
+            e1.record()
+            ev.append((e0, e1))
+        return got
+
+    def _staged_sharded_edit(self, mode: str, n: int, d: int, chunks: int):
+        """The q|k edit of ``staged_attn1`` on a frame shard (``halo_exchange``: this rank holds global frames [first, first + F)
+        of ``total``), as ``edit(qkv, F)``: the same kernels on the same numbers as the unsharded edit, with the exchange between
+        the projection and the edit -- hence the unsharded rows, bit for bit.
+        temporal: chunk 0's first two and last two frames go to the other ranks, the two frames before and after the shard come
+          back (``start_temporal``), and the halo form of the Gaussian reads them (``vface_temporal_gauss_halo``).
+        adaIn: every (q | k, chunk) pair's row partials (``vface_adain_rows``) are gathered over the ranks in ONE exchange
+          (``start_gather``: global row order), then each pair's global std and scale (``vface_adain_reduce_scale``)."""
+        ex = self.halo_exchange
+        first, total = ex.first, ex.total
+
+        def temporal(qkv, F_):
+            if chunks < 2:
+                return                              # (chunk 0 alone: nothing to smooth, nothing to exchange -- on every rank)
+            Fn, lo = F_ * n, min(F_, 2)
+            edges = self._new(4 * n, 2 * d)
+            hip.copy2d(qkv, edges, rows=lo * n, cols=2 * d, ld_src=3 * d, ld_dst=2 * d)
+            hip.copy2d(qkv[(F_ - lo) * n:], edges[(4 - lo) * n:], rows=lo * n, cols=2 * d, ld_src=3 * d, ld_dst=2 * d)
+            halo = self._halo_finish(self._halo_start(edges.view(4, n, 2 * d), "temporal")).reshape(4 * n, 2 * d)
+            hip.temporal_gauss_halo(qkv, halo if first > 0 else None, halo[2 * n:] if first + F_ < total else None, qkv[Fn:],
+                                    qkv[2 * Fn:] if chunks > 2 else None, F=F_, first=first, F_total=total, n=n, C_=2 * d,
+                                    ld_src=3 * d, fs_src=n * 3 * d, ld_dst=3 * d, fs_dst=n * 3 * d, ld_halo=2 * d, fs_halo=n * 2 * d)
+
+        def adain(qkv, F_):
+            pairs = [(col, ch) for col in (0, d) for ch in range(1, chunks)]      # (the unsharded edit's order)
+            if not pairs:
+                return
+            Fn = F_ * n
+            part = torch.empty(len(pairs), Fn, 2, dtype=torch.float64, device=qkv.device)
+            ws = [torch.empty(hip.adain_rows_workspace_bytes(Fn, d), dtype=torch.uint8, device=qkv.device) for _ in pairs]
+            for i, (col, ch) in enumerate(pairs):
+                own = qkv[ch * Fn:(ch + 1) * Fn, col:col + d]
+                hip.adain_rows(qkv[:Fn, col:col + d], own, part[i], ws[i], rows=Fn, C_=d, lda=3 * d, ldb=3 * d)
+            glob = self._halo_finish(self._halo_start(part, "gather"))
+            for i, (col, ch) in enumerate(pairs):
+                hip.adain_reduce_scale(glob[i], ws[i], qkv[ch * Fn:(ch + 1) * Fn, col:col + d], partial_rows=glob.shape[1], rows=Fn,
+                                       C_=d, ldd=3 * d)
+
+        if mode == "temporal":
+            return temporal
+        if mode == "adaIn":
+            return adain
+        raise ValueError(mode)
 
     def _ffn_ok(self, M: int, c: int) -> bool:
         """``vface_ffn_fused_supported`` per (rows, width), asked once (a ctypes call per block per forward otherwise)."""

@@ -101,6 +101,11 @@ SIGNATURES = {
     "vface_temporal_gauss": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "vface_adain_workspace_bytes": (_sz, [_i64, _i32]),
     "vface_adain_fusion": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _sz, _i32, _vp]),
+    "vface_temporal_gauss_halo": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
+                                            _i32, _i32, _vp]),
+    "vface_adain_rows_workspace_bytes": (_sz, [_i64, _i32]),
+    "vface_adain_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _sz, _i32, _vp]),
+    "vface_adain_reduce_scale": (C.c_int, [_vp, _i64, _i32, _vp, _sz, _vp, _i64, _i64, _i32, _vp]),
     "vface_timestep_embedding": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "vface_silu": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     "vface_softmax_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _vp]),
@@ -657,6 +662,35 @@ def adain_fusion(a, b, dst, *, rows, C_, lda, ldb, ldd):
     rc = lib.vface_adain_fusion(_p(a), lda, _p(b), ldb, _p(dst), ldd, rows, C_, _p(ws), ws.numel(), dtype_code(a.dtype),
                                 _stream())
     _check(rc, "vface_adain_fusion")
+
+
+def temporal_gauss_halo(src, prev, next_, dst1, dst2, *, F, first, F_total, n, C_, ld_src, fs_src, ld_dst, fs_dst,
+                        ld_halo=0, fs_halo=0):
+    """``temporal_gauss`` on frames [first, first + F) of an F_total-frame clip; ``prev`` / ``next_``: the two frames before / after
+    the shard (slab s at ``s * fs_halo``), None where the shard touches the clip's end."""
+    rc = load().vface_temporal_gauss_halo(_p(src), ld_src, fs_src, _p(prev), _p(next_), ld_halo, fs_halo, _p(dst1), _p(dst2), ld_dst,
+                                          fs_dst, F, first, F_total, n, C_, dtype_code(src.dtype), _stream())
+    _check(rc, "vface_temporal_gauss_halo")
+
+
+def adain_rows_workspace_bytes(rows: int, C_: int) -> int:
+    return int(load().vface_adain_rows_workspace_bytes(rows, C_))
+
+
+def adain_rows(a, b, partial, ws, *, rows, C_, lda, ldb):
+    """Pass 1 of ``adain_fusion``: fused rows into ``ws`` (``adain_rows_workspace_bytes``), fp64 ``partial`` [rows][2]."""
+    assert partial.dtype == torch.float64 and partial.is_contiguous()
+    rc = load().vface_adain_rows(_p(a), lda, _p(b), ldb, rows, C_, _p(partial), _p(ws), ws.numel() * ws.element_size(),
+                                 dtype_code(a.dtype), _stream())
+    _check(rc, "vface_adain_rows")
+
+
+def adain_reduce_scale(partial, ws, dst, *, partial_rows, rows, C_, ldd):
+    """Pass 2: the global std over ``partial`` [partial_rows][2] (all ranks' rows, global order), then dst = fused / (std + 1e-5)."""
+    assert partial.dtype == torch.float64 and partial.is_contiguous()
+    rc = load().vface_adain_reduce_scale(_p(partial), partial_rows, C_, _p(ws), ws.numel() * ws.element_size(), _p(dst), ldd, rows,
+                                         dtype_code(dst.dtype), _stream())
+    _check(rc, "vface_adain_reduce_scale")
 
 
 def softmax_rows(scores: torch.Tensor, out: torch.Tensor, *, M: int, N: int, scale: float, ld_s: Optional[int] = None,

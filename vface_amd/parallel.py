@@ -1,13 +1,25 @@
 """Frame sharding of a clip across the GPUs of one node (one process per GPU, RCCL over xGMI).
 
 The hot path shards by frame: every rank runs the full 3-way batch for a contiguous range of frames.  FSAI and
-structure injection have no cross-frame dependency; flow-guided smoothing reads exactly one
-neighbour (F9): rank r needs rank r-1's LAST frame's fused q|k of chunk 1 at the level-0 hooked layers.  That is
-the only exchange step on the path, and the only collective this module issues: per hooked level-0 layer and
-DDIM step, a ``[n, 2d]`` 16-bit slab (5.2 MB at 512x512: 2.6 MB each of q and k) moves one hop down the chain -- point-to-point
-``isend/irecv`` (xGMI is point-to-point, so a one-hop shift costs one link transfer), or an all-gather of the
-slabs when ``mode="allgather"``.  The transfer is started right after chunk 1's fused projection and waited for
-just before the warp, so it overlaps chunk 2's projection (see ``UNetEngine._attn1_sharded``).
+structure injection have no cross-frame dependency.  Three hook modes read other frames, and each has its
+exchange step here, issued between the hooked ``attn1``'s projection and its edit:
+
+* ``flow_fix`` reads exactly one neighbour (F9): rank r needs rank r-1's LAST frame's fused q|k of chunk 1 at the level-0
+  hooked layers.  Per hooked level-0 layer and DDIM step, a ``[n, 2d]`` 16-bit slab (5.2 MB at 512x512: 2.6 MB each of q and
+  k) moves one hop down the chain -- point-to-point ``isend/irecv`` (xGMI is point-to-point, so a one-hop shift costs one link
+  transfer), or an all-gather of the slabs when ``mode="allgather"`` (``start_exchange``).  The transfer is started right after
+  chunk 1's fused projection and waited for just before the warp, so it overlaps chunk 2's projection
+  (see ``UNetEngine._attn1_sharded``).
+* ``temporal`` smooths chunk 0's q|k over +-2 frames: rank r needs the two frames before and the two after its range, in both
+  directions, at EVERY hooked layer (``start_temporal``): each rank sends its first two frames down and its last two up
+  (point-to-point), or -- with ``mode="allgather"``, or when a shard holds fewer than two frames, so that a needed frame may
+  live two ranks away -- all ranks all-gather their first two and last two frames and each picks the ones it needs.
+* ``adaIn`` divides by a std over ALL frames: every rank's fp64 row partials (sum, centred M2; ``vface_adain_rows``) are
+  all-gathered, padded to the largest shard, and laid out in global row order (``start_gather``) -- the exact array the
+  unsharded reduce reads.
+
+``finish_exchange`` completes any of the three (bounded: ``exchange_timeout_s``, ``ExchangeTimeout``).  Under gloo with device
+tensors every form runs through host staging (the rehearsal on a box without one GPU per rank).
 """
 from __future__ import annotations
 
@@ -102,15 +114,85 @@ class FrameShard:
         works = d.batch_isend_irecv(ops) if ops else []
         return ("p2p", works, halo)
 
+    # ---- the two-directional halo of fusion="temporal" (+-2 frames) and the row-partial gather of fusion="adaIn"
+    def temporal_form(self) -> str:
+        """``"p2p"`` where every shard holds at least two frames (a +-2 window then reaches the neighbouring ranks only), else
+        ``"allgather"``.  Decided from (mode, world, total) alone -- ``frame_range`` gives the last rank the fewest frames -- so
+        every rank of the clip makes the same choice."""
+        return "p2p" if self.mode == "p2p" and self.total // self.world >= 2 else "allgather"
+
+    def halo_frames(self):
+        """Global frames of the four slots ``start_temporal``'s result holds: first-2, first-1, last+1, last+2 (None: outside the clip)."""
+        last = self.first + self.count - 1
+        return [g if 0 <= g < self.total else None for g in (self.first - 2, self.first - 1, last + 1, last + 2)]
+
+    def _edge_slot(self, g: int):
+        """(rank, slot of its ``edges``) that carries global frame ``g`` -- one of the owner's first two or last two frames
+        whenever another rank's window reaches it."""
+        for q in range(self.world):
+            f, c = frame_range(q, self.world, self.total)
+            if f <= g < f + c:
+                j = g - f
+                return q, (j if j < 2 else 4 - (c - j))
+        raise IndexError(g)
+
+    def start_temporal(self, edges: torch.Tensor, recv: Optional[torch.Tensor] = None):
+        """Start the temporal halo exchange.  ``edges`` ``[4, ...]``: this shard's frames first, first+1, last-1, last (a
+        one-frame shard: its frame in slots 0 and 3).  ``finish_exchange`` then returns ``[4, ...]``: global frames first-2,
+        first-1, last+1, last+2 (``halo_frames``; a slot outside the clip is left unwritten).  ``recv``: a persistent buffer
+        shaped like ``edges`` to receive into where the form allows it (RCCL point-to-point)."""
+        if self.world == 1:
+            return None
+        d = self.dist
+        dev = edges.device if (edges.is_cuda and d.get_backend() == "gloo") else None      # host staging (see start_exchange)
+        src = edges.detach().to("cpu").contiguous() if dev is not None else edges.contiguous()
+        if self.temporal_form() == "p2p":
+            halo = recv if (recv is not None and dev is None) else torch.empty_like(src)
+            ops = []
+            if self.rank > 0:
+                ops += [d.P2POp(d.isend, src[0:2], self.rank - 1), d.P2POp(d.irecv, halo[0:2], self.rank - 1)]
+            if self.rank + 1 < self.world:
+                ops += [d.P2POp(d.isend, src[2:4], self.rank + 1), d.P2POp(d.irecv, halo[2:4], self.rank + 1)]
+            peers = " and ".join(f"rank {q}" for q in (self.rank - 1, self.rank + 1) if 0 <= q < self.world) + " (their edge frames)"
+            return ("temporal", d.batch_isend_irecv(ops), (halo, None, dev, peers))
+        bufs = torch.empty((self.world * 4,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+        work = d.all_gather_into_tensor(bufs, src, async_op=True)       # rank q's edge slots = rows [4q, 4q + 4)
+        return ("temporal", [work], (None, bufs, dev, f"all {self.world} ranks (all-gather of edge frames)"))
+
+    def start_gather(self, part: torch.Tensor, recv: Optional[torch.Tensor] = None):
+        """Start the gather of adaIn row partials: ``part`` ``[P, count * n, 2]`` fp64 (P arrays of this shard's rows).
+        ``finish_exchange`` returns ``[P, total * n, 2]``: every rank's rows in global row order.  Shards of unequal length are
+        padded to the longest for the all-gather.  (``recv`` is accepted for symmetry; the result is always assembled.)"""
+        if self.world == 1:
+            return None
+        d = self.dist
+        P, rows = int(part.shape[0]), int(part.shape[1])
+        n = rows // self.count
+        most = frame_range(0, self.world, self.total)[1] * n
+        dev = part.device if (part.is_cuda and d.get_backend() == "gloo") else None
+        src = part.detach().to("cpu") if dev is not None else part
+        if rows < most:
+            src = torch.cat([src, torch.zeros((P, most - rows) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)], 1)
+        src = src.contiguous()
+        bufs = torch.empty((self.world * P,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+        work = d.all_gather_into_tensor(bufs, src, async_op=True)       # rank q's arrays = rows [qP, (q + 1)P)
+        return ("gather", [work], (bufs.view((self.world, P) + tuple(src.shape[1:])), n, dev,
+                                   f"all {self.world} ranks (all-gather of adaIn row partials)"))
+
+    def gather_shape(self, part: torch.Tensor):
+        """Shape of what ``finish_exchange`` returns for ``start_gather(part)``."""
+        return (int(part.shape[0]), int(part.shape[1]) // self.count * self.total) + tuple(part.shape[2:])
+
     def _peers(self) -> str:
         peers = ([f"rank {self.rank - 1} (its last-frame slab)"] if self.rank > 0 else []) + \
                 ([f"rank {self.rank + 1} (to take ours)"] if self.rank + 1 < self.world else [])
         return " and ".join(peers) if self.mode != "allgather" else f"all {self.world} ranks (all-gather)"
 
-    def _wait(self, works) -> None:
+    def _wait(self, works, peers: Optional[str] = None) -> None:
         """Bounded wait on the works of one exchange.  gloo (and any backend whose ``wait`` blocks the host) takes the timeout
         directly; RCCL's ``wait`` only orders the stream, so the bound there is the process group's own timeout (watchdog),
-        unless ``VFACE_EXCHANGE_BLOCKING=1`` asks for host polling."""
+        unless ``VFACE_EXCHANGE_BLOCKING=1`` asks for host polling.  ``peers``: whom the exchange waits for, named in the
+        ``ExchangeTimeout`` message (default: the flow halo's peers)."""
         limit = exchange_timeout_s()
         backend = self.dist.get_backend() if hasattr(self.dist, "get_backend") else "gloo"
         poll = backend != "gloo" and os.environ.get("VFACE_EXCHANGE_BLOCKING") == "1"
@@ -133,15 +215,34 @@ class FrameShard:
             except (TimeoutError, RuntimeError) as e:
                 if isinstance(e, TimeoutError) or "time" in str(e).lower():
                     raise ExchangeTimeout(f"rank {self.rank} of {self.world}: the boundary exchange did not complete within "
-                                          f"{limit:g} s -- waited for {self._peers()}") from e
+                                          f"{limit:g} s -- waited for {peers or self._peers()}") from e
                 raise
 
     def finish_exchange(self, handle) -> Optional[torch.Tensor]:
         """Wait (bounded: ``exchange_timeout_s``) for the transfer; returns the previous rank's slab (None on rank 0 / single
-        rank).  Raises ``ExchangeTimeout`` naming the peer when it does not arrive."""
+        rank) -- or, for a ``start_temporal`` / ``start_gather`` handle, what those describe.  Raises ``ExchangeTimeout`` naming
+        the peer when it does not arrive."""
         if handle is None:
             return None
         kind, work, buf = handle
+        if kind == "temporal":
+            halo, bufs, dev, peers = buf
+            self._wait(work, peers)
+            if bufs is not None:
+                halo = torch.empty((4,) + tuple(bufs.shape[1:]), dtype=bufs.dtype, device=bufs.device)
+                for s, g in enumerate(self.halo_frames()):
+                    if g is not None:
+                        q, slot = self._edge_slot(g)
+                        halo[s].copy_(bufs[4 * q + slot])
+            return halo.to(dev) if dev is not None else halo
+        if kind == "gather":
+            bufs, n, dev, peers = buf
+            self._wait(work, peers)
+            out = torch.empty((bufs.shape[1], self.total * n) + tuple(bufs.shape[3:]), dtype=bufs.dtype, device=bufs.device)
+            for q in range(self.world):
+                f, c = frame_range(q, self.world, self.total)
+                out[:, f * n:(f + c) * n].copy_(bufs[q, :, :c * n])
+            return out.to(dev) if dev is not None else out
         if kind == "host":
             self._wait(work)
             halo, dev = buf
@@ -168,18 +269,28 @@ class FrameShard:
     def drain(self, pending, remaining) -> None:
         """Finish the paired exchanges of an aborted forward so that the neighbours' calls still match: ``pending`` = a handle
         that was started and not finished (or None), ``remaining`` = the slabs (tensors shaped like the tails the forward would
-        have sent; contents irrelevant) of the exchanges not yet started."""
+        have sent; contents irrelevant) of the exchanges not yet started -- a ``(kind, tensor)`` pair for a temporal halo or an
+        adaIn gather (kind ``"temporal"`` / ``"gather"``)."""
         if pending is not None:
             self.finish_exchange(pending)
         for tail in remaining:
-            self.finish_exchange(self.start_exchange(tail))
+            if isinstance(tail, tuple):
+                kind, t = tail
+                self.finish_exchange(getattr(self, "start_" + kind)(t))
+            else:
+                self.finish_exchange(self.start_exchange(tail))
 
     def slab_bytes_per_step(self, n: int, d: int, layers: int = 2, elem: int = 2) -> int:
         """Bytes this rank SENDS per DDIM step: one ``[n, 2d]`` slab per hooked level-0 layer (none from the last rank)."""
         return 0 if self.rank + 1 >= self.world else layers * n * 2 * d * elem
 
-    def install(self, engine, global_flow: torch.Tensor, device) -> None:
-        """Hook the exchange into a ``UNetEngine`` (used by flow_fix layers only)."""
+    def install(self, engine, global_flow: Optional[torch.Tensor] = None, device=None) -> None:
+        """Hook the exchange into a ``UNetEngine``: flow_fix layers use it with the clip's flow fields (``global_flow``
+        ``[total-1, 2, h, w]``), temporal / adaIn layers without any."""
+        if global_flow is None:
+            engine.halo_flow, engine.halo_hw = None, None
+            engine.halo_exchange = self if self.world > 1 else None
+            return
         hf = self.halo_flow(global_flow)
         engine.halo_flow = hf.to(device=device, dtype=torch.float32).contiguous() if hf is not None else None
         engine.halo_exchange = self if self.world > 1 else None
@@ -216,6 +327,14 @@ class LoopbackShard(FrameShard):
         if handle is None or self.rank == 0:
             return None
         return self.store[self.rank - 1][handle[1]]
+
+    def start_temporal(self, edges, recv=None):
+        raise NotImplementedError("a loop-back shard runs the ranks one after another: the temporal halo needs the NEXT rank's "
+                                  "frames too (run the shards as processes: FrameShard)")
+
+    def start_gather(self, part, recv=None):
+        raise NotImplementedError("a loop-back shard runs the ranks one after another: the adaIn gather needs every rank's rows "
+                                  "(run the shards as processes: FrameShard)")
 
     def agree(self, ok: bool, over_budget: bool = False):
         return bool(ok), bool(over_budget)      # one process: its own verdict is everybody's
