@@ -396,6 +396,24 @@ def test_split_plan_halves_frames_across_chunks_and_refuses_coupled_modes():
     assert eng._split_plan(24) is None
 
 
+def test_every_env_switch_of_the_engine_is_in_the_graph_key_or_exempt():
+    """A captured graph is replayed only for the launch sequence it holds: every ``self.NAME = ... os.environ.get("VFACE_...")`` of
+    the engine's two initialisers must be in ``_GRAPH_SWITCHES`` (the graph key is built from it) or in the list below, with a reason.
+    Purely mechanical: it catches the next switch that is added without a thought for a live engine's cached graphs."""
+    import inspect
+    from vface_amd.engine import UNetEngine
+    from vface_amd.replay import _StepReplay
+    # these choose WHETHER and HOW a forward is replayed (step_forward_nhwc, _step_forward_one, _capture); no forward reads them
+    exempt = {"use_graph": "replay or launch kernel by kernel", "graph_budget_bytes": "which graphs stay cached",
+              "split_streams": "one launch sequence or two halves, each with its own key", "split_selfcheck": "checks and times the halves"}
+    src = inspect.getsource(UNetEngine.__init__) + inspect.getsource(_StepReplay._init_replay)
+    names = re.findall(r"^\s*self\.(\w+)\s*=[^\n#]*os\.environ\.get\(\"VFACE_", src, flags=re.M)
+    assert len(names) == len(set(names)) >= 14, names
+    assert set(exempt) <= set(names) and not set(exempt) & set(_StepReplay._GRAPH_SWITCHES)
+    for name in names:
+        assert name in _StepReplay._GRAPH_SWITCHES or name in exempt, f"{name}: not in the graph key (_GRAPH_SWITCHES) and not exempt"
+
+
 def test_every_built_kernel_keeps_its_values_in_registers():
     """no instantiation that ships in libvface_hip.so carries scratch (a spilled kernel is a kernel whose schedule
     nobody chose) -- read from the code-object notes of csrc/build/*.o (tools/codeobj_audit.py; no GPU needed).  Round 5 still had

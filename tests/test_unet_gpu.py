@@ -648,6 +648,52 @@ def test_two_launch_streams_equal_one(small, fusion):
         sampler.make_schedule(50, ddim_eta=0.0, verbose=False)
 
 
+def test_second_split_kind_at_one_shape_is_checked_and_timed_too(small):
+    """The self-check and the both-ways timing of the two-launch-stream form fire on the second split step OF EACH KIND: an engine
+    that runs free halves (fft) and then coupled halves (flow_fix) at the same batch and resolution -- the shipped hook schedule
+    changes mode between the steps of one clip -- checks and times both.  (With one step counter per shape, the coupled kind's
+    second step was the shape's fifth: never checked, never timed.)"""
+    from vface_amd.ldm.models.diffusion.ddim_w_inv import HookPlan
+    ldm, sampler, sd = small
+    eng = ldm.unet.engine
+    F_, h, w = 6, 32, 32
+    d = lambda v: v.to(DEV)
+    x_T = d(synth.synth_normal("two.xT", (F_, 4, h, w)))
+    c, uc, tc = (d(synth.synth_normal(f"two.{k}", (F_, 1, 768))) for k in ("c", "uc", "tc"))
+    inp = d(synth.synth_normal("two.inpaint", (F_, 4, h, w)) * 0.18215)
+    mask = d(synth.synth_mask(F_, h, w))
+    inv = {int(s): d(synth.synth_normal(f"two.inv.{int(s)}", (F_, 4, h, w))) for s in oddim.ddim_timesteps(50)}
+    flow = [synth.synth_flow(F_ - 1, h, w)[i][None] for i in range(F_ - 1)]
+    old_gate = getattr(sampler, "flow_gate", None)
+    sampler.flow_gate = "flow_hw"        # (32 x 32 latents: the reference's 4096-token gate would never fire)
+    old = sampler.hook_plan, eng.use_graph, eng._graphs, eng.split_streams, sampler.drop_dead_branches
+    old_split = eng._split_state, set(eng._split_off), dict(eng.split_timing), dict(eng.split_checked), eng._split_verified
+    try:
+        eng.use_graph, eng._graphs, eng._split_state, eng.split_streams, sampler.drop_dead_branches = True, {}, {}, 2, False
+        eng._split_off.clear(); eng.split_timing.clear(); eng.split_checked.clear()
+        eng._split_verified = True       # (the overlap probe is not the subject: where the two streams share a hardware queue it
+        #                                   would put the engine on one sequence before the second kind runs)
+        for fusion, fl in (("fft", None), ("flow_fix", flow)):
+            sampler.hook_plan = HookPlan(fusion=fusion)
+            sampler.sample(S=50, batch_size=F_, shape=[4, h, w], conditioning=c, target_conditioning=tc, inverse_results_dir=inv,
+                           verbose=False, unconditional_guidance_scale=3.0, unconditional_conditioning=uc, eta=0.0, x_T=x_T, flow=fl,
+                           test_model_kwargs={"inpaint_image": inp, "inpaint_mask": mask}, max_steps=3)
+        assert not eng._graph_failed
+        print("split_checked", eng.split_checked, "split_timing", eng.split_timing)
+        assert eng.split_checked == {"free": True, "coupled": True}
+        for kind in ("free", "coupled"):
+            assert (kind, 3 * F_, h, w) in eng.split_timing, kind
+            t2, t1 = eng.split_timing[(kind, 3 * F_, h, w)]
+            assert t2 > 0 and t1 > 0, (kind, t2, t1)
+    finally:
+        sampler.hook_plan, eng.use_graph, eng._graphs, eng.split_streams, sampler.drop_dead_branches = old
+        eng._split_state, eng._split_verified = old_split[0], old_split[4]
+        for live, was in ((eng._split_off, old_split[1]), (eng.split_timing, old_split[2]), (eng.split_checked, old_split[3])):
+            live.clear(); live.update(was)
+        sampler.flow_gate = old_gate
+        sampler.make_schedule(50, ddim_eta=0.0, verbose=False)
+
+
 def test_config1_single_frame_256x256_twenty_steps_vs_oracle(small):
     """BASELINE configs[0] (the reference's own CPU-runnable case): ONE 256 x 256 frame (32 x 32 latent), the whole 20-step DDIM
     loop with the shipped hook schedule -- a clip of one frame has no flow field and no neighbour, every hook degenerates to
