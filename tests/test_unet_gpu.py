@@ -844,7 +844,7 @@ def test_drop_source_half_of_inversion_is_bit_identical(small):
 
 @pytest.mark.parametrize("mode", ["off", "in_replace", "in_fft", "in_flow_fix", "in_fft_vfixed"])
 def test_decomposed_attn1_equals_one_call_form_bit_for_bit(small, mode):
-    """bench.py's instrumented pass issues the launches of ``vface_attn1_forward`` call by call (UNetEngine._attn1_decomposed)
+    """bench.py's instrumented pass issues the launches of ``vface_attn1_forward`` call by call (UNetEngine._attn1_qkv_att + _attn1_out)
     to time the projections and the attention kernel separately: same kernels, same parameters, same order -> same bits."""
     ldm, sampler, _ = small
     F_, h, w = 2, 32, 32

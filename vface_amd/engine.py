@@ -183,6 +183,21 @@ def sample_map(kind: str, B: int, c: int) -> torch.Tensor:
     raise ValueError(kind)
 
 
+def fold_qk(kind: str, param: float, wq: torch.Tensor, wk: torch.Tensor) -> torch.Tensor:
+    """The folded ``[2d, 2d]`` q|k weight of a linear hook fusion (``plan_fusion``'s ``wlin``: FSAI or mix), fp32 on the CPU."""
+    wq, wk = wq.detach().float().cpu(), wk.detach().float().cpu()
+    return packing.fold_fsai(wq, wk, param) if kind == "fsai" else packing.fold_mix(wq, wk, param)
+
+
+def qkv_attention(qkv: torch.Tensor, att: torch.Tensor, *, B: int, n: int, d: int, heads: int, **maps):
+    """Self-attention over a ``[rows, 3d]`` q|k|v buffer of n-token samples into ``att`` ``[rows, d]``, as ``vface_attn1_forward``
+    (capi.cpp) sets it up; ``maps``: ``hip.attention``'s sample maps / value sets."""
+    dh = d // heads
+    hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=B, heads=heads, n=n, nk=n, dh=dh, ldq=3 * d, ldk=3 * d, ldv=3 * d,
+                  bsq=n * 3 * d, bsk=n * 3 * d, bsv=n * 3 * d, ldo=d, bso=n * d,
+                  scale=float(np.float32(1.0) / np.sqrt(np.float32(dh))), **maps)   # fp32 arithmetic, as capi.cpp computes it
+
+
 def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, rowbias=None, residual=None,
                  residual32=None, out32=None, chunks: int = 3, edit: Optional[Callable] = None):
     """Hooked attn1 for fusion modes that edit q,k with their own kernels ("temporal", "adaIn"; pnp_utils.py:145-160):
@@ -208,8 +223,7 @@ def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, 
     else:
         raise ValueError(mode)
     att = torch.empty(B * n, d, dtype=dt, device=dev)
-    hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=B, heads=heads, n=n, nk=n, dh=d // heads, ldq=3 * d, ldk=3 * d,
-                  ldv=3 * d, bsq=n * 3 * d, bsk=n * 3 * d, bsv=n * 3 * d, ldo=d, bso=n * d, scale=(d // heads) ** -0.5)
+    qkv_attention(qkv, att, B=B, n=n, d=d, heads=heads)
     o = out if out is not None else out32
     hip.gemm(att, wo, out, M=B * n, N=o.shape[1], K=d, lda=d, ldc=out.stride(0) if out is not None else 0, bias=bo,
              rowbias=rowbias, rows_per_sample=n, residual=residual, ldr=residual.stride(0) if residual is not None else 0,
@@ -249,14 +263,11 @@ def attn_module_forward(mod, x: torch.Tensor, context: Optional[torch.Tensor], c
         if pl["wlin"]:
             key = (pl["wlin"][0], round(float(pl["wlin"][1]), 9))
             if key not in pk["wlin"]:
-                wq, wk = mod.to_q.weight.detach().float().cpu(), mod.to_k.weight.detach().float().cpu()
-                w = packing.fold_fsai(wq, wk, key[1]) if key[0] == "fsai" else packing.fold_mix(wq, wk, key[1])
-                pk["wlin"][key] = w.to(device=dev, dtype=dt).contiguous()
+                pk["wlin"][key] = fold_qk(*key, mod.to_q.weight, mod.to_k.weight).to(device=dev, dtype=dt).contiguous()
             wlin = pk["wlin"][key]
-        idx = torch.arange(B, dtype=torch.int32)
         c = B // chunks
-        qk_map = (idx % c).to(dev) if pl["fusion"] == hip.FUSION_REPLACE else None
-        v_map = torch.where(idx < c, idx, (idx // c) * c).to(dev) if pl["v_fixed"] else None
+        qk_map = sample_map("qk_replace", B, c).to(dev) if pl["fusion"] == hip.FUSION_REPLACE else None
+        v_map = sample_map("v_fixed", B, c).to(dev) if pl["v_fixed"] else None
         ws = torch.empty(hip.attn1_workspace_bytes(B, n, d, chunks), dtype=torch.uint8, device=dev)
         flow = pl["flow"]
         hw = pl["warp_hw"] or (0, 0)
@@ -330,8 +341,7 @@ class UNetEngine(_StepReplay):
         # carrier covers the skip columns only and the concat GroupNorm reads the 16-bit copy (forward_nhwc).  VFACE_CONCAT32=1: A/B
         self.concat32 = os.environ.get("VFACE_CONCAT32", "0") == "1"
         self.interior16 = os.environ.get("VFACE_INTERIOR16", "1") != "0"      # (see _st; VFACE_INTERIOR16=0: fp32 interior sums, A/B)
-        self._front_supported: Dict[tuple, bool] = {}
-        self._ffn_supported: Dict[tuple, bool] = {}
+        self._shape_ok: Dict[tuple, bool] = {}         # (_supported)
         self.decompose_attn1 = False                   # bench.py's instrumented pass: vface_attn1_forward's launches call by call
         # the batch holds only the first `live_chunks` chunks of the hooks' three (the sampler's dead-branch elimination leaves
         # the recon third out: DDIMSampler.drop_dead_branches); None = every chunk is there
@@ -495,9 +505,7 @@ class UNetEngine(_StepReplay):
     def _wlin(self, st: dict, kind: str, param: float) -> torch.Tensor:
         key = (kind, round(float(param), 9))
         if key not in st["wlin"]:
-            wq, wk = (t.detach().float().cpu() for t in st["qk_src"])
-            w = packing.fold_fsai(wq, wk, param) if kind == "fsai" else packing.fold_mix(wq, wk, param)
-            st["wlin"][key] = self._w16(w)
+            st["wlin"][key] = self._w16(fold_qk(kind, param, *st["qk_src"]))
         return st["wlin"][key]
 
     def _map(self, kind: str, B: int, c: int) -> torch.Tensor:
@@ -628,15 +636,23 @@ class UNetEngine(_StepReplay):
             skip = x
         return self._conv(h, p["conv2"], out, residual=skip, gn_ab=gn2)
 
-    def _attn1(self, xln: torch.Tensor, resid: torch.Tensor, p: dict, cfg: Optional[HookCfg], a2vec: torch.Tensor,
-               N: int, n: int, heads: int, hw) -> torch.Tensor:
-        """``resid`` 16-bit -> 16-bit result; ``resid`` fp32 (the residual stream) -> fp32 result, no 16-bit copy."""
+    def _hook_plan(self, attn1, N: int, n: int) -> dict:
+        """``plan_fusion`` of the hook registered on ``attn1`` for N samples of n tokens on this engine (its frame shard, its live chunks)."""
+        fw = attn1.__dict__.get("forward")
+        if fw is not None and not getattr(fw, "_vface", False):
+            raise hip.VFaceHipError("attn1.forward was replaced by a closure this engine does not know; use "
+                                    "vface_amd.ldm.models.pnp_utils.register_spa_attn_injection")
+        return plan_fusion(getattr(attn1, "_vface_cfg", None), N, n, self.halo_hw if self.halo_exchange is not None else None,
+                           self.live_chunks)
+
+    def _attn1(self, xln: torch.Tensor, resid: torch.Tensor, p: dict, pl: dict, a2vec: torch.Tensor, N: int, n: int,
+               heads: int) -> torch.Tensor:
+        """``resid`` 16-bit -> 16-bit result; ``resid`` fp32 (the residual stream) -> fp32 result, no 16-bit copy.  ``pl``: ``_hook_plan``."""
         d = p["c"]
         s32 = resid.dtype == torch.float32
         out = None if s32 else self._new(N * n, d)
         out32 = self._new(N * n, d, torch.float32) if s32 else None
         res_kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid, "ldr": resid.stride(0)}
-        pl = plan_fusion(cfg, N, n, self.halo_hw if self.halo_exchange is not None else None, self.live_chunks)
         if pl["staged"]:
             # frames sharded across ranks: the edit exchanges what it needs from the other ranks (temporal: +-2 frames; adaIn:
             # the row partials of the global std) between the projection and the attention
@@ -644,101 +660,100 @@ class UNetEngine(_StepReplay):
             kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid}
             return staged_attn1(xln, p["wqkv"], p["wo"]["w"], p["wo"]["b"], out, B=N, n=n, d=d, heads=heads,
                                 mode=pl["staged"], rowbias=a2vec, chunks=pl["chunks"], edit=edit, **kw)
-        fusion, chunks, flow, alpha, v_fixed = pl["fusion"], pl["chunks"], pl["flow"], pl["alpha"], pl["v_fixed"]
-        wlin = self._wlin(p, *pl["wlin"]) if pl["wlin"] else None
-        qk_map = self._map("qk_replace", N, N // chunks) if fusion == hip.FUSION_REPLACE else None
-        v_map = self._map("v_fixed", N, N // chunks) if v_fixed else None
-        ws = torch.empty(hip.attn1_workspace_bytes(N, n, d, chunks), dtype=torch.uint8, device=self.device)
-        hw = pl["warp_hw"]
-        if hw is not None and self.halo_exchange is not None:
-            # every rank of a sharded clip takes part in the boundary exchange, a one-frame shard (no local field) too
-            return self._attn1_sharded(xln, res_kw, p, wlin, a2vec, N, n, heads, flow, hw, alpha, out, chunks)
-        if self.decompose_attn1 or pl["hook_chunks"] != chunks:
-            # (a batch without its last chunk: the shared-score attention must run the FULL hook's instantiation with fewer live
-            # sets to keep the bits of the full batch -- vface_attn1_forward only knows the chunks it is handed)
-            self._attn1_decomposed(xln, p, wlin, a2vec, N, n, heads, chunks, fusion, v_fixed, flow if hw is not None else None,
-                                   hw, alpha, qk_map, v_map, out, res_kw, pl["hook_chunks"])
+        fusion, chunks, hw = pl["fusion"], pl["chunks"], pl["warp_hw"]
+        if (hw is not None and self.halo_exchange is not None) or self.decompose_attn1 or pl["hook_chunks"] != chunks:
+            # the launches of the one call below, issued from here: a sharded clip (the boundary exchange sits between them); bench.py's
+            # instrumented pass (HIP events around the projections and the attention kernel separately); a batch without its last
+            # chunk (the shared-score attention must run the FULL hook's instantiation with fewer live sets to keep the bits of the
+            # full batch -- vface_attn1_forward only knows the chunks it is handed)
+            att = self._attn1_qkv_att(xln, self._new(N * n, 3 * d), p, pl, N, n, heads, projected=False)
+            self._attn1_out(att, p, a2vec, n, out, **res_kw)
             return out32 if s32 else out
-        hip.attn1_forward(xln, p["wqkv"], wlin, p["wo"]["w"], p["wo"]["b"], out, B=N, n=n, d=d, heads=heads,
-                          chunks=chunks, fusion=fusion, ldx=xln.stride(0), ldo=d, workspace=ws,
-                          rowbias=a2vec, v_fixed=v_fixed, flow=flow if hw is not None else None,
-                          h=hw[0] if hw else 0, w=hw[1] if hw else 0,
-                          alpha=alpha, qk_map=qk_map, v_map=v_map, **res_kw)
+        ws = torch.empty(hip.attn1_workspace_bytes(N, n, d, chunks), dtype=torch.uint8, device=self.device)
+        hip.attn1_forward(xln, p["wqkv"], self._wlin(p, *pl["wlin"]) if pl["wlin"] else None, p["wo"]["w"], p["wo"]["b"], out,
+                          B=N, n=n, d=d, heads=heads, chunks=chunks, fusion=fusion, ldx=xln.stride(0), ldo=d, workspace=ws,
+                          rowbias=a2vec, v_fixed=pl["v_fixed"], flow=pl["flow"], h=hw[0] if hw else 0, w=hw[1] if hw else 0,
+                          alpha=pl["alpha"], qk_map=self._map("qk_replace", N, N // chunks) if fusion == hip.FUSION_REPLACE else None,
+                          v_map=self._map("v_fixed", N, N // chunks) if pl["v_fixed"] else None, **res_kw)
         return out32 if s32 else out
 
-    def _attn1_decomposed(self, xln, p, wlin, a2vec, N, n, heads, chunks, fusion, v_fixed, flow, hw, alpha, qk_map, v_map,
-                          out, res_kw, hook_chunks=None):
-        """The launch sequence of ``vface_attn1_forward`` (capi.cpp) issued call by call from here -- the same kernels with the
-        same parameters in the same order, hence the same bits (tests/test_kernels_gpu.py) -- so that ``bench.py``'s
-        instrumented pass can put HIP events around the projections and the attention kernel separately."""
+    def _attn1_out(self, att: torch.Tensor, p: dict, a2vec: torch.Tensor, n: int, out: Optional[torch.Tensor], **res_kw):
+        """attn1's out-projection + bias + attn2's row bias + residual, as ``vface_attn1_forward`` ends (no split-K workspace)."""
         d = p["c"]
-        F_ = N // chunks
-        Fn = F_ * n
-        ldx = xln.stride(0)
-        qkv = self._new(N * n, 3 * d)
-        g = lambda a, w, o, M, Nn, K, **kw: hip.gemm(a, w, o, M=M, N=Nn, K=K, lda=ldx, ldc=o.stride(0), ldw=w.stride(0),
-                                                      split_k=False, **kw)
-        if fusion == hip.FUSION_NONE:
-            g(xln, p["wqkv"], qkv, N * n, 3 * d, d)
-        else:
-            g(xln, p["wqkv"], qkv, Fn, 3 * d, d)
-            g(xln[Fn:], p["wqkv"][2 * d:], qkv[Fn:, 2 * d:], N * n - Fn, d, d)
-            if fusion == hip.FUSION_LINEAR:
-                T = self._new(Fn, 2 * d) if flow is not None else None
-                for c in range(1, chunks):
-                    dst = T if (flow is not None and c == 1) else qkv[c * Fn:(c + 1) * Fn, :2 * d]
-                    g(xln[c * Fn:], wlin, dst, Fn, 2 * d, 2 * d, a2=xln, lda2=ldx, k1=d)
-                if flow is not None:
-                    hip.flow_warp(T, qkv[Fn:2 * Fn, :2 * d], flow, F=F_, h=hw[0], w=hw[1], C_=2 * d, ld_src=2 * d,
-                                  fs_src=n * 2 * d, ld_dst=3 * d, fs_dst=n * 3 * d, alpha=alpha)
-        att = self._new(N * n, d)
-        kw = dict(heads=heads, n=n, nk=n, dh=d // heads, ldq=3 * d, ldk=3 * d, ldv=3 * d, bsq=n * 3 * d, bsk=n * 3 * d,
-                  bsv=n * 3 * d, ldo=d, bso=n * d,
-                  scale=float(np.float32(1.0) / np.sqrt(np.float32(d // heads))))   # fp32 arithmetic, as capi.cpp computes it
-        hc = hook_chunks or chunks
-        if fusion == hip.FUSION_REPLACE and chunks > 1 and hip.load().vface_attention_shared_scores_supported(d // heads, hc):
-            hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=F_, v_map=v_map if v_fixed else None, v_sets=hc,
-                          v_sets_live=chunks, set_stride=F_, **kw)
-        else:
-            hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=N, qk_map=qk_map if fusion == hip.FUSION_REPLACE else None,
-                          v_map=v_map if v_fixed else None, **kw)
-        o = out if out is not None else res_kw["out32"]
-        hip.gemm(att, p["wo"]["w"], out, M=N * n, N=d, K=d, lda=d, ldc=out.stride(0) if out is not None else 0,
+        hip.gemm(att, p["wo"]["w"], out, M=att.shape[0], N=d, K=d, lda=d, ldc=out.stride(0) if out is not None else 0, ldw=d,
                  bias=p["wo"]["b"], rowbias=a2vec, rows_per_sample=n, split_k=False, **res_kw)
-        return o
 
-    def _attn1_sharded(self, xln, res_kw, p, wlin, a2vec, N, n, heads, flow, hw, alpha, out, chunks=3):
-        """flow_fix with frames sharded across ranks: the same kernels as vface_attn1_forward, sequenced here
-        so the one-neighbour boundary exchange sits between the fused projection and the warp."""
+    def _fused_qk(self, own: torch.Tensor, first: torch.Tensor, wlin: torch.Tensor, dst: torch.Tensor, rows: int, d: int):
+        """The dual-source q|k projection of a linear hook fusion: ``[own | first]`` (K = 2d; ``first``: chunk 0's rows
+        of the same LayerNorm output) times the folded weight ``_wlin``."""
+        hip.gemm(own, wlin, dst, M=rows, N=2 * d, K=2 * d, lda=own.stride(0), ldc=dst.stride(0), ldw=2 * d, a2=first,
+                 lda2=first.stride(0), k1=d, split_k=False)
+
+    def _warp(self, T: torch.Tensor, dst: torch.Tensor, pl: dict, F_: int, n: int, d: int, halo: Optional[torch.Tensor]):
+        """The flow warp of chunk 1's fused q|k ``T`` ``[F n, 2d]`` into its rows of a qkv buffer; ``halo``: the previous rank's last
+        frame of ``T`` when frames are sharded (None on the first rank and on an unsharded clip)."""
+        h, w = pl["warp_hw"]
+        hip.flow_warp(T, dst, pl["flow"], F=F_, h=h, w=w, C_=2 * d, ld_src=2 * d, fs_src=n * 2 * d, ld_dst=3 * d,
+                      fs_dst=n * 3 * d, alpha=pl["alpha"], prev=halo, ld_prev=2 * d,
+                      flow_prev=self.halo_flow if halo is not None else None)
+
+    def _attn1_qkv_att(self, ln: Optional[torch.Tensor], qkv: torch.Tensor, p: dict, pl: dict, N: int, n: int, heads: int, *,
+                       projected: bool) -> torch.Tensor:
+        """The middle of a hooked attn1, from the LayerNorm output ``ln`` to the attention output ``[N n, d]``: the launch sequence
+        of ``vface_attn1_forward`` (capi.cpp) without its out-projection -- the same kernels with the same parameters in the same
+        order, hence the same bits (tests/test_kernels_gpu.py).  ``projected``: the fused front already wrote chunk 0's q|k|v and
+        the other chunks' v into ``qkv`` (``_st_front``; ``ln`` is then only needed by the linear fusions); otherwise those two GEMMs
+        (one over the whole batch when no hook edits it) are issued here.
+        Frames sharded across ranks and a flow warp: the one-neighbour boundary exchange sits between chunk 1's
+        fused projection and the warp, and the launches that do not depend on it are issued behind its start."""
         d = p["c"]
+        fusion, chunks = pl["fusion"], pl["chunks"]
         F_ = N // chunks
         Fn = F_ * n
-        qkv = self._new(N * n, 3 * d)
-        T = self._new(Fn, 2 * d)
-        def fused(c, dst):
-            hip.gemm(xln[c * Fn:], wlin, dst, M=Fn, N=2 * d, K=2 * d, lda=xln.stride(0), ldc=dst.stride(0), ldw=2 * d,
-                     a2=xln, lda2=xln.stride(0), k1=d)
 
-        fused(1, T)
-        # my last frame's fused q|k goes to the next rank; the previous rank's arrives while chunk 0 / chunk 2 /
-        # the v projections below are computed
-        handle = self._halo_start(T[(F_ - 1) * n:])
-        hip.gemm(xln, p["wqkv"], qkv, M=Fn, N=3 * d, K=d, lda=xln.stride(0), ldc=3 * d)
-        hip.gemm(xln[Fn:], p["wqkv"][2 * d:], qkv[Fn:, 2 * d:], M=N * n - Fn, N=d, K=d, lda=xln.stride(0), ldc=3 * d)
-        for ch in range(2, chunks):
-            fused(ch, qkv[ch * Fn:(ch + 1) * Fn, :2 * d])
-        halo = self._halo_finish(handle)
-        dst = qkv[Fn:2 * Fn, :2 * d]
-        hip.flow_warp(T, dst, flow, F=F_, h=hw[0], w=hw[1], C_=2 * d, ld_src=2 * d, fs_src=n * 2 * d,
-                      ld_dst=3 * d, fs_dst=n * 3 * d, alpha=alpha, prev=halo, ld_prev=2 * d,
-                      flow_prev=self.halo_flow if halo is not None else None)
+        def project():
+            if projected:
+                return
+            g = lambda a, w, o, M, Nn: hip.gemm(a, w, o, M=M, N=Nn, K=d, lda=ln.stride(0), ldc=3 * d, ldw=d, split_k=False)
+            if fusion == hip.FUSION_NONE:
+                g(ln, p["wqkv"], qkv, N * n, 3 * d)
+            else:
+                g(ln, p["wqkv"], qkv, Fn, 3 * d)                                         # chunk 0: q, k, v as projected
+                g(ln[Fn:], p["wqkv"][2 * d:], qkv[Fn:, 2 * d:], N * n - Fn, d)          # other chunks: v only, the fusion writes their q, k
+
+        if fusion != hip.FUSION_LINEAR:
+            project()
+        else:
+            wlin = self._wlin(p, *pl["wlin"])
+            warp = pl["warp_hw"] is not None
+            # every rank of a sharded clip takes part in the boundary exchange, a one-frame shard (no local field) too
+            sharded = warp and self.halo_exchange is not None
+            T = self._new(Fn, 2 * d) if warp else None
+            fused = lambda ch: self._fused_qk(ln[ch * Fn:], ln, wlin, T if (warp and ch == 1) else qkv[ch * Fn:(ch + 1) * Fn, :2 * d],
+                                              Fn, d)
+            halo = None
+            if sharded:
+                fused(1)
+                # my last frame's fused q|k goes to the next rank; the previous rank's arrives while chunk 0 / chunk 2 /
+                # the v projections below are computed
+                handle = self._halo_start(T[(F_ - 1) * n:])
+            project()
+            for ch in range(2 if sharded else 1, chunks):
+                fused(ch)
+            if sharded:
+                halo = self._halo_finish(handle)
+            if warp:
+                self._warp(T, qkv[Fn:2 * Fn, :2 * d], pl, F_, n, d, halo)
         att = self._new(N * n, d)
-        hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=N, heads=heads, n=n, nk=n, dh=d // heads, ldq=3 * d,
-                      ldk=3 * d, ldv=3 * d, bsq=n * 3 * d, bsk=n * 3 * d, bsv=n * 3 * d, ldo=d, bso=n * d,
-                      scale=(d // heads) ** -0.5)
-        hip.gemm(att, p["wo"]["w"], out, M=N * n, N=d, K=d, lda=d, ldc=d, bias=p["wo"]["b"], rowbias=a2vec,
-                 rows_per_sample=n, **res_kw)
-        return res_kw.get("out32") if out is None else out
+        v_map = self._map("v_fixed", N, F_) if pl["v_fixed"] else None
+        hc = pl["hook_chunks"]
+        if fusion == hip.FUSION_REPLACE and chunks > 1 and hip.load().vface_attention_shared_scores_supported(d // heads, hc):
+            # every chunk attends with q,k of chunk 0 (pnp_utils.py:136-142): softmax once per frame, one value set per chunk
+            qkv_attention(qkv, att, B=F_, n=n, d=d, heads=heads, v_map=v_map, v_sets=hc, v_sets_live=chunks, set_stride=F_)
+        else:
+            qkv_attention(qkv, att, B=N, n=n, d=d, heads=heads,
+                          qk_map=self._map("qk_replace", N, F_) if fusion == hip.FUSION_REPLACE else None, v_map=v_map)
+        return att
 
     def _block(self, t0: torch.Tensor, p: dict, attn1, a2vec: torch.Tensor, N: int, n: int, hw, want32: bool = False):
         """BasicTransformerBlock._forward (attention.py:239-243) on the block's running sum ``t0`` ``[N*n, c]`` (fp32 when the
@@ -747,12 +762,7 @@ class UNetEngine(_StepReplay):
         c, M = p["c"], t0.shape[0]
         ln = self._new(M, c)
         hip.layernorm(t0, p["ln1"][0], p["ln1"][1], ln, M=M, C_=c, ldx=c, ldy=c)
-        cfg = getattr(attn1, "_vface_cfg", None)
-        fw = attn1.__dict__.get("forward")
-        if fw is not None and not getattr(fw, "_vface", False):
-            raise hip.VFaceHipError("attn1.forward was replaced by a closure this engine does not know; use "
-                                    "vface_amd.ldm.models.pnp_utils.register_spa_attn_injection")
-        t1 = self._attn1(ln, t0, p, cfg, a2vec, N, n, attn1.heads, hw)
+        t1 = self._attn1(ln, t0, p, self._hook_plan(attn1, N, n), a2vec, N, n, attn1.heads)
         return self._ffn(t1, p, n, want32)
 
     def _ffn(self, t1: torch.Tensor, p: dict, n: int, want32: bool = False):
@@ -778,75 +788,24 @@ class UNetEngine(_StepReplay):
         and the producer's column statistics of ``x`` and a width the kernel takes.  Returns the block's last running sum
         (16-bit, proj_out's operand), or None when this layer does not qualify (the caller then runs the separate launches), or
         True when ``post = (out16 | None, colstats | None, out32)`` was given and the tail launch also ran proj_out + ``x`` into it.
-        What follows the front is the launch sequence of ``vface_attn1_forward`` (capi.cpp) minus its first two GEMMs: the
-        dual-source projections of the hook's linear fusions (they read the LayerNorm output the front also writes then), the flow
-        warp -- with the boundary exchange between chunk 1's fused projection and the warp when frames are sharded --, the
-        attention kernel, the out-projection into the fp32 stream, then norm3 + FeedForward."""
+        What follows the front is the launch sequence of ``vface_attn1_forward`` (capi.cpp) minus its first two GEMMs
+        (``_attn1_qkv_att``: the dual-source projections of the hook's linear fusions read the LayerNorm output the front also
+        writes then), the out-projection into the fp32 stream, then norm3 + FeedForward."""
         c, N, n, M = p["c"], x.N, x.hw, x.M
-        if not self.fuse_front or p.get("front_w") is None or x.t32 is None or x.cs is None:
+        if not self.fuse_front or p.get("front_w") is None or x.t32 is None or x.cs is None or not self._front_ok(M, c, n):
             return None
-        key = (M, c, n)
-        ok = self._front_supported.get(key)
-        if ok is None:
-            ok = self._front_supported[key] = bool(hip.st_front_supported(M, c, n))
-        if not ok:
-            return None
-        cfg = getattr(attn1, "_vface_cfg", None)
-        fw = attn1.__dict__.get("forward")
-        if fw is not None and not getattr(fw, "_vface", False):
-            raise hip.VFaceHipError("attn1.forward was replaced by a closure this engine does not know; use "
-                                    "vface_amd.ldm.models.pnp_utils.register_spa_attn_injection")
-        pl = plan_fusion(cfg, N, n, self.halo_hw if self.halo_exchange is not None else None, self.live_chunks)
+        pl = self._hook_plan(attn1, N, n)
         if pl["staged"]:
             return None      # "temporal" / "adaIn" edit a full q,k,v buffer with their own kernels
-        d, heads = c, attn1.heads
-        fusion, chunks, flow, alpha, v_fixed = pl["fusion"], pl["chunks"], pl["flow"], pl["alpha"], pl["v_fixed"]
-        F_ = N // chunks
-        Fn = F_ * n
-        hw = pl["warp_hw"]
-        sharded = hw is not None and self.halo_exchange is not None
-        if hw is None:
-            flow = None
+        d, fusion = c, pl["fusion"]
+        Fn = N // pl["chunks"] * n
         ab = hip.groupnorm_coeffs_from_cols(x.cs, p["gn"][0], p["gn"][1], nimg=N, hw=n, C_=c, eps=1e-6)
         t0 = self._new(M, c, torch.float32)
         qkv = self._new(M, 3 * d)
         ln = self._new(M, c) if fusion == hip.FUSION_LINEAR else None
         hip.st_front(x.t32, ab, p["front_w"], p["proj_in"]["b"], p["ln1"][0], p["ln1"][1], t0, qkv, M=M, C_=c, hw=n, NQ=3 * d,
                      rows_full=M if fusion == hip.FUSION_NONE else Fn, nq_lo=0 if fusion == hip.FUSION_NONE else 2 * d, ln=ln)
-        if fusion == hip.FUSION_LINEAR:
-            wlin = self._wlin(p, *pl["wlin"])
-            ldl = ln.stride(0)
-
-            def fused(ch, dst):
-                hip.gemm(ln[ch * Fn:], wlin, dst, M=Fn, N=2 * d, K=2 * d, lda=ldl, ldc=dst.stride(0), ldw=2 * d, a2=ln, lda2=ldl, k1=d,
-                         split_k=False)
-            T = self._new(Fn, 2 * d) if (flow is not None or sharded) else None
-            halo = None
-            if sharded:
-                fused(1, T)
-                handle = self._halo_start(T[(F_ - 1) * n:])
-                for ch in range(2, chunks):
-                    fused(ch, qkv[ch * Fn:(ch + 1) * Fn, :2 * d])
-                halo = self._halo_finish(handle)
-            else:
-                for ch in range(1, chunks):
-                    fused(ch, T if (T is not None and ch == 1) else qkv[ch * Fn:(ch + 1) * Fn, :2 * d])
-            if T is not None:
-                hip.flow_warp(T, qkv[Fn:2 * Fn, :2 * d], flow, F=F_, h=hw[0], w=hw[1], C_=2 * d, ld_src=2 * d, fs_src=n * 2 * d,
-                              ld_dst=3 * d, fs_dst=n * 3 * d, alpha=alpha, prev=halo, ld_prev=2 * d,
-                              flow_prev=self.halo_flow if halo is not None else None)
-        att = self._new(M, d)
-        kw = dict(heads=heads, n=n, nk=n, dh=d // heads, ldq=3 * d, ldk=3 * d, ldv=3 * d, bsq=n * 3 * d, bsk=n * 3 * d,
-                  bsv=n * 3 * d, ldo=d, bso=n * d,
-                  scale=float(np.float32(1.0) / np.sqrt(np.float32(d // heads))))   # fp32 arithmetic, as capi.cpp computes it
-        v_map = self._map("v_fixed", N, F_) if v_fixed else None
-        if fusion == hip.FUSION_REPLACE and chunks > 1 and \
-                hip.load().vface_attention_shared_scores_supported(d // heads, pl["hook_chunks"]):
-            hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=F_, v_map=v_map, v_sets=pl["hook_chunks"], v_sets_live=chunks,
-                          set_stride=F_, **kw)
-        else:
-            hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=N,
-                          qk_map=self._map("qk_replace", N, F_) if fusion == hip.FUSION_REPLACE else None, v_map=v_map, **kw)
+        att = self._attn1_qkv_att(ln, qkv, p, pl, N, n, attn1.heads, projected=True)
         if self.fuse_tail and p.get("tail_w") is not None and n % 128 == 0 and self._ffn_ok(M, c):
             # to_out + bias + attn2's row bias + residual -> norm3 -> FeedForward -> + x in ONE launch: t1 never exists in HBM
             if self.fuse_post and p.get("tail_post") and post is not None and (post[0] is not None or post[2] is not None):
@@ -859,8 +818,7 @@ class UNetEngine(_StepReplay):
                                    p["ff2"]["b"], t2, M=M, C_=c, rows_per_sample=n)
             return t2
         t1 = self._new(M, c, torch.float32)
-        hip.gemm(att, p["wo"]["w"], None, M=M, N=d, K=d, lda=d, ldc=0, bias=p["wo"]["b"], rowbias=a2vec, rows_per_sample=n,
-                 split_k=False, residual32=t0, out32=t1)
+        self._attn1_out(att, p, a2vec, n, None, residual32=t0, out32=t1)
         return self._ffn(t1, p, n)
 
     # ------------------------------------------------------------------ chunks 0 and 1 of the sampler's batch share their prefix
@@ -882,18 +840,14 @@ class UNetEngine(_StepReplay):
         if not (self.fuse_front and self.fuse_ffn and self.fuse_tail and self.fuse_post) or p.get("front_w") is None or \
                 p.get("tail_w") is None or not p.get("tail_post"):
             return False
-        key = ((L - 1) * F_ * n, c, n)
-        ok = self._front_supported.get(key)
-        if ok is None:
-            ok = self._front_supported[key] = bool(hip.st_front_supported(key[0], c, n))
-        if not ok or not self._ffn_ok(F_ * n, c) or not self._ffn_ok((L - 1) * F_ * n, c):
+        if not self._front_ok((L - 1) * F_ * n, c, n) or not self._ffn_ok(F_ * n, c) or not self._ffn_ok((L - 1) * F_ * n, c):
             return False
         attn1 = block[1][2].transformer_blocks[0].attn1
         cfg = getattr(attn1, "_vface_cfg", None)
         if cfg is not None and cfg.switch_on and cfg.chunks != 3:
             return False
         try:
-            pl = plan_fusion(cfg, h.N, n, self.halo_hw if self.halo_exchange is not None else None, self.live_chunks)
+            pl = self._hook_plan(attn1, h.N, n)
         except Exception:
             return False          # (the whole-batch path raises it where the caller expects it)
         if pl["staged"] or pl["v_fixed"]:
@@ -937,14 +891,9 @@ class UNetEngine(_StepReplay):
         d, heads = c, attn1.heads
         Fn = F_ * n
         M2, M3 = (L - 1) * Fn, 3 * Fn
-        cfg = getattr(attn1, "_vface_cfg", None)
-        fw = attn1.__dict__.get("forward")
-        if fw is not None and not getattr(fw, "_vface", False):
-            raise hip.VFaceHipError("attn1.forward was replaced by a closure this engine does not know; use "
-                                    "vface_amd.ldm.models.pnp_utils.register_spa_attn_injection")
-        pl = plan_fusion(cfg, L * F_, n, self.halo_hw if self.halo_exchange is not None else None, self.live_chunks)
-        fusion, flow, alpha, hw = pl["fusion"], pl["flow"], pl["alpha"], pl["warp_hw"]
-        warp = hw is not None
+        pl = self._hook_plan(attn1, L * F_, n)
+        fusion = pl["fusion"]
+        warp = pl["warp_hw"] is not None
         assert L == 3 or not warp
         sharded = warp and self.halo_exchange is not None
         ab = hip.groupnorm_coeffs_from_cols(x.cs, p["gn"][0], p["gn"][1], nimg=(L - 1) * F_, hw=n, C_=c, eps=1e-6)
@@ -958,40 +907,31 @@ class UNetEngine(_StepReplay):
                      rows_full=M2 if fusion == hip.FUSION_NONE else Fn, nq_lo=0 if fusion == hip.FUSION_NONE else 2 * d, ln=ln)
         if fusion == hip.FUSION_LINEAR and L == 3:
             wlin = self._wlin(p, *pl["wlin"])
-            ldl = ln.stride(0)
-
-            def fused(src, dst):      # own rows `src`, structure rows = A (chunk 0's LayerNorm output)
-                hip.gemm(src, wlin, dst, M=Fn, N=2 * d, K=2 * d, lda=ldl, ldc=dst.stride(0), ldw=2 * d, a2=ln, lda2=ldl, k1=d,
-                         split_k=False)
+            # (own rows, then the structure rows = A, chunk 0's LayerNorm output)
             if warp:
                 T = self._new(Fn, 2 * d)
-                fused(ln, T)                                  # chunk 1 (its own rows are A's)
+                self._fused_qk(ln, ln, wlin, T, Fn, d)                             # chunk 1 (its own rows are A's)
                 halo = None
                 if sharded:
                     handle = self._halo_start(T[(F_ - 1) * n:])
-                fused(ln[Fn:], qkv[Fn:, :2 * d])              # chunk 2
+                self._fused_qk(ln[Fn:], ln, wlin, qkv[Fn:, :2 * d], Fn, d)         # chunk 2
                 if sharded:
                     halo = self._halo_finish(handle)
-                hip.flow_warp(T, qkv3[:Fn, :2 * d], flow, F=F_, h=hw[0], w=hw[1], C_=2 * d, ld_src=2 * d, fs_src=n * 2 * d,
-                              ld_dst=3 * d, fs_dst=n * 3 * d, alpha=alpha, prev=halo, ld_prev=2 * d,
-                              flow_prev=self.halo_flow if halo is not None else None)
+                self._warp(T, qkv3[:Fn, :2 * d], pl, F_, n, d, halo)
             else:
-                fused(ln[Fn:], qkv[Fn:, :2 * d])              # chunk 2; chunk 1's FSAI(q0, q0) is q0
-        kw = dict(heads=heads, n=n, nk=n, dh=d // heads, ldq=3 * d, ldk=3 * d, ldv=3 * d, bsq=n * 3 * d, bsk=n * 3 * d,
-                  bsv=n * 3 * d, ldo=d, bso=n * d,
-                  scale=float(np.float32(1.0) / np.sqrt(np.float32(d // heads))))   # fp32 arithmetic, as capi.cpp computes it
+                self._fused_qk(ln[Fn:], ln, wlin, qkv[Fn:, :2 * d], Fn, d)         # chunk 2; chunk 1's FSAI(q0, q0) is q0
         if warp:
             att = self._new(M3, d)
-            hip.attention(qkv3, qkv3[:, d:], qkv3[:, 2 * d:], att, B=3 * F_, qk_map=self._map("share_qk", 3 * F_, F_),
-                          v_map=self._map("share_v", 3 * F_, F_), **kw)
+            qkv_attention(qkv3, att, B=3 * F_, n=n, d=d, heads=heads, qk_map=self._map("share_qk", 3 * F_, F_),
+                          v_map=self._map("share_v", 3 * F_, F_))
             att_0, att_12 = att, att[Fn:]
         else:
             att = self._new(M2, d)
             if fusion == hip.FUSION_REPLACE and hip.load().vface_attention_shared_scores_supported(d // heads, 3):
-                hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=F_, v_sets=3, v_sets_live=2, set_stride=F_, **kw)
+                qkv_attention(qkv, att, B=F_, n=n, d=d, heads=heads, v_sets=3, v_sets_live=2, set_stride=F_)
             else:
-                hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=(L - 1) * F_,
-                              qk_map=self._map("qk_replace", 2 * F_, F_) if fusion == hip.FUSION_REPLACE else None, **kw)
+                qkv_attention(qkv, att, B=(L - 1) * F_, n=n, d=d, heads=heads,
+                              qk_map=self._map("qk_replace", 2 * F_, F_) if fusion == hip.FUSION_REPLACE else None)
             att_0, att_12 = att, att
         o16, cs, o32 = post
         for r0, rows, a_, s0 in ((0, Fn, att_0, 0), (Fn, (L - 1) * Fn, att_12, F_)):
@@ -1066,13 +1006,20 @@ class UNetEngine(_StepReplay):
             return adain
         raise ValueError(mode)
 
-    def _ffn_ok(self, M: int, c: int) -> bool:
-        """``vface_ffn_fused_supported`` per (rows, width), asked once (a ctypes call per block per forward otherwise)."""
-        key = (M, c)
-        ok = self._ffn_supported.get(key)
+    def _supported(self, rule, *shape) -> bool:
+        """A host-side shape rule of the library (``hip.*_supported``) per shape, asked once (a ctypes call per block per forward
+        otherwise)."""
+        key = (rule,) + shape
+        ok = self._shape_ok.get(key)
         if ok is None:
-            ok = self._ffn_supported[key] = bool(hip.ffn_fused_supported(M, c))
+            ok = self._shape_ok[key] = bool(rule(*shape))
         return ok
+
+    def _ffn_ok(self, M: int, c: int) -> bool:
+        return self._supported(hip.ffn_fused_supported, M, c)
+
+    def _front_ok(self, M: int, c: int, n: int) -> bool:
+        return self._supported(hip.st_front_supported, M, c, n)
 
     def _st(self, x: Act, p: dict, mod, a2_all: torch.Tensor, tgt) -> Act:
         """SpatialTransformer.forward + BasicTransformerBlock._forward (attention.py:278-289, 239-243).

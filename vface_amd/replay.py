@@ -79,7 +79,7 @@ class _GraphSegments:
                 pass
             self.cur = None
 
-    # ---- the exchange interface (parallel.FrameShard), as seen by UNetEngine._attn1_sharded while capturing
+    # ---- the exchange interface (parallel.FrameShard), as seen by UNetEngine._attn1_qkv_att while capturing
     def set_index(self, k: int) -> None:
         self.index = int(k)
 
