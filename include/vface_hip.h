@@ -231,7 +231,9 @@ int vface_im2col(const void* X, int64_t ldx, int nimg, int H, int W, int C, int 
                  int64_t ldo, int dtype, void* stream);
 
 /* nn.InstanceNorm2d statistics (per image and channel over hw pixels, biased variance): stats [nimg][C][2] = (mean, rstd);
- * `partial` = vface_channel_stats_partial_floats(nimg, hw, C) floats of scratch (fixed summation order: reproducible). */
+ * `partial` = vface_channel_stats_partial_floats(nimg, hw, C) floats of scratch (fixed summation order: reproducible).
+ * The moments are accumulated around each channel's value at the image's first pixel, so their error follows the spread of
+ * the data and not mean^2 / var. */
 int64_t vface_channel_stats_partial_floats(int nimg, int hw, int C);
 int vface_channel_stats(const void* x, int64_t ldx, int nimg, int hw, int C, float eps, float* partial, float* stats, int dtype,
                         void* stream);

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, rel_l2
+from kernel_bounds import U32, rnd, sentinel, ulp
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +22,6 @@ def hip():
     from vface_amd import hip as h
     h.load()
     return h
-
-
-def rnd(shape, seed, dt, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(shape, generator=g) * scale).to(dt)
 
 
 # 0 = automatic schedule; 5..8 forced product schedules (include/vface_hip.h).  (Codes 1..4, 9, 10 were the experimental schedules
@@ -1556,22 +1552,7 @@ def test_attention_wave_count_and_query_tiling_do_not_change_bits(dh, n, B):
 # Buffers laid out as engine.staged_attn1 lays them: one qkv buffer [3 F n, 3d], q|k = C_ = 2d columns at ld = 3d, frame stride
 # n 3d, chunk k at rows [k F n, (k + 1) F n).  The whole buffer starts as a sentinel pattern, so a write outside the q|k columns
 # of the target chunks shows.
-U32 = 2.0 ** -24                                   # fp32 unit roundoff
-MANT = {torch.float16: (10, -14), torch.bfloat16: (7, -126)}     # explicit mantissa bits, smallest normal exponent
-
-
-def ulp(ref64, dt):
-    """One unit in the last place of ``dt`` at each element of the fp64 ``ref64`` (the subnormal spacing below the normals)."""
-    p, emin = MANT[dt]
-    _, e = torch.frexp(ref64.abs())                # |r| = m 2^e, m in [0.5, 1): floor(log2 |r|) = e - 1
-    e = torch.where(ref64 == 0, torch.full_like(e, emin + 1), e)
-    return torch.exp2((torch.clamp(e - 1, min=emin) - p).double())
-
-
-def sentinel(rows, cols, dt):
-    """-63.5 .. 63.5 in steps of 0.25 along the flat index, period 509 (built in the 16-bit type: the buffers reach 0.75 GB)."""
-    period = ((torch.arange(509, dtype=torch.float32) - 254) * 0.25).to(dt)
-    return period.repeat(-(-rows * cols // 509))[:rows * cols].reshape(rows, cols)
+# (U32, ulp() and sentinel() live in tests/kernel_bounds.py, shared with test_glue_kernels_gpu.py)
 
 
 # (the largest clips at the largest maps are trimmed to ~0.2 GB of buffer, except the level-0 pairing n = 4096, d = 320 at every F,

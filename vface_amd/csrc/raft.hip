@@ -30,9 +30,13 @@ enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_SIGMOID = 3 };
 __device__ __forceinline__ float act_f(float v, int act) {
     if (act == ACT_RELU) return fmaxf(v, 0.0f);
     if (act == ACT_TANH) return tanhf(v);
-    if (act == ACT_SIGMOID) return 1.0f / (1.0f + __expf(-v));
+    // expf, not __expf: the fast form rounds v * log2(e) before the exponential, a relative error of about |v| u -- 20 u at
+    // v = -30, which an fp32 output (y32) shows
+    if (act == ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
     return v;
 }
+// the ConvGRU gates round to 16 bits at once: the fast exponential's |v| u is far below their half ulp
+__device__ __forceinline__ float sigmoid_fast(float v) { return 1.0f / (1.0f + __expf(-v)); }
 
 // out[m][tap * C + c] = x[img][oy * stride - pad_y + ky][ox * stride - pad_x + kx][c] (zero outside), 8 channels per thread
 template <class TT>
@@ -57,7 +61,9 @@ __global__ __launch_bounds__(256) void im2col_kernel(const typename TT::elem* __
     }
 }
 
-// partial[(img * S + s)][C][2] = (sum, sum of squares) over pixel slice s of image img; a block covers 64 channels
+// partial[(img * S + s)][C][2] = (sum, sum of squares) of x - pivot over pixel slice s of image img, pivot = the channel's value at
+// the image's first pixel (the same for every slice, so the slices add up); a block covers 64 channels.  Raw sums would lose
+// digits in proportion to mean^2 / var in `q / hw - mean^2`; around a pivot taken from the data the loss follows the spread only.
 template <class TT>
 __global__ __launch_bounds__(256) void chan_stats_partial_kernel(const typename TT::elem* __restrict__ x, long ldx, int hw, int C, int S,
                                                                  float* __restrict__ partial) {
@@ -66,15 +72,19 @@ __global__ __launch_bounds__(256) void chan_stats_partial_kernel(const typename 
     const int img = blockIdx.y, s = blockIdx.z, t = threadIdx.x;
     const int chunk = t & 7, lane = t >> 3, c0 = blockIdx.x * 64 + chunk * 8;
     const int per = (hw + S - 1) / S, p0 = s * per, p1 = min(hw, p0 + per);
-    float sum[8], sq[8];
+    float sum[8], sq[8], piv[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) sum[j] = sq[j] = 0.0f;
-    if (c0 < C)
+    for (int j = 0; j < 8; ++j) sum[j] = sq[j] = piv[j] = 0.0f;
+    if (c0 < C) {
+        const V8 v0 = *reinterpret_cast<const V8*>(x + (long)img * hw * ldx + c0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) piv[j] = to_f32(v0[j]);
         for (int p = p0 + lane; p < p1; p += 32) {
             const V8 v = *reinterpret_cast<const V8*>(x + ((long)img * hw + p) * ldx + c0);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float f = to_f32(v[j]); sum[j] += f; sq[j] += f * f; }
+            for (int j = 0; j < 8; ++j) { const float f = to_f32(v[j]) - piv[j]; sum[j] += f; sq[j] += f * f; }
         }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { red[lane][chunk * 8 + j][0] = sum[j]; red[lane][chunk * 8 + j][1] = sq[j]; }
     __syncthreads();
@@ -86,8 +96,9 @@ __global__ __launch_bounds__(256) void chan_stats_partial_kernel(const typename 
     }
 }
 
-__global__ __launch_bounds__(256) void chan_stats_finalize_kernel(const float* __restrict__ partial, int nimg, int hw, int C, int S, float eps,
-                                                                  float* __restrict__ stats) {
+template <class TT>
+__global__ __launch_bounds__(256) void chan_stats_finalize_kernel(const typename TT::elem* __restrict__ x, long ldx, const float* __restrict__ partial,
+                                                                  int nimg, int hw, int C, int S, float eps, float* __restrict__ stats) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)nimg * C) return;
     const long img = i / C;
@@ -97,10 +108,10 @@ __global__ __launch_bounds__(256) void chan_stats_finalize_kernel(const float* _
         s += partial[((img * S + k) * C + c) * 2];
         q += partial[((img * S + k) * C + c) * 2 + 1];
     }
-    const double mean = s / hw;
-    double var = q / hw - mean * mean;
+    const double d = s / hw;                                     // mean - pivot
+    double var = q / hw - d * d;
     if (var < 0.0) var = 0.0;
-    stats[i * 2] = (float)mean;
+    stats[i * 2] = (float)((double)to_f32(x[img * hw * ldx + c]) + d);
     stats[i * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
@@ -145,7 +156,7 @@ __global__ __launch_bounds__(256) void gru_gate_kernel(const typename TT::elem* 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long m = i / Hd;
         const int c = (int)(i - m * Hd);
-        const float z = act_f(to_f32(zr[m * ldzr + c]), ACT_SIGMOID), r = act_f(to_f32(zr[m * ldzr + Hd + c]), ACT_SIGMOID);
+        const float z = sigmoid_fast(to_f32(zr[m * ldzr + c])), r = sigmoid_fast(to_f32(zr[m * ldzr + Hd + c]));
         zout[m * ldz + c] = from_f32<E>(z);
         rh[m * ldrh + c] = from_f32<E>(r * h32[i]);
     }
@@ -284,8 +295,9 @@ int vf_launch_chan_stats(const void* x, long ldx, int nimg, int hw, int C, float
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         hipLaunchKernelGGL((chan_stats_partial_kernel<TT>), dim3((C + 63) / 64, nimg, S), dim3(256), 0, stream, (const E*)x, ldx, hw, C, S, partial);
+        hipLaunchKernelGGL((chan_stats_finalize_kernel<TT>), dim3(((long)nimg * C + 255) / 256), dim3(256), 0, stream, (const E*)x, ldx, partial, nimg,
+                           hw, C, S, eps, stats);
     });
-    hipLaunchKernelGGL(chan_stats_finalize_kernel, dim3(((long)nimg * C + 255) / 256), dim3(256), 0, stream, partial, nimg, hw, C, S, eps, stats);
     return ok();
 }
 
