@@ -1,6 +1,7 @@
-"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py): seeded 16-bit inputs, the unit in the last
-place of a 16-bit type, sentinel-filled buffers that show a store outside a kernel's slot, and the element-wise bound check that
-names the worst element.  Plain functions, nothing collected by pytest."""
+"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py): seeded 16-bit inputs, the
+unit in the last place of a 16-bit type, sentinel-filled buffers that show a store outside a kernel's slot, the element-wise bound
+check that names the worst element, and the attention kernel's fp64 reference with its per-element bound.  Plain functions, nothing
+collected by pytest."""
 import torch
 
 U32 = 2.0 ** -24                                   # fp32 unit roundoff
@@ -61,3 +62,58 @@ def cpu_fp32_rel_error(fn, x32, factor=4.0, **kw):
     ok = torch.isfinite(r64) & (r64.abs() >= 2.0 ** -100)
     rel = float(((r32 - r64).abs()[ok] / r64.abs()[ok]).max()) if bool(ok.any()) else 0.0
     return factor * max(rel, 2.0 ** -23)
+
+
+def attention_ref_and_bound(q, k, v, scale, dt, chunk_bytes=4.0e8):
+    """One (sample, head) of ``vface_attention`` in fp64 and what a correct 16-bit streaming-softmax kernel may differ by, per element.
+    ``q [n, dh]``, ``k, v [nk, dh]``: the 16-bit inputs.  Returns ``(o, bound)``, both fp64 ``[n, dh]``, both from fp64 quantities of
+    the reference alone.  With u the unit roundoff of ``dt``, s = scale q k^T, w = softmax(s), o = w v, A = scale |q| |k|^T and
+    dev_jc = v_jc - o_c: for ANY per-score perturbation d_j the kernel's o' obeys o' - o = sum_j w_j (e^{d_j} - 1) dev_j / sum_k w_k
+    e^{d_k} exactly (sum_j w_j dev_j = 0), so with |d_j| <= D, e^{d} - 1 = d + r, |r| <= 0.5 D^2 e^D and a denominator >= e^{-D}:
+
+      bound = e^D (Tq + sum_j w_j ds_j |dev_jc| + 0.5 D^2 e^D sum_j w_j |dev_jc| + tiny sum_j |dev_jc| / L)
+              + u |o| + (nk + 16) U32 (sum_j w_j |v_jc| + |o|) + 2 U32 |o| + 0.5 ulp(|o| + all of the above)
+
+    * Tq_c = u sum_d |q_d| |G_dc|, G_dc = scale sum_j w_j k_jd dev_jc: the default form rounds q * scale * log2(e) to 16 bits once, so
+      d_j is linear in the dh rounding errors of the query, shared by all its keys -- the sum over keys keeps its signs.
+    * ds_j, independent per score: the fp32 dot product (dh + 8) U32 (A_j + max_k A_k) -- the maximum because the default form's
+      score v_mfma_f32_16x16x32 carries -m_ref, as large as the largest score, as its C operand through the whole accumulation (the
+      one term here that is looser than A_j alone); the subtraction of the reference 4 U32 |s_j - max s|; v_exp_f32 8 U32; the
+      rounding of P to 16 bits u.  D = max_j (ds_j + u A_j).
+    * tiny / L, L = sum_j exp(s_j - max s): what the absolute floor of a probability loses against a reference that is never above
+      the row maximum (lazy, speculative and exact form alike).  fp16: 2^-25, half the subnormal spacing -- gradual underflow of the
+      v_cvt_f16_f32 result, the same allowance a softmax rounded to fp16 gets.  bf16: 2^-126, below which v_exp_f32 returns 0.
+    * u |o|: numerator and denominator may see differently rounded P (instantiations without a spare V column sum the fp32 P).
+    * (nk + 16) U32 (sum_j w_j |v_jc| + |o|): fp32 accumulation of O and (the |o| part) of the denominator, both over nk keys.
+    * 2 U32 |o| for the reciprocal and the product, and one final rounding to ``dt`` taken at the largest value the bound admits.
+    Queries are walked in chunks so the [chunk, nk, dh] intermediate stays below ``chunk_bytes``."""
+    u = 2.0 ** -(MANT[dt][0] + 1)
+    tiny = 2.0 ** -25 if dt == torch.float16 else TINY32
+    q64, k64, v64 = q.double(), k.double(), v.double()
+    n, dh = q64.shape
+    nk = k64.shape[0]
+    kv = (k64[:, :, None] * v64[:, None, :]).reshape(nk, dh * dh)
+    o_all, b_all = [], []
+    step = max(1, int(chunk_bytes // (nk * dh * 8)))
+    for i in range(0, n, step):
+        qc = q64[i:i + step]
+        s = (qc @ k64.T) * scale
+        A = (qc.abs() @ k64.abs().T) * scale
+        mx = s.max(dim=1, keepdim=True).values
+        e = torch.exp(s - mx)
+        L = e.sum(dim=1, keepdim=True)
+        w = e / L
+        o = w @ v64
+        G = scale * ((w @ kv).reshape(-1, dh, dh) - (w @ k64)[:, :, None] * o[:, None, :])
+        Tq = u * torch.einsum("qd,qdc->qc", qc.abs(), G.abs())
+        ds = (dh + 8) * U32 * (A + A.max(dim=1, keepdim=True).values) + 4 * U32 * (mx - s) + 8 * U32 + u
+        D = (ds + u * A).max(dim=1, keepdim=True).values
+        eD = torch.exp(D)
+        coef = w * (ds + 0.5 * D * D * eD) + tiny / L
+        X = (v64[None, :, :] - o[:, None, :]).abs()
+        b = eD * (Tq + torch.bmm(coef[:, None, :], X)[:, 0, :])
+        b = b + u * o.abs() + (nk + 16) * U32 * (w @ v64.abs() + o.abs()) + 2 * U32 * o.abs()
+        b = b + 0.5 * ulp(o.abs() + b, dt)
+        o_all.append(o)
+        b_all.append(b)
+    return torch.cat(o_all), torch.cat(b_all)

@@ -82,3 +82,47 @@ def test_spatial_transformer_block_ff_geglu_forward():
     from vface_amd import hip
     with pytest.raises(hip.VFaceHipError):
         mod(x, ctx)          # CPU tensors: no fallback
+
+
+def _block_ref(sd, tp, c, heads, tok, ctx):
+    """BasicTransformerBlock._forward (attention.py:239-243) from the oracle's attention and torch's fp32 layers."""
+    from oracle import hooks as ohooks
+    ln = lambda v, q: F.layer_norm(v, (c,), sd[f"{tp}.{q}.weight"], sd[f"{tp}.{q}.bias"], 1e-5)
+    att = lambda v, a, cx: ohooks.attention(v, sd[f"{tp}.{a}.to_q.weight"], sd[f"{tp}.{a}.to_k.weight"], sd[f"{tp}.{a}.to_v.weight"],
+                                           sd[f"{tp}.{a}.to_out.0.weight"], sd[f"{tp}.{a}.to_out.0.bias"], heads, cx, None, None)
+    t = att(ln(tok, "norm1"), "attn1", None) + tok
+    t = att(ln(t, "norm2"), "attn2", ctx) + t
+    g = F.linear(ln(t, "norm3"), sd[tp + ".ff.net.0.proj.weight"], sd[tp + ".ff.net.0.proj.bias"])
+    a, gate = g.chunk(2, dim=-1)
+    return F.linear(a * F.gelu(gate), sd[tp + ".ff.net.2.weight"], sd[tp + ".ff.net.2.bias"]) + t
+
+
+@pytest.mark.parametrize("m", [77, 5])
+def test_spatial_transformer_block_cross_attention_with_a_context_of_several_tokens(m):
+    """A drop-in caller's ``SpatialTransformer(x, context)`` / ``BasicTransformerBlock(x, context)`` / ``CrossAttention(x, context)``
+    with the 77 tokens of a text encoder (and 5): softmax over more than one key, nk != n, nk < 64 and nk = 64 + 13 -- where the
+    one-token context of the VFace configuration (above) makes the softmax the constant 1."""
+    from oracle import hooks as ohooks
+    from vface_amd.ldm.modules.attention import SpatialTransformer
+    c, heads = 128, 8
+    mod, sd = _filled(SpatialTransformer(c, heads, c // heads, depth=1, context_dim=768), "t.")
+    x = synth.synth_normal("mod.st.x", (3, c, 16, 16))
+    ctx = synth.synth_normal(f"mod.st.ctx{m}", (3, m, 768))
+    got = mod(x.to(DEV), ctx.to(DEV)).float().cpu()
+    ref = ounet._st(ounet._Ctx(sd, None), ounet.Layer("st", "t", c, c, heads), x, ctx, None, (16, 16))
+    assert got.shape == ref.shape and rel_l2(got, ref) < TOL, rel_l2(got, ref)
+    blk = mod.transformer_blocks[0]
+    tp = "t.transformer_blocks.0"
+    tok = synth.synth_normal("mod.blk.x", (3, 256, c))
+    got = blk(tok.to(DEV), ctx.to(DEV)).float().cpu()
+    ref = _block_ref(sd, tp, c, heads, tok, ctx)
+    assert got.shape == ref.shape and rel_l2(got, ref) < TOL, rel_l2(got, ref)
+    # attn2 alone: the context decides the output (a one-token context would not)
+    a2 = blk.attn2
+    q = synth.synth_normal("mod.a2.x", (3, 200, c))
+    got = a2(q.to(DEV), ctx.to(DEV)).float().cpu()
+    w = lambda k: sd[f"{tp}.attn2.{k}"]
+    ref = ohooks.attention(q, w("to_q.weight"), w("to_k.weight"), w("to_v.weight"), w("to_out.0.weight"), w("to_out.0.bias"), heads, ctx, None, None)
+    assert got.shape == ref.shape and rel_l2(got, ref) < TOL, rel_l2(got, ref)
+    other = a2(q.to(DEV), ctx.flip(1).roll(1, 0).to(DEV)).float().cpu()
+    assert rel_l2(other, ref) > 0.05

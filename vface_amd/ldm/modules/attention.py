@@ -56,7 +56,7 @@ class FeedForward(nn.Module):
 
 class CrossAttention(nn.Module):
     """attention.py:152-221.  ``forward`` handles what the path issues: self-attention (``context=None``,
-    optionally hooked) and attention over a single context token; ``mask`` is not used on this path."""
+    optionally hooked) and cross-attention over a context of any length; ``mask`` is not used on this path."""
 
     def __init__(self, query_dim, context_dim=None, heads=8, dim_head=64, dropout=0., sep_head_att=False):
         super().__init__()
@@ -97,7 +97,8 @@ class CrossAttention(nn.Module):
 
 class BasicTransformerBlock(nn.Module):
     """attention.py:224-243.  Inside the UNet the block runs as part of ``UNetEngine._st``; called directly,
-    ``forward(x [B, n, d], context [B, 1, ctx])`` runs the same kernel sequence (``vface_amd.module_exec``)."""
+    ``forward(x [B, n, d], context [B, 1, ctx])`` runs the same kernel sequence (``vface_amd.module_exec``); a context of several
+    tokens runs attn2 as a cross-attention of its own (``module_exec._block_several_tokens``)."""
 
     def __init__(self, dim, n_heads, d_head, dropout=0., context_dim=None, gated_ff=True, checkpoint=True,
                  sep_head_att=False):
@@ -118,7 +119,8 @@ class BasicTransformerBlock(nn.Module):
 
 class SpatialTransformer(nn.Module):
     """attention.py:246-289.  Inside the UNet the layer runs through ``UNetEngine._st``; called directly,
-    ``forward(x [N, C, H, W], context [N, 1, ctx])`` runs the same kernel sequence (``vface_amd.module_exec``)."""
+    ``forward(x [N, C, H, W], context [N, 1, ctx])`` runs the same kernel sequence (``vface_amd.module_exec``); a context of several
+    tokens: see ``BasicTransformerBlock``."""
 
     def __init__(self, in_channels, n_heads, d_head, depth=1, dropout=0., context_dim=None, sep_head_att=False,
                  head_splits=None):

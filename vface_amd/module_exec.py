@@ -94,7 +94,7 @@ def _a2vec(eng: UNetEngine, sd, t: str, context: Optional[torch.Tensor], N: int,
                          "self-attention, which is not part of the VFace configuration")
     ctx = context.reshape(context.shape[0], -1)
     if context.dim() != 3 or context.shape[1] != 1:
-        raise hip.VFaceHipError(f"context must be [N, 1, context_dim] (single token, SURVEY F11); got {tuple(context.shape)}")
+        raise hip.VFaceHipError(f"context must be [N, tokens, context_dim]; got {tuple(context.shape)}")
     c16 = eng._new(N, ctx.shape[1])
     hip.cast_f32(ctx.float().contiguous(), c16)
     v = eng._new(N, c)
@@ -106,6 +106,45 @@ def _a2vec(eng: UNetEngine, sd, t: str, context: Optional[torch.Tensor], N: int,
     return out
 
 
+def _several_tokens(context: Optional[torch.Tensor]) -> bool:
+    return context is not None and context.dim() == 3 and context.shape[1] > 1
+
+
+def _block_several_tokens(eng: UNetEngine, blk, sd, t: str, p: dict, t0: torch.Tensor, context: torch.Tensor, B: int, n: int,
+                          P: dict, want32: bool = False):
+    """``UNetEngine._block`` for a context of SEVERAL tokens (attention.py:239-243 as written): the engine folds the single-token
+    attn2 of the VFace configuration into attn1's epilogue as a row bias; with more tokens attn2 is a real
+    cross-attention between attn1 and the FeedForward -- norm2, to_q of the tokens, to_k / to_v of the context, ``vface_attention``
+    with nk = the context length, to_out into the block's running sum.  ``t0``: that sum ``[B*n, c]``, fp32 or 16-bit."""
+    c, M, a2m = p["c"], t0.shape[0], blk.attn2
+    ln = eng._new(M, c)
+    hip.layernorm(t0, p["ln1"][0], p["ln1"][1], ln, M=M, C_=c, ldx=c, ldy=c)
+    no_bias = torch.zeros(B, c, dtype=torch.float32, device=t0.device)
+    t1 = eng._attn1(ln, t0, p, eng._hook_plan(blk.attn1, B, n), no_bias, B, n, blk.attn1.heads)
+    if "x2" not in P:
+        P["x2"] = {"ln2": (eng._f32(sd[t + ".norm2.weight"]), eng._f32(sd[t + ".norm2.bias"])),
+                   "wq": eng.pack_lin(sd, t + ".attn2.to_q", bias=False), "wk": eng.pack_lin(sd, t + ".attn2.to_k", bias=False),
+                   "wv": eng.pack_lin(sd, t + ".attn2.to_v", bias=False), "wo": eng.pack_lin(sd, t + ".attn2.to_out.0")}
+    x2 = P["x2"]
+    hip.layernorm(t1, x2["ln2"][0], x2["ln2"][1], ln, M=M, C_=c, ldx=c, ldy=c)
+    m, d2 = context.shape[1], a2m.heads * a2m.dim_head
+    c16 = eng._new(B * m, context.shape[2])
+    hip.cast_f32(context.reshape(B * m, -1).float().contiguous(), c16)
+    q, k, v, att = eng._new(M, d2), eng._new(B * m, d2), eng._new(B * m, d2), eng._new(M, d2)
+    eng._gemm(ln, x2["wq"], q)
+    eng._gemm(c16, x2["wk"], k)
+    eng._gemm(c16, x2["wv"], v)
+    hip.attention(q, k, v, att, B=B, heads=a2m.heads, n=n, nk=m, dh=a2m.dim_head, ldq=d2, ldk=d2, ldv=d2, bsq=n * d2, bsk=m * d2,
+                  bsv=m * d2, ldo=d2, bso=n * d2, scale=a2m.scale)
+    if t1.dtype == torch.float32:
+        t1b = eng._new(M, c, torch.float32)
+        eng._gemm(att, x2["wo"], None, hw=n, residual32=t1, out32=t1b)
+    else:
+        t1b = eng._new(M, c)
+        eng._gemm(att, x2["wo"], t1b, hw=n, residual=t1, ldr=t1.stride(0))
+    return eng._ffn(t1b, p, n, want32)
+
+
 def spatial_transformer_forward(mod, x: torch.Tensor, context: Optional[torch.Tensor]) -> torch.Tensor:
     eng, P = _engine_for(mod, x)
     sd = {("." + k): v for k, v in _sd(mod).items()}
@@ -113,6 +152,17 @@ def spatial_transformer_forward(mod, x: torch.Tensor, context: Optional[torch.Te
         P["st"] = eng.pack_st(sd, "")
     p = dict(P["st"])
     a = _to_act(eng, x)
+    if _several_tokens(context):
+        # (GroupNorm, proj_in and proj_out + x as the separate launches of UNetEngine._st)
+        c, hw = p["c"], a.H * a.W
+        g = eng._gn(a, p["gn"], 1e-6, False)
+        s32 = eng.stream32 and c % 8 == 0
+        t0 = eng._new(a.M, c, torch.float32 if s32 else None)
+        eng._gemm(g.t, p["proj_in"], None if s32 else t0, hw=hw, **({"out32": t0} if s32 else {}))
+        t2 = _block_several_tokens(eng, mod.transformer_blocks[0], sd, ".transformer_blocks.0", p, t0, context, a.N, hw, P)
+        out, cs, o32 = eng._new_target(a.M, c, hw)
+        eng._gemm(t2, p["proj_out"], out, colstats=cs, hw=hw, out32=o32, **eng._resid(a))
+        return _from_act(Act(out, a.N, a.H, a.W, cs, o32), x)
     a2 = _a2vec(eng, sd, ".transformer_blocks.0", context, a.N, p["c"], P)
     p["a2_slice"] = (0, p["c"])
     y = eng._st(a, p, mod, a2, None)
@@ -132,6 +182,8 @@ def transformer_block_forward(mod, x: torch.Tensor, context: Optional[torch.Tens
     else:
         t0 = eng._new(B * n, d)
         hip.cast_f32(x.reshape(B * n, d).float().contiguous(), t0)
+    if _several_tokens(context):
+        return _block_several_tokens(eng, mod, sd, "", p, t0, context, B, n, P, want32=True)[1].reshape(B, n, d).to(x.dtype)
     a2 = _a2vec(eng, sd, "", context, B, d, P)
     t2, t2_32 = eng._block(t0, p, mod.attn1, a2, B, n, None, want32=True)
     return t2_32.reshape(B, n, d).to(x.dtype)
