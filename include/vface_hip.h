@@ -301,6 +301,32 @@ int vface_perspective_paste(const uint8_t* crop, int crop_w, int crop_h, uint8_t
  * kernel differs from it by <= 2 ulp (tests bound it at 2e-6). */
 int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out, int OW, int OH, int frames, void* stream);
 
+/* ---- frame intake: decoded frame -> aligned crop -> the sampler's tensors (the mirror image of the paste-back) ---------------
+ * The reference runs these steps per frame on the host with Pillow and numpy.  The Lanczos shrink of a large face
+ * (alignmengt.py:108-114) and the bicubic resize to 512 x 512 (video_swap_dataset.py:139) are vface_resample_u8 with the tap
+ * tables of those filters (vface_amd/scripts/intake.py `resample_coeffs`).
+ *
+ * vface_quad_crop: the "Crop" and "Transform" steps of `crop_image` (REFace/src/utils/alignmengt.py:115-123, :142, reached from
+ *   crop_faces_by_quads :255-263): `img.crop(window)` then `img.transform((out_size, out_size), Image.QUAD, quad + 0.5,
+ *   Image.BILINEAR)` (Pillow Geometry.c quad_transform / bilinear_filter32RGB), without materialising the cropped image.
+ *   frames [nframes][H][W][3]; out [nframes][out_size][out_size][3]; quads [nframes][8] doubles = the coefficients Pillow's
+ *   Image.__transformer derives from the quad (a0 + a1 x + a2 y + a3 x y ; a4 ..), in WINDOW coordinates; windows [nframes][4]
+ *   int32 = (x0, y0, x1, y1) of the crop window inside the frame, 0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H.  Taps are clamped
+ *   to the window, pixels that map outside it are 0 in all three bytes.  Bit-identical to Pillow. */
+int vface_quad_crop(const uint8_t* frames, int W, int H, uint8_t* out, int out_size, int nframes, const double* quads,
+                    const int32_t* windows, void* stream);
+
+/* vface_dataset_tensors: `VideoDataset.__getitem_gray__` (REFace/ldm/data/video_swap_dataset.py:157-163, :214-221) and the mask
+ *   resize of REFace/scripts/VFace_inference_batch.py:459.  crop [nframes][H][W][3] uint8, label [nframes][H][W] uint8 (any value
+ *   0..255), member[256] uint8: non-zero where the label is on the `remove_mask_tar_FFHQ` list.
+ *     image         [nframes][3][H][W]   fp32 = (u8 / 255 - 0.5) / 0.5            get_tensor() (:214)
+ *     inpaint_mask  [nframes][1][H][W]   fp32 = 1 - isin(label, remove)             (:219)
+ *     inpaint_image [nframes][3][H][W]   fp32 = image * inpaint_mask                (:221)
+ *     mask_latent   [nframes][1][OH][OW] fp32 = transforms.Resize([OH, OW])(inpaint_mask): bilinear, align_corners false, no
+ *                   antialias (:459), fp32 in vface_frame_normalise_resize's order; computed from the label map itself. */
+int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, const uint8_t* member, int W, int H, float* image,
+                          float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH, int nframes, void* stream);
+
 /* The hooked self-attention as one call (pnp_utils.py:94-287, the closure installed on attn1):
  *   x [B][n][d] (already LayerNorm'd), B = chunks * F laid out [uncond ; cond ; recon]
  *   Wqkv [3d][d]  = rows of to_q | to_k | to_v

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Timings of the widened rows at the sizes the 8-frame / 16-frame workloads use, HIP events on the launch
-stream: the RAFT-shaped flow producer (F - 1 pairs of 512 x 512 frames, 20 updates) and the paste-back (F decoded 512 x 512
-crops -> 1024 canvas -> 1024 x 1024 frames), with the per-step DDIM time of bench.py beside them for scale.
-usage: python tools/bench_widening.py [--frames 8]"""
+stream: the RAFT-shaped flow producer (F - 1 pairs of 512 x 512 frames, 20 updates), the paste-back (F decoded 512 x 512
+crops -> 1024 canvas -> 1024 x 1024 frames) and the frame intake (F frames of 1080 x 1920 -> 1024 x 1024 aligned crops -> 512 x 512
+sampler tensors), each next to the same Pillow calls on the host.
+usage: python tools/bench_widening.py [--frames 8] [--only intake]"""
 import argparse
 import os
 import statistics
@@ -36,8 +37,11 @@ def main():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--frame_size", type=int, default=1024)
+    ap.add_argument("--only", choices=["intake"], default=None, help="time this row alone")
     a = ap.parse_args()
     F_, R, S = a.frames, a.res, a.frame_size
+    if a.only == "intake":
+        return bench_intake(F_, R)
     from vface_amd.raft import RAFT
     from vface_amd.scripts import temporal_flow as tflow
     from vface_amd.scripts.paste_back import PasteBack
@@ -79,6 +83,68 @@ def main():
         bg = Image.fromarray(fr).convert("RGBA")
         bg.alpha_composite(sw.transform((S, S), Image.PERSPECTIVE, co[0], Image.BILINEAR))
     print(f"the same three Pillow calls on the host (no VAE, no PCIe): {(time.time() - t0) / 3 * 1e3:8.1f} ms per frame", flush=True)
+
+    bench_intake(F_, R)
+
+
+def bench_intake(F_, R, image_size=1024, Hs=1080, Ws=1920):
+    """The frame intake (scripts/intake.py) at the reference's sizes: F frames of 1080 x 1920 -> 1024 x 1024 aligned crops -> R x R
+    sampler tensors, launch by launch with the HBM bytes each one has to move (compulsory traffic: every input byte it touches
+    once, every output byte once), and the same Pillow / numpy / torch calls on the host for one frame."""
+    import time
+    from PIL import Image
+    from vface_amd import hip
+    from vface_amd.scripts.intake import FrameIntake, crop_plan
+    from vface_amd.scripts.VFace_inference_batch import REMOVE_MASK_TAR_FFHQ
+    S, lat = image_size, (R // 8, R // 8)
+    frames = torch.randint(0, 256, (F_, Hs, Ws, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1)).to(DEV)
+    labels = torch.randint(0, 19, (F_, R, R), dtype=torch.uint8, generator=torch.Generator().manual_seed(2)).to(DEV)
+    quads = np.empty((F_, 4, 2))
+    for f in range(F_):          # a face 600 px wide, rotated 7 degrees, drifting
+        th = np.deg2rad(7.0)
+        c, x = np.array([Ws / 2 + 5.0 * f, Hs / 2 + 2.0 * f]), 300.0 * np.array([np.cos(th), np.sin(th)])
+        y = np.flipud(x) * [-1, 1]
+        quads[f] = np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+    fi = FrameIntake(image_size=S, H=R, W=R, latent=lat, device=DEV)
+    plans = [crop_plan(q, Ws, Hs, S) for q in quads]
+    assert all(p[0] <= 1 for p in plans)
+    co = torch.from_numpy(np.stack([p[3] for p in plans])).to(DEV)
+    win = torch.tensor([p[2] for p in plans], dtype=torch.int32).to(DEV)
+    window_px = sum((p[2][2] - p[2][0]) * (p[2][3] - p[2][1]) for p in plans)
+    crops = hip.quad_crop(frames, co, win, S)
+    tx, ty = fi._table(S, R, "bicubic"), fi._table(S, R, "bicubic")
+    half = hip.resample_u8(crops, R, 0, *tx)
+    small = hip.resample_u8(half, R, 1, *ty)
+    member = hip.label_membership(REMOVE_MASK_TAR_FFHQ, DEV)
+    rows = [("quad_crop", lambda: hip.quad_crop(frames, co, win, S), window_px * 3 + F_ * S * S * 3),
+            ("resample_u8 bicubic, x", lambda: hip.resample_u8(crops, R, 0, *tx), F_ * (S * S * 3 + S * R * 3)),
+            ("resample_u8 bicubic, y", lambda: hip.resample_u8(half, R, 1, *ty), F_ * (S * R * 3 + R * R * 3)),
+            ("dataset_tensors (+ mask_latent)", lambda: hip.dataset_tensors(small, labels, member, lat),
+             F_ * (R * R * 4 + R * R * 7 * 4 + lat[0] * lat[1] * 4))]
+    print(f"frame intake: {F_} frames {Hs}x{Ws} -> {S}x{S} crops -> {R}x{R} tensors (median of 5, output allocation included)", flush=True)
+    total = 0.0
+    for name, fn, nbytes in rows:
+        t = time_ms(fn)
+        total += t
+        print(f"   {name:34s} {t * 1e3:8.1f} us  {nbytes / 1e6:7.1f} MB  {nbytes / t / 1e6:7.1f} GB/s", flush=True)
+    print(f"   sum of the launches                {total * 1e3:8.1f} us  ({total / F_ * 1e3:6.1f} us per frame)", flush=True)
+    t = time_ms(lambda: fi(frames, quads, labels, REMOVE_MASK_TAR_FFHQ))
+    print(f"   FrameIntake.__call__ (host scalars, coefficient upload, inv_transforms included): {t:8.2f} ms", flush=True)
+    # the reference's host route for one frame: crop_image (:115-123, :142), resize (:139), tensors (:157-221), Resize (:459)
+    fr, lab, q0 = frames[0].cpu().numpy(), labels[0].cpu().numpy(), quads[0]
+    t0 = time.time()
+    for _ in range(3):
+        _, _, window, _ = crop_plan(q0, Ws, Hs, S)
+        img = Image.fromarray(fr).crop(window)
+        img = img.transform((S, S), Image.QUAD, (q0 - window[0:2] + 0.5).flatten(), Image.BILINEAR)
+        img_p = img.convert("RGB").resize((R, R))
+        image = (torch.from_numpy(np.array(img_p)).permute(2, 0, 1).float().div(255) - 0.5) / 0.5
+        conv = np.zeros_like(lab)
+        conv[np.isin(lab, REMOVE_MASK_TAR_FFHQ)] = 255
+        m = 1 - torch.from_numpy(conv)[None].float().div(255)
+        inpaint = image * m
+        torch.nn.functional.interpolate(m[None], size=lat, mode="bilinear", align_corners=False)
+    print(f"   the same Pillow / numpy / torch calls on the host (no PCIe): {(time.time() - t0) / 3 * 1e3:8.1f} ms per frame", flush=True)
 
 
 if __name__ == "__main__":

@@ -266,6 +266,17 @@ int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out,
     return vf_launch_frame_normalise_resize(frame, W, H, out, OW, OH, frames, S(stream));
 }
 
+int vface_quad_crop(const uint8_t* frames, int W, int H, uint8_t* out, int out_size, int nframes, const double* quads,
+                    const int32_t* windows, void* stream) {
+    return vf_launch_quad_crop(frames, W, H, out, out_size, nframes, quads, windows, S(stream));
+}
+
+int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, const uint8_t* member, int W, int H, float* image,
+                          float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH, int nframes, void* stream) {
+    return vf_launch_dataset_tensors(crop, label, member, W, H, image, inpaint_image, inpaint_mask, mask_latent, OW, OH, nframes,
+                                     S(stream));
+}
+
 size_t vface_attn1_workspace_bytes(int B, int n, int d, int chunks) {
     if (B <= 0 || n <= 0 || d <= 0 || chunks <= 0) return 0;
     const size_t F = (size_t)B / chunks;

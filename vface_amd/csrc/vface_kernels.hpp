@@ -223,6 +223,12 @@ int vf_launch_perspective_paste(const unsigned char* crop, int sw, int sh, unsig
                                 const double* coeffs_dev, const double* coeffs_host, hipStream_t stream);
 int vf_launch_frame_normalise_resize(const unsigned char* frame, int W, int H, float* out, int OW, int OH, int frames,
                                      hipStream_t stream);
+// intake.hip: frame -> aligned crop -> sampler tensors (alignmengt.py:99-145, video_swap_dataset.py:135-240, VFace_inference_batch.py:459)
+int vf_launch_quad_crop(const unsigned char* frames, int Ws, int Hs, unsigned char* out, int S, int nframes, const double* quads,
+                        const int* windows, hipStream_t stream);
+int vf_launch_dataset_tensors(const unsigned char* crop, const unsigned char* label, const unsigned char* member, int W, int H,
+                              float* image, float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH,
+                              int nframes, hipStream_t stream);
 int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, int dtype, hipStream_t stream);
 int vf_launch_silu(const void* x, void* y, long count, int in_f32, int dtype, hipStream_t stream);
 int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, int N, float scale, int dtype, hipStream_t stream);

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -82,6 +82,8 @@ SIGNATURES = {
     "vface_resample_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "vface_perspective_paste": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_frame_normalise_resize": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vface_attn1_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "vface_attn1_forward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32,
                                       _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp,
@@ -495,6 +497,72 @@ def frame_normalise_resize(frame: torch.Tensor, OH: int, OW: int) -> torch.Tenso
     out = torch.empty(F_, 3, OH, OW, dtype=torch.float32, device=frame.device)
     _check(load().vface_frame_normalise_resize(_p(frame), W, H, _p(out), OW, OH, F_, _stream()), "vface_frame_normalise_resize")
     return out
+
+
+def quad_crop(frames: torch.Tensor, quads: torch.Tensor, windows: torch.Tensor, out_size: int,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``img.crop(window).transform((out_size, out_size), QUAD, .., BILINEAR)`` of uint8 frames [F, H, W, 3] (alignmengt.py:115-123,
+    :142), bit-identical to Pillow.  ``quads`` float64 device [F, 8]: Pillow's QUAD coefficients in window coordinates;
+    ``windows`` int32 [F, 4] (host or device): the crop window (x0, y0, x1, y1) of each frame, inside it and not empty.  Returns
+    uint8 [F, out_size, out_size, 3] (``out`` if given)."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise VFaceHipError("quad_crop: frames must be contiguous uint8 [F, H, W, 3]")
+    F_, H, W, _ = frames.shape
+    if out_size <= 0 or F_ <= 0:
+        raise VFaceHipError("quad_crop: the output size and the number of frames must be positive")
+    if not quads.is_cuda or quads.dtype != torch.float64 or tuple(quads.shape) != (F_, 8) or not quads.is_contiguous():
+        raise VFaceHipError("quad_crop: quads must be a contiguous float64 device tensor [F, 8]")
+    if windows.dtype != torch.int32 or tuple(windows.shape) != (F_, 4):
+        raise VFaceHipError("quad_crop: windows must be int32 [F, 4]")
+    wh = windows.cpu()
+    if bool(((wh[:, 0] < 0) | (wh[:, 1] < 0) | (wh[:, 2] > W) | (wh[:, 3] > H) | (wh[:, 0] >= wh[:, 2]) | (wh[:, 1] >= wh[:, 3])).any()):
+        raise VFaceHipError("quad_crop: every window must be a non-empty rectangle inside its frame")
+    windows = windows.to(frames.device).contiguous()
+    if out is None:
+        out = torch.empty(F_, out_size, out_size, 3, dtype=torch.uint8, device=frames.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F_, out_size, out_size, 3) or not out.is_contiguous():
+        raise VFaceHipError("quad_crop: out must be contiguous uint8 [F, out_size, out_size, 3]")
+    rc = load().vface_quad_crop(_p(frames), W, H, _p(out), out_size, F_, _p(quads), _p(windows), _stream())
+    _check(rc, "vface_quad_crop")
+    return out
+
+
+def label_membership(remove_labels, device) -> torch.Tensor:
+    """The 256-entry table ``member[v] = v in remove_labels`` that ``dataset_tensors`` reads in place of ``np.isin``."""
+    member = torch.zeros(256, dtype=torch.uint8)
+    for v in remove_labels:
+        if not 0 <= int(v) <= 255:
+            raise VFaceHipError(f"label {v} is outside an 8-bit label map")
+        member[int(v)] = 1
+    return member.to(device)
+
+
+def dataset_tensors(crop: torch.Tensor, label: torch.Tensor, member: torch.Tensor, latent: Tuple[int, int], out=None):
+    """``VideoDataset.__getitem_gray__`` (video_swap_dataset.py:157-163, :214-221) + the mask resize of VFace_inference_batch.py:459
+    for uint8 crops [F, H, W, 3] and uint8 label maps [F, H, W]; ``member``: ``label_membership(remove_labels)``; ``latent`` =
+    (h, w) of the latent grid.  Returns fp32 ``image [F, 3, H, W], inpaint_image [F, 3, H, W], inpaint_mask [F, 1, H, W],
+    mask_latent [F, 1, h, w]`` (written into the four tensors of ``out`` if given)."""
+    if crop.dtype != torch.uint8 or crop.dim() != 4 or crop.shape[3] != 3 or not crop.is_contiguous():
+        raise VFaceHipError("dataset_tensors: crops must be contiguous uint8 [F, H, W, 3]")
+    F_, H, W, _ = crop.shape
+    if label.dtype != torch.uint8 or tuple(label.shape) != (F_, H, W) or not label.is_contiguous():
+        raise VFaceHipError(f"dataset_tensors: label maps must be contiguous uint8 {[F_, H, W]}, the crops' size; got {list(label.shape)}")
+    if member.dtype != torch.uint8 or tuple(member.shape) != (256,) or not member.is_contiguous():
+        raise VFaceHipError("dataset_tensors: member must be the uint8 [256] table of label_membership()")
+    oh, ow = int(latent[0]), int(latent[1])
+    if min(F_, H, W, oh, ow) <= 0:
+        raise VFaceHipError("dataset_tensors: F, H, W and the latent grid must be positive")
+    shapes = [(F_, 3, H, W), (F_, 3, H, W), (F_, 1, H, W), (F_, 1, oh, ow)]
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=crop.device) for s in shapes)
+    for t, s in zip(out, shapes):
+        if t.dtype != torch.float32 or tuple(t.shape) != s or not t.is_contiguous():
+            raise VFaceHipError(f"dataset_tensors: outputs must be contiguous fp32 {shapes}")
+    image, inpaint, mask, mlat = out
+    rc = load().vface_dataset_tensors(_p(crop), _p(label), _p(member), W, H, _p(image), _p(inpaint), _p(mask), _p(mlat), ow, oh, F_,
+                                      _stream())
+    _check(rc, "vface_dataset_tensors")
+    return image, inpaint, mask, mlat
 
 
 def attn1_workspace_bytes(B: int, n: int, d: int, chunks: int) -> int:

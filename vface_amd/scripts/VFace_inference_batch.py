@@ -66,7 +66,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--paste_back", action="store_true",
                    help="with --with_vae: paste the decoded crops into (synthetic) original frames on the GPU, the block of "
                         "VFace_inference_batch.py:603-636 (scripts/paste_back.py); --only_target_crop is implied")
-    p.add_argument("--frame_size", type=int, default=1024, help="side of the synthetic original frames of --paste_back")
+    p.add_argument("--frame_size", type=int, default=1024, help="side of the synthetic original frames of --paste_back / --intake")
+    p.add_argument("--intake", action="store_true",
+                   help="with --with_vae: start from (synthetic) video frames, one quad per frame and a label map, and make the "
+                        "aligned crops, the images, inpaint images and the latent mask on the GPU -- crop_faces_by_quads "
+                        "(alignmengt.py:255-263), VideoDataset.__getitem_gray__ (video_swap_dataset.py:135-240) and :459 "
+                        "(scripts/intake.py); with --paste_back the same frames and their inv_transforms (:68-71) are pasted into")
     p.add_argument("--with_vae", action="store_true",
                    help="synthetic run through the first-stage KL-VAE too: the inpaint latents come from encode_first_stage of "
                         "synthetic images (:456-457) and the samples are decoded to pixels (:596-600)")
@@ -216,11 +221,36 @@ def _quad_coeffs(size, quad):
     return np.linalg.solve(np.array(A, float), np.array(B, float))
 
 
+REMOVE_MASK_TAR_FFHQ = (1, 2, 3, 5, 6, 7, 9)      # models/REFace/configs/project_ffhq.yaml: remove_mask_tar_FFHQ
+
+
+def synthetic_intake_inputs(F_: int, S_: int, H: int, W: int, seed: int):
+    """Stand-ins for what video decoding, landmark detection and face parsing hand to the intake: seeded uint8 frames
+    [F, S, S, 3], one quad [4, 2] per frame (NW, SW, SE, NE; half the frame wide, rotating and drifting from frame to frame, the
+    first one partly outside the frame) and a label map [F, H, W] with the parser's values 0..18 in rings round the centre."""
+    import numpy as np
+    gen = torch.Generator().manual_seed(seed)
+    frames = torch.randint(0, 256, (F_, S_, S_, 3), dtype=torch.uint8, generator=gen)
+    quads = np.empty((F_, 4, 2), np.float64)
+    for f in range(F_):
+        c = np.array([S_ * (0.15 if f == 0 else 0.5) + 3.0 * f, S_ * 0.5 + 2.0 * f])
+        th = 0.05 * (f + 1)
+        x = S_ / 4.0 * np.array([np.cos(th), np.sin(th)])
+        y = np.flipud(x) * [-1, 1]
+        quads[f] = np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    r = torch.hypot((ys - (H - 1) / 2) / (0.5 * H), (xs - (W - 1) / 2) / (0.5 * W))
+    labels = torch.stack([((r * 12).long() + f) % 19 for f in range(F_)]).to(torch.uint8)
+    return frames, quads, labels
+
+
 def run_synthetic(opt) -> dict:
     from ..ldm.models.diffusion.ddim_w_inv import DDIMSampler, HookPlan
     from ..ldm.models.diffusion.ddpm import LatentDiffusion
     from ..utils import synth
 
+    if getattr(opt, "intake", False) and not opt.with_vae:
+        raise SystemExit("--intake makes the pixels the VAE encodes: it needs --with_vae")
     dev = torch.device("cuda", 0)
     dt = torch.float16 if opt.compute_dtype == "fp16" else torch.bfloat16
     cfg = load_unet_config(opt.config)
@@ -251,6 +281,10 @@ def run_synthetic(opt) -> dict:
     os.makedirs(opt.Base_dir, exist_ok=True)
     results, t_all = [], time.time()
     paster, raft = None, None
+    intake = None
+    if getattr(opt, "intake", False):
+        from .intake import FrameIntake
+        intake = FrameIntake(H=opt.H, W=opt.W, latent=(h, w), device=dev)
     nbatches = opt.n_frames // F_       # DataLoader(batch_size=n_samples, drop_last=True) (:376-382)
     # --pipeline_inversion: the DDIM inversion of batch k + 1 runs beside the sampling of batch k (DDIMSampler.sample_while_inverting:
     # the batches are independent, :413, :529-553); batch 0's inversion runs alone, the last batch's sampling too
@@ -268,15 +302,24 @@ def run_synthetic(opt) -> dict:
         d = lambda t: t.to(dev)
         stages = {}
         c, uc, tc = (d(synth.synth_normal(tag(k), (F_, 1, 768))) for k in ("c", "uc", "tc"))
-        img = None
-        if opt.with_vae:
+        img, frames, inv_tf = None, None, None
+        if intake is not None:
+            frames, quads, labels = synthetic_intake_inputs(F_, opt.frame_size, opt.H, opt.W, opt.seed + 1000 + batch_id)
+            frames, labels = d(frames), d(labels)
+            ts_ = stage(stages, "_", time.time())
+            img, inpaint_image, _, mask, inv_tf = intake(frames, quads, labels, REMOVE_MASK_TAR_FFHQ)
+            ts_ = stage(stages, "intake", ts_)
+            z_inp = model.get_first_stage_encoding(model.encode_first_stage(inpaint_image)).detach()     # :456-457
+            stage(stages, "vae_encode", ts_)
+        elif opt.with_vae:
             img = d(torch.stack([synth.synth_normal(tag(f"img{f}"), (3, opt.H, opt.W)).clamp(-1, 1) for f in range(F_)]))
             ts_ = stage(stages, "_", time.time())
             z_inp = model.get_first_stage_encoding(model.encode_first_stage(img)).detach()       # :456-457
             stage(stages, "vae_encode", ts_)
         else:
             z_inp = d(synth.synth_normal(tag("inp"), (F_, opt.C, h, w)) * 0.18215)
-        mask = d(synth.synth_mask(F_, h, w))
+        if intake is None:
+            mask = d(synth.synth_mask(F_, h, w))
         if opt.raft_flow:     # :550-553 flow = return_flow(target frames), pixel resolution
             from . import temporal_flow as tflow
             if raft is None:
@@ -311,7 +354,7 @@ def run_synthetic(opt) -> dict:
                              unconditional_guidance_scale=opt.scale, unconditional_conditioning=None,
                              inverse_dir=inv_store, batch_size=F_, test_model_kwargs=kw2, max_steps=opt.max_steps)
         return {"id": batch_id, "c": c, "uc": uc, "tc": tc, "z_inp": z_inp, "mask": mask, "flow": flow, "inv_store": inv_store,
-                "invert_kw": invert_kw, "inverted": invert_kw is None, "stages": stages}
+                "invert_kw": invert_kw, "inverted": invert_kw is None, "stages": stages, "frames": frames, "inv_transforms": inv_tf}
 
     def sample_kwargs(b):
         # :541 start code = the cached latent of the second-highest timestep ("ddim_latents_961.pt" at 50 steps)
@@ -369,12 +412,16 @@ def run_synthetic(opt) -> dict:
                 # (--precision autocast, the reference's default: its decoded tensor is float16 and :597-608 quantise in float16)
                 paster = PasteBack(H=opt.H, W=opt.W, device=dev, encode_decode=PasteBack.vae_round_trip(model),
                                    half_arithmetic=opt.precision == "autocast")
-            S_ = opt.frame_size
-            gen = torch.Generator().manual_seed(opt.seed + 1000 + batch_id)
-            frames = torch.randint(0, 256, (F_, S_, S_, 3), dtype=torch.uint8, generator=gen).to(dev)
-            # inv_transforms_all rows (:625): here the 1024 canvas lands on the central half of the frame, slightly sheared
-            q = S_ / 4.0
-            co = [_quad_coeffs(paster.canvas, [(q + 3 * f, q), (3 * q, q + f), (3 * q - f, 3 * q), (q, 3 * q - 2 * f)]) for f in range(F_)]
+            if intake is not None:      # the frames the crops were cut from and the inverse of that cut (:68-71, :625)
+                frames, co = cur["frames"], cur["inv_transforms"]
+            else:
+                S_ = opt.frame_size
+                gen = torch.Generator().manual_seed(opt.seed + 1000 + batch_id)
+                frames = torch.randint(0, 256, (F_, S_, S_, 3), dtype=torch.uint8, generator=gen).to(dev)
+                # inv_transforms_all rows (:625): here the 1024 canvas lands on the central half of the frame, slightly sheared
+                q = S_ / 4.0
+                co = [_quad_coeffs(paster.canvas, [(q + 3 * f, q), (3 * q, q + f), (3 * q - f, 3 * q), (q, 3 * q - 2 * f)])
+                      for f in range(F_)]
             torch.cuda.synchronize()
             t1 = time.time()
             pasted = paster.paste(x_samples, frames, co)                                           # :603-633

@@ -20,7 +20,6 @@ every call raises.
 """
 from __future__ import annotations
 
-import math
 from typing import Callable, Dict, Optional, Tuple
 
 import numpy as np
@@ -28,37 +27,7 @@ import torch
 
 from .. import hip
 
-PRECISION_BITS = 32 - 8 - 2      # Pillow Resample.c: 8-bit samples, 2 guard bits -> 22 fractional bits
-
-
-def resample_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Tap tables of ``Image.resize(.., Image.BILINEAR)`` from ``in_size`` to ``out_size`` samples: ``bounds`` int32
-    [out_size, 2] = (first input sample, taps) and ``kk`` int32 [out_size, ksize] = 22-bit fixed-point weights, as Pillow's
-    ``precompute_coeffs`` (triangle filter, support = max(scale, 1), window centred on (o + 0.5) * scale, weights normalised to
-    sum 1 in double) and ``normalize_coeffs_8bpc`` (round half away from zero) produce them."""
-    if in_size <= 0 or out_size <= 0:
-        raise ValueError("resample_coeffs: sizes must be positive")
-    scale = in_size / out_size
-    filterscale = max(scale, 1.0)
-    support = filterscale            # bilinear: filter support 1.0
-    ksize = int(math.ceil(support)) * 2 + 1
-    inv = 1.0 / filterscale
-    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
-    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
-    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size) - xmin
-    w = np.zeros((out_size, ksize), np.float64)
-    total = np.zeros(out_size, np.float64)
-    for x in range(ksize):           # sequential accumulation, tap by tap, as the C loop sums it
-        a = np.abs((x + xmin - center + 0.5) * inv)
-        col = np.where((x < xmax) & (a < 1.0), 1.0 - a, 0.0)
-        w[:, x] = col
-        total = total + col
-    nz = total != 0.0
-    w[nz] = w[nz] / total[nz, None]
-    w[np.arange(ksize)[None, :] >= xmax[:, None]] = 0.0
-    fixed = w * float(1 << PRECISION_BITS)
-    kk = np.where(w < 0, np.trunc(-0.5 + fixed), np.trunc(0.5 + fixed)).astype(np.int32)
-    return np.stack([xmin, xmax], 1).astype(np.int32), kk
+from .resample import PRECISION_BITS, resample_coeffs  # noqa: F401  (the tables this module has always exported)
 
 
 class PasteBack:
