@@ -327,6 +327,44 @@ int vface_quad_crop(const uint8_t* frames, int W, int H, uint8_t* out, int out_s
 int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, const uint8_t* member, int W, int H, float* image,
                           float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH, int nframes, void* stream);
 
+/* ---- face parsing: aligned crop -> label map (BiSeNet over ResNet-18) ---------------------------------------------------------
+ * The reference runs `faceParsing_demo` -> `FaceParser.forward` -> `BiSeNet` (REFace/pretrained/face_parsing/{face_parsing_demo,
+ * model,resnet}.py; scripts/VFace_inference_batch.py:251, 292-294) one frame at a time in fp32.  Its convolutions are vface_conv3x3 /
+ * vface_im2col + vface_gemm with eval-mode BatchNorm folded in on the host, its ReLUs vface_channel_norm_act and its global average
+ * pools the means of vface_channel_stats (vface_amd/parsing.py); these entry points are the rest.  All: raw device pointers, no
+ * allocation, no synchronisation, capturable; a refusal launches nothing; no atomics (bits do not depend on the batch).
+ *
+ * vface_parse_prefilter: `FaceParser.preprocess_img` with `BicubicDownSample(factor=2)` (face_parsing_demo.py:124-193, 260-264).
+ *   crops [nframes][H2][W2][3] uint8 -> out [nframes * H2/2 * W2/2][ldo] 16-bit, 8 channels written per pixel (3 values, 5 zeros):
+ *   u8 / 255; the 8-tap separable filter k[i] = bicubic((i - 4 + 0.5) / 2), a = -0.5, normalised to sum 1 -- vertical pass, then
+ *   horizontal, `reflect` padding 3 + 3, stride 2; clamp(0, 1); (x - seg_mean) / seg_std (model.py:15-16).  fp32 throughout, one
+ *   rounding.  factor must be 2 and H2, W2 even and >= 8 (VFACE_ERR_SHAPE otherwise). */
+int vface_parse_prefilter(const uint8_t* crops, int W2, int H2, int factor, void* out, int64_t ldo, int nframes, int dtype,
+                          void* stream);
+
+/* vface_maxpool3x3s2: nn.MaxPool2d(3, stride 2, padding 1) (resnet.py:64) on NHWC 16-bit rows; padding is -inf.
+ *   x [nimg * H * W][ldx] -> y [nimg * OH * OW][ldy], OH = (H - 1) / 2 + 1, OW likewise; C % 8 == 0. */
+int vface_maxpool3x3s2(const void* x, int64_t ldx, int nimg, int H, int W, int C, void* y, int64_t ldy, int dtype, void* stream);
+
+/* vface_channel_gate: y[m][c] = x[m][c] * g[m / hw][c] + r (one fp32 fma, one rounding to 16 bits); g fp32 [nimg][ldg].  r is at
+ *   most one of: rvec fp32 [nimg][ldrv] (model.py:122: `feat32_arm + avg_up`, the nearest upsample of a 1 x 1 map), rten 16-bit
+ *   [M][ldr] (:127), add_x != 0 for x itself (:214-215); none: the plain gate (:88).  y may be x.  M % hw == 0, C % 8 == 0. */
+int vface_channel_gate(const void* x, int64_t ldx, const float* g, int64_t ldg, const float* rvec, int64_t ldrv, const void* rten,
+                       int64_t ldr, int add_x, void* y, int64_t ldy, int64_t M, int hw, int C, int dtype, void* stream);
+
+/* vface_pooled_linear: the 1 x 1 convolutions on globally pooled vectors (model.py:85-87, :118, :210-213), fp32:
+ *   out[n][o] = act(sum_k W[o][k] * a[n * lda + k * sa] + bias[o]), W fp32 [N][K] (BatchNorm folded in), bias may be NULL,
+ *   act 0 none | 1 ReLU | 3 sigmoid (vface_channel_norm_act's codes).  sa = 2 reads the means where vface_channel_stats left them. */
+int vface_pooled_linear(const float* a, int64_t lda, int sa, const float* W, const float* bias, float* out, int64_t ldo, int nimg,
+                        int N, int K, int act, void* stream);
+
+/* vface_upsample_argmax_u8: `F.interpolate(.., (H, W), 'bilinear', align_corners=True)` (model.py:258) + `torch.argmax(dim=1)`
+ *   (face_parsing_demo.py:278) + a byte table (the 12-class map of :74-122, or the identity) in one pass: the full-resolution logit
+ *   planes never exist.  logits fp32 [nframes * h * w][ld], columns 0 .. ncls - 1 compared (ncls <= 32 <= table entries; columns
+ *   ncls .. ld - 1 may hold anything); out [nframes][H][W] uint8 = table[first maximal class].  ld % 4 == 0. */
+int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h, int w, int ncls, const uint8_t* table,
+                             uint8_t* out, int H, int W, void* stream);
+
 /* The hooked self-attention as one call (pnp_utils.py:94-287, the closure installed on attn1):
  *   x [B][n][d] (already LayerNorm'd), B = chunks * F laid out [uncond ; cond ; recon]
  *   Wqkv [3d][d]  = rows of to_q | to_k | to_v

@@ -2,8 +2,9 @@
 """Timings of the widened rows at the sizes the 8-frame / 16-frame workloads use, HIP events on the launch
 stream: the RAFT-shaped flow producer (F - 1 pairs of 512 x 512 frames, 20 updates), the paste-back (F decoded 512 x 512
 crops -> 1024 canvas -> 1024 x 1024 frames) and the frame intake (F frames of 1080 x 1920 -> 1024 x 1024 aligned crops -> 512 x 512
-sampler tensors), each next to the same Pillow calls on the host.
-usage: python tools/bench_widening.py [--frames 8] [--only intake]"""
+sampler tensors), each next to the same Pillow calls on the host, and the face parser (F aligned 1024 x 1024 crops -> 512 x 512 label
+maps) launch by launch.
+usage: python tools/bench_widening.py [--frames 8] [--only intake | parse]"""
 import argparse
 import os
 import statistics
@@ -37,11 +38,13 @@ def main():
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--frame_size", type=int, default=1024)
-    ap.add_argument("--only", choices=["intake"], default=None, help="time this row alone")
+    ap.add_argument("--only", choices=["intake", "parse"], default=None, help="time this row alone")
     a = ap.parse_args()
     F_, R, S = a.frames, a.res, a.frame_size
     if a.only == "intake":
         return bench_intake(F_, R)
+    if a.only == "parse":
+        return bench_parse(F_)
     from vface_amd.raft import RAFT
     from vface_amd.scripts import temporal_flow as tflow
     from vface_amd.scripts.paste_back import PasteBack
@@ -85,6 +88,66 @@ def main():
     print(f"the same three Pillow calls on the host (no VAE, no PCIe): {(time.time() - t0) / 3 * 1e3:8.1f} ms per frame", flush=True)
 
     bench_intake(F_, R)
+    bench_parse(F_)
+
+
+def bench_parse(F_, size=1024):
+    """The face parser (vface_amd/parsing.py) on F aligned crops of size x size: every launch of one ``FaceParser.labels`` call with
+    its own HIP-event time and the HBM bytes it has to move (compulsory traffic: operands once, result once), then the call as a
+    whole.  The per-launch times are taken in one pass with an event pair round each launch; the whole call is timed without them."""
+    from vface_amd import hip
+    from vface_amd.pretrained.face_parsing import FaceParser
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+    import cases_parse as cp
+    crops = torch.from_numpy(np.stack([cp.crop(size // 2, size // 2, 50 + f) for f in range(F_)])).to(DEV)
+    fp = FaceParser(seg_ckpt=None, size=size, device=DEV)
+    fp.labels(crops)
+    torch.cuda.synchronize()
+
+    def out_rows(n, H, W, st, up):
+        vh, vw = (2 * H, 2 * W) if up else (H, W)
+        return n * ((vh - 1) // st + 1) * ((vw - 1) // st + 1)
+    nbytes = {
+        "parse_prefilter": lambda a, k: a[0].numel() + a[1].shape[0] * 16,
+        "im2col": lambda a, k: k["nimg"] * k["H"] * k["W"] * k["C_"] * 2 + a[1].numel() * 2,
+        "gemm": lambda a, k: (k["M"] * k["K"] + k["N"] * k["K"]) * 2 + k["M"] * k["N"] * a[2].element_size(),
+        "conv3x3": lambda a, k: (k["nimg"] * k["H"] * k["W"] * k["cin"] + 9 * k["cin"] * k["cout"]) * 2
+        + out_rows(k["nimg"], k["H"], k["W"], k.get("stride", 1), k.get("upsample", False)) * k["cout"] * 2,
+        "channel_norm_act": lambda a, k: k["M"] * k["C_"] * 2 * (2 + (k.get("residual") is not None)),
+        "channel_stats": lambda a, k: k["nimg"] * k["hw"] * k["C_"] * 2 + k["nimg"] * k["C_"] * 8,
+        "pooled_linear": lambda a, k: k["N"] * k["K"] * 4 + k["nimg"] * (k["K"] + k["N"]) * 4,
+        "channel_gate": lambda a, k: k["M"] * k["C_"] * 2 * (2 + (k.get("rten") is not None)),
+        "maxpool3x3s2": lambda a, k: k["nimg"] * k["H"] * k["W"] * k["C_"] * 2 + a[1].shape[0] * k["C_"] * 2,
+        "upsample_argmax_u8": lambda a, k: a[0].numel() * 4 + k["F"] * k["H"] * k["W"],
+    }
+    rows, saved = [], {}
+    for name, fb in nbytes.items():
+        saved[name] = getattr(hip, name)
+
+        def wrapped(*a, _name=name, _fb=fb, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            r = saved[_name](*a, **k)
+            e1.record()
+            shape = "x".join(str(k[key]) for key in ("nimg", "F", "M", "H", "W", "hw", "cin", "C_", "K", "cout", "N") if key in k)
+            rows.append((_name, shape, e0, e1, _fb(a, k)))
+            return r
+        setattr(hip, name, wrapped)
+    try:
+        fp.labels(crops)
+        torch.cuda.synchronize()
+    finally:
+        for name, fn in saved.items():
+            setattr(hip, name, fn)
+    print(f"face parser: {F_} crops {size}x{size} -> {size // 2}x{size // 2} label maps, {len(rows)} launches (one pass, an event pair each)", flush=True)
+    total, tbytes = 0.0, 0
+    for name, shape, e0, e1, nb in rows:
+        t = e0.elapsed_time(e1)
+        total, tbytes = total + t, tbytes + nb
+        print(f"   {name:20s} {shape:28s} {t * 1e3:8.1f} us  {nb / 1e6:8.2f} MB  {nb / max(t, 1e-6) / 1e6:7.1f} GB/s", flush=True)
+    print(f"   sum of the launches {total:8.2f} ms  {tbytes / 1e6:8.1f} MB  ({total / F_:6.2f} ms per frame)", flush=True)
+    t = time_ms(lambda: fp.labels(crops))
+    print(f"   FaceParser.labels as one call (median of 5, allocations included): {t:8.2f} ms  ({t / F_:6.2f} ms per frame)", flush=True)
 
 
 def bench_intake(F_, R, image_size=1024, Hs=1080, Ws=1920):

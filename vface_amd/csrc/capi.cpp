@@ -277,6 +277,30 @@ int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, const uint8
                                      S(stream));
 }
 
+int vface_parse_prefilter(const uint8_t* crops, int W2, int H2, int factor, void* out, int64_t ldo, int nframes, int dtype,
+                          void* stream) {
+    return vf_launch_parse_prefilter(crops, W2, H2, factor, out, ldo, nframes, dtype, S(stream));
+}
+
+int vface_maxpool3x3s2(const void* x, int64_t ldx, int nimg, int H, int W, int C, void* y, int64_t ldy, int dtype, void* stream) {
+    return vf_launch_maxpool3x3s2(x, ldx, nimg, H, W, C, y, ldy, dtype, S(stream));
+}
+
+int vface_channel_gate(const void* x, int64_t ldx, const float* g, int64_t ldg, const float* rvec, int64_t ldrv, const void* rten,
+                       int64_t ldr, int add_x, void* y, int64_t ldy, int64_t M, int hw, int C, int dtype, void* stream) {
+    return vf_launch_channel_gate(x, ldx, g, ldg, rvec, ldrv, rten, ldr, add_x, y, ldy, M, hw, C, dtype, S(stream));
+}
+
+int vface_pooled_linear(const float* a, int64_t lda, int sa, const float* W, const float* bias, float* out, int64_t ldo, int nimg,
+                        int N, int K, int act, void* stream) {
+    return vf_launch_pooled_linear(a, lda, sa, W, bias, out, ldo, nimg, N, K, act, S(stream));
+}
+
+int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h, int w, int ncls, const uint8_t* table,
+                             uint8_t* out, int H, int W, void* stream) {
+    return vf_launch_upsample_argmax_u8(logits, ld, nframes, h, w, ncls, table, out, H, W, S(stream));
+}
+
 size_t vface_attn1_workspace_bytes(int B, int n, int d, int chunks) {
     if (B <= 0 || n <= 0 || d <= 0 || chunks <= 0) return 0;
     const size_t F = (size_t)B / chunks;

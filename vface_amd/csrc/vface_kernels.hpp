@@ -229,6 +229,16 @@ int vf_launch_quad_crop(const unsigned char* frames, int Ws, int Hs, unsigned ch
 int vf_launch_dataset_tensors(const unsigned char* crop, const unsigned char* label, const unsigned char* member, int W, int H,
                               float* image, float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH,
                               int nframes, hipStream_t stream);
+// parsing.hip: glue of the face-parsing network (pretrained/face_parsing/{face_parsing_demo,model,resnet}.py)
+int vf_launch_parse_prefilter(const unsigned char* crops, int W2, int H2, int factor, void* out, long ldo, int nframes, int dtype,
+                              hipStream_t stream);
+int vf_launch_maxpool3x3s2(const void* x, long ldx, int nimg, int H, int W, int C, void* y, long ldy, int dtype, hipStream_t stream);
+int vf_launch_channel_gate(const void* x, long ldx, const float* g, long ldg, const float* rvec, long ldrv, const void* rten, long ldr,
+                           int add_x, void* y, long ldy, long M, int hw, int C, int dtype, hipStream_t stream);
+int vf_launch_pooled_linear(const float* a, long lda, int sa, const float* W, const float* bias, float* out, long ldo, int nimg, int N,
+                            int K, int act, hipStream_t stream);
+int vf_launch_upsample_argmax_u8(const float* logits, long ld, int nframes, int h, int w, int ncls, const unsigned char* table,
+                                 unsigned char* out, int H, int W, hipStream_t stream);
 int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, int dtype, hipStream_t stream);
 int vf_launch_silu(const void* x, void* y, long count, int in_f32, int dtype, hipStream_t stream);
 int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, int N, float scale, int dtype, hipStream_t stream);

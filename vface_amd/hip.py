@@ -84,6 +84,11 @@ SIGNATURES = {
     "vface_frame_normalise_resize": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vface_parse_prefilter": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
+    "vface_maxpool3x3s2": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
+    "vface_channel_gate": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "vface_pooled_linear": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "vface_upsample_argmax_u8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
     "vface_attn1_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "vface_attn1_forward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32,
                                       _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp,
@@ -563,6 +568,71 @@ def dataset_tensors(crop: torch.Tensor, label: torch.Tensor, member: torch.Tenso
                                       _stream())
     _check(rc, "vface_dataset_tensors")
     return image, inpaint, mask, mlat
+
+
+# ---- glue of the face-parsing network (csrc/parsing.hip; include/vface_hip.h "face parsing") ----
+def parse_prefilter(crops: torch.Tensor, out: torch.Tensor, factor: int = 2):
+    """uint8 crops [F, 2h, 2w, 3] -> ``out`` 16-bit [F*h*w, 8] (3 normalised channels, 5 zeros): ``FaceParser.preprocess_img``."""
+    if crops.dtype != torch.uint8 or crops.dim() != 4 or crops.shape[3] != 3 or not crops.is_contiguous():
+        raise VFaceHipError("parse_prefilter: crops must be contiguous uint8 [F, H, W, 3]")
+    F_, H2, W2, _ = crops.shape
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[1] < 8 or out.shape[0] != F_ * (H2 // 2) * (W2 // 2):
+        raise VFaceHipError(f"parse_prefilter: out must be a 16-bit [F*h*w, >= 8] view; got {tuple(out.shape)}")
+    rc = load().vface_parse_prefilter(_p(crops), W2, H2, factor, _p(out), out.stride(0), F_, dtype_code(out.dtype), _stream())
+    _check(rc, "vface_parse_prefilter")
+
+
+def maxpool3x3s2(x: torch.Tensor, y: torch.Tensor, *, nimg: int, H: int, W: int, C_: int, ldx: Optional[int] = None,
+                 ldy: Optional[int] = None):
+    rc = load().vface_maxpool3x3s2(_p(x), ldx if ldx is not None else x.stride(0), nimg, H, W, C_, _p(y),
+                                   ldy if ldy is not None else y.stride(0), dtype_code(x.dtype), _stream())
+    _check(rc, "vface_maxpool3x3s2")
+
+
+def channel_gate(x: torch.Tensor, g: torch.Tensor, y: torch.Tensor, *, M: int, hw: int, C_: int, rvec=None, rten=None,
+                 add_x: bool = False, ldx: Optional[int] = None, ldy: Optional[int] = None, ldr: Optional[int] = None):
+    """``y = x * g[image] + r`` with ``r`` one of nothing, ``rvec`` (fp32 per image), ``rten`` (16-bit tensor), ``x`` itself."""
+    for t in (g, rvec):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1):
+            raise VFaceHipError("channel_gate: g and rvec are 2-D fp32 views [nimg, C] with unit column stride")
+    rc = load().vface_channel_gate(_p(x), ldx if ldx is not None else x.stride(0), _p(g), g.stride(0), _p(rvec),
+                                   rvec.stride(0) if rvec is not None else 0, _p(rten),
+                                   (ldr if ldr is not None else rten.stride(0)) if rten is not None else 0, int(add_x), _p(y),
+                                   ldy if ldy is not None else y.stride(0), M, hw, C_, dtype_code(x.dtype), _stream())
+    _check(rc, "vface_channel_gate")
+
+
+def pooled_linear(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, *, nimg: int, N: int, K: int,
+                  lda: int, sa: int = 1, act: int = 0):
+    """``out[n, :N] = act(w[:N, :K] @ a[n] + bias)`` in fp32; ``a`` element (n, k) at ``a.data_ptr + 4 * (n * lda + k * sa)``."""
+    for t in (a, w, bias, out):
+        if t is not None and t.dtype != torch.float32:
+            raise VFaceHipError("pooled_linear: every operand is fp32")
+    if not w.is_contiguous() or tuple(w.shape) != (N, K) or (bias is not None and bias.numel() != N):
+        raise VFaceHipError("pooled_linear: w must be contiguous [N, K] and bias [N]")
+    if a.numel() < (nimg - 1) * lda + (K - 1) * sa + 1 or out.dim() != 2 or out.shape[0] < nimg:
+        raise VFaceHipError("pooled_linear: a / out are too small for nimg rows")
+    rc = load().vface_pooled_linear(_p(a), lda, sa, _p(w), _p(bias), _p(out), out.stride(0), nimg, N, K, act, _stream())
+    _check(rc, "vface_pooled_linear")
+
+
+def upsample_argmax_u8(logits: torch.Tensor, table: torch.Tensor, *, F: int, h: int, w: int, ncls: int, H: int, W: int,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 logits [F*h*w, ld] -> uint8 [F, H, W] = table[argmax over the first ``ncls`` columns of the bilinear
+    (align_corners) upsampling]; ``table``: uint8 [32] on the device."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[0] != F * h * w:
+        raise VFaceHipError(f"upsample_argmax_u8: logits must be an fp32 [F*h*w, ld] view; got {tuple(logits.shape)}")
+    if table.dtype != torch.uint8 or tuple(table.shape) != (32,) or not table.is_contiguous():
+        raise VFaceHipError("upsample_argmax_u8: table must be uint8 [32]")
+    if logits.shape[1] < ncls:
+        raise VFaceHipError("upsample_argmax_u8: fewer logit columns than classes")
+    if out is None:
+        out = torch.empty(F, H, W, dtype=torch.uint8, device=logits.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, H, W) or not out.is_contiguous():
+        raise VFaceHipError("upsample_argmax_u8: out must be contiguous uint8 [F, H, W]")
+    rc = load().vface_upsample_argmax_u8(_p(logits), logits.stride(0), F, h, w, ncls, _p(table), _p(out), H, W, _stream())
+    _check(rc, "vface_upsample_argmax_u8")
+    return out
 
 
 def attn1_workspace_bytes(B: int, n: int, d: int, chunks: int) -> int:

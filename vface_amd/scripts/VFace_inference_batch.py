@@ -72,6 +72,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "aligned crops, the images, inpaint images and the latent mask on the GPU -- crop_faces_by_quads "
                         "(alignmengt.py:255-263), VideoDataset.__getitem_gray__ (video_swap_dataset.py:135-240) and :459 "
                         "(scripts/intake.py); with --paste_back the same frames and their inv_transforms (:68-71) are pasted into")
+    p.add_argument("--parse", action="store_true",
+                   help="with --intake: the label maps come from the face parser on the GPU -- faceParsing_demo on the aligned "
+                        "crops (:251, :292-294; pretrained/face_parsing, vface_amd/parsing.py) -- instead of synthetic rings; needs "
+                        "--H 512 --W 512, the size of the reference's map (video_swap_dataset.py:139)")
+    p.add_argument("--faceParsing_ckpt", type=str, default=None,
+                   help="face-parsing state dict (Other_dependencies/face_parsing/79999_iter.pth); default synthetic weights")
+    p.add_argument("--faceParser_name", type=str, default="default", help="default (BiSeNet) | segnext (mmseg: not built)")
+    p.add_argument("--seg12", default=True, action="store_true", help="12-class label maps (the reference's default)")
     p.add_argument("--with_vae", action="store_true",
                    help="synthetic run through the first-stage KL-VAE too: the inpaint latents come from encode_first_stage of "
                         "synthetic images (:456-457) and the samples are decoded to pixels (:596-600)")
@@ -244,6 +252,20 @@ def synthetic_intake_inputs(F_: int, S_: int, H: int, W: int, seed: int):
     return frames, quads, labels
 
 
+def check_parse_options(opt):
+    """--parse feeds the intake, and the map it makes is the parser's 512 x 512 one, which the intake takes at the sampler's size."""
+    if not getattr(opt, "parse", False):
+        return
+    if not getattr(opt, "intake", False):
+        raise SystemExit("--parse makes the label maps the intake reads: it needs --intake")
+    if (opt.H, opt.W) != (512, 512):
+        raise SystemExit(f"--parse needs --H 512 --W 512: the parser's label map is 512 x 512 by construction; got {opt.H} x {opt.W}")
+    if opt.faceParser_name == "segnext":
+        raise NotImplementedError("--faceParser_name segnext is mmseg's parser (third party); only the default BiSeNet parser is built")
+    if opt.faceParser_name != "default":
+        raise SystemExit(f"--faceParser_name: default | segnext; got {opt.faceParser_name!r}")
+
+
 def run_synthetic(opt) -> dict:
     from ..ldm.models.diffusion.ddim_w_inv import DDIMSampler, HookPlan
     from ..ldm.models.diffusion.ddpm import LatentDiffusion
@@ -251,6 +273,7 @@ def run_synthetic(opt) -> dict:
 
     if getattr(opt, "intake", False) and not opt.with_vae:
         raise SystemExit("--intake makes the pixels the VAE encodes: it needs --with_vae")
+    check_parse_options(opt)
     dev = torch.device("cuda", 0)
     dt = torch.float16 if opt.compute_dtype == "fp16" else torch.bfloat16
     cfg = load_unet_config(opt.config)
@@ -285,6 +308,11 @@ def run_synthetic(opt) -> dict:
     if getattr(opt, "intake", False):
         from .intake import FrameIntake
         intake = FrameIntake(H=opt.H, W=opt.W, latent=(h, w), device=dev)
+    parser = None
+    if getattr(opt, "parse", False):
+        from ..pretrained.face_parsing import FaceParser
+        parser = FaceParser(seg_ckpt=opt.faceParsing_ckpt, size=1024, device=dev, dtype=dt)
+        parser.seg.engine      # fold and upload the weights now, not inside the first batch's `parse` stage
     nbatches = opt.n_frames // F_       # DataLoader(batch_size=n_samples, drop_last=True) (:376-382)
     # --pipeline_inversion: the DDIM inversion of batch k + 1 runs beside the sampling of batch k (DDIMSampler.sample_while_inverting:
     # the batches are independent, :413, :529-553); batch 0's inversion runs alone, the last batch's sampling too
@@ -302,12 +330,21 @@ def run_synthetic(opt) -> dict:
         d = lambda t: t.to(dev)
         stages = {}
         c, uc, tc = (d(synth.synth_normal(tag(k), (F_, 1, 768))) for k in ("c", "uc", "tc"))
-        img, frames, inv_tf = None, None, None
+        img, frames, inv_tf, labels = None, None, None, None
         if intake is not None:
             frames, quads, labels = synthetic_intake_inputs(F_, opt.frame_size, opt.H, opt.W, opt.seed + 1000 + batch_id)
             frames, labels = d(frames), d(labels)
             ts_ = stage(stages, "_", time.time())
-            img, inpaint_image, _, mask, inv_tf = intake(frames, quads, labels, REMOVE_MASK_TAR_FFHQ)
+            if parser is not None:      # :251, :292-294: the parser sees the aligned crop, the dataset reads its map
+                from .intake import inv_transforms
+                crops = intake.crop(frames, quads)
+                ts_ = stage(stages, "intake", ts_)
+                labels = parser.labels(crops, convert_to_seg12=opt.seg12)
+                ts_ = stage(stages, "parse", ts_)
+                img, inpaint_image, _, mask = intake.tensors(crops, labels, REMOVE_MASK_TAR_FFHQ)
+                inv_tf = inv_transforms(quads, intake.image_size)
+            else:
+                img, inpaint_image, _, mask, inv_tf = intake(frames, quads, labels, REMOVE_MASK_TAR_FFHQ)
             ts_ = stage(stages, "intake", ts_)
             z_inp = model.get_first_stage_encoding(model.encode_first_stage(inpaint_image)).detach()     # :456-457
             stage(stages, "vae_encode", ts_)
@@ -354,7 +391,8 @@ def run_synthetic(opt) -> dict:
                              unconditional_guidance_scale=opt.scale, unconditional_conditioning=None,
                              inverse_dir=inv_store, batch_size=F_, test_model_kwargs=kw2, max_steps=opt.max_steps)
         return {"id": batch_id, "c": c, "uc": uc, "tc": tc, "z_inp": z_inp, "mask": mask, "flow": flow, "inv_store": inv_store,
-                "invert_kw": invert_kw, "inverted": invert_kw is None, "stages": stages, "frames": frames, "inv_transforms": inv_tf}
+                "invert_kw": invert_kw, "inverted": invert_kw is None, "stages": stages, "frames": frames, "inv_transforms": inv_tf,
+                "labels": labels}
 
     def sample_kwargs(b):
         # :541 start code = the cached latent of the second-highest timestep ("ddim_latents_961.pt" at 50 steps)
@@ -439,6 +477,7 @@ def run_synthetic(opt) -> dict:
         torch.cuda.synchronize()
         results.append({"batch": batch_id, "frames": F_, "sample_seconds": dt_s, "batch_wall_seconds": time.time() - t_batch,
                         "samples": samples if getattr(opt, "return_samples", False) else None,
+                        "labels": cur["labels"] if getattr(opt, "return_samples", False) else None,
                         "finite": bool(torch.isfinite(samples).all()) and (pixels is None or bool(torch.isfinite(pixels).all())),
                         "pixels": None if pixels is None else list(pixels.shape),
                         "pasted": None if pasted is None else list(pasted.shape), "paste_seconds": paste_s,
@@ -459,6 +498,7 @@ def main(argv=None):
                  "conditioning and paste-back (VFace_inference_batch.py:193-528,603-670) need checkpoints "
                  "that are not available offline; run with --synthetic, or feed real latents through "
                  "vface_amd.ldm.models.diffusion.ddim_w_inv.DDIMSampler (see INTEGRATION.md).")
+    check_parse_options(opt)
     if not torch.cuda.is_available():
         sys.exit("An MI355X is required: the VFace hot path has no CPU fallback.")
     return run_synthetic(opt)

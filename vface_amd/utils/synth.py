@@ -84,3 +84,18 @@ def synth_mask(f: int, h: int, w: int) -> torch.Tensor:
     ys, xs = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
     m = (((ys - (h - 1) / 2) / (0.38 * h)) ** 2 + ((xs - (w - 1) / 2) / (0.30 * w)) ** 2 <= 1.0).astype(np.float32)
     return torch.from_numpy(m)[None, None].repeat(f, 1, 1, 1)
+
+
+@torch.no_grad()
+def fill_parser_(module: torch.nn.Module, seed: int = 0, prefix: str = "") -> torch.nn.Module:
+    """``fill_module_`` for the face-parsing network, with every ``*.running_mean`` shifted by -1.
+
+    The plain fill draws every vector as 1 +- 0.1, a BatchNorm's running mean included, while a convolution with zero-mean weights
+    has outputs centred on zero: each BatchNorm then subtracts about one standard deviation more than it should, the ReLUs that
+    follow cut almost everything, and after ResNet-18's seventeen of them the logits are exactly zero.  Centred running means
+    (0 +- 0.1) keep the network alive: logits of standard deviation about 1, several labels present."""
+    fill_module_(module, seed, prefix)
+    for k, v in module.state_dict().items():
+        if k.endswith("running_mean"):
+            v.sub_(1.0)
+    return module
