@@ -57,7 +57,7 @@ WINDOWS = [(7, 7, 2), (1, 5, 1), (5, 1, 1), (1, 1, 2), (3, 3, 1), (3, 3, 2)]
 @pytest.mark.parametrize("C", [8, 96, 328, 384])
 @pytest.mark.parametrize("kh,kw,stride", WINDOWS)
 def test_im2col(dt, kh, kw, stride, C):
-    """The window matrix of the engine's `_window` (pad = (k - 1) // 2) at an odd 13 x 11 map (the stride-2 output size rounds),
+    """The window matrix of the engines' `window` (pad = (k - 1) // 2) at an odd 13 x 11 map (the stride-2 output size rounds),
     three images, the input a column view of a wider buffer (ldx = C + 16) and the output rows 8 sentinel columns longer than
     kh kw C.  Zero padding is +0, as F.unfold's."""
     h = hip()
@@ -138,7 +138,7 @@ def test_copy2d_columns_of_a_wider_buffer(dt, rows, cols, wrap):
 @pytest.mark.parametrize("N,C,hw,cpad", [(3, 3, 13 * 11, 8), (2, 4, 77, 4), (1, 9, 5, 16), (2, 3, 512 * 512, 8)])
 def test_nchw_to_nhwc(dt, N, C, hw, cpad):
     """fp32 NCHW -> 16-bit tokens [N hw, cpad]: the value's own rounding (x.to(dt)), channels C .. cpad - 1 are +0, nothing past
-    the last row.  The last case is the engine's `_tokens8` of two 512 x 512 images: 4.19 M items, a wrap (cap 2.10 M)."""
+    the last row.  The last case is the engines' `tokens8` of two 512 x 512 images: 4.19 M items, a wrap (cap 2.10 M)."""
     h = hip()
     x = randn((N, C, hw), N * hw + C, 3.0)
     oh = sentinel(N * hw + 1, cpad, dt)

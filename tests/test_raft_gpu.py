@@ -40,7 +40,7 @@ def test_encoder_matches_oracle(sd, eng, enc):
     InstanceNorm (feature) or folded BatchNorm (context), 1x1 head: [N, 3, 96, 128] -> [N, 256, 12, 16]."""
     x = synth.synth_normal(f"raft.{enc}.x", (2, 3, 96, 128)).clamp(-1, 1)      # (the encoders alone accept any multiple of 8)
     ref = oraft.encoder(sd, enc, x)
-    got = _nchw(eng._encoder(enc, eng._tokens8(x.to(DEV)), 2, 96, 128), 2, 12, 16)
+    got = _nchw(eng._encoder(enc, eng.tokens8(x.to(DEV)), 2, 96, 128), 2, 12, 16)
     assert got.shape == ref.shape
     assert rel_l2(got, ref) < 3e-3          # 15 rounded fp16 layers
 

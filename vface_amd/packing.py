@@ -4,6 +4,7 @@ Everything here is a re-layout or an exact linear refactoring of the reference's
 computed in fp64 and handed to the device in the 16-bit compute type:
 
 * ``pack_conv3x3``   nn.Conv2d weight [Cout, Cin, 3, 3] -> [Cout, (ky, kx, Cin_pad)] for the implicit GEMM.
+* ``pack_conv_im2col`` any window -> [Cout, (tap, Cin_pad)], the row order of ``vface_im2col`` (convnet.py's explicit-window GEMMs).
 * ``pack_geglu``     GEGLU.proj rows (attention.py:40-44: first half value, second half gate) interleaved in
                      16-row blocks so the GEMM epilogue finds value and gate of a channel in the same lane.
 * ``pack_qkv``       to_q | to_k | to_v stacked into one [3d, d] matrix (one GEMM, attention.py:161,171-172).
@@ -42,6 +43,18 @@ def pack_conv_window(w: torch.Tensor, cin_pad: int | None = None) -> torch.Tenso
     taps[..., :cin] = w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
     if cp % 64 == 0:
         taps = taps.reshape(cout, kh * kw, cp // 64, 64).permute(0, 2, 1, 3)
+    return taps.reshape(cout, kh * kw * cp).contiguous()
+
+
+def pack_conv_im2col(w: torch.Tensor, cin_pad: int | None = None) -> torch.Tensor:
+    """[Cout, Cin, KH, KW] -> [Cout, KH*KW*Cin_pad] in K order (tap, channel), channels zero-padded (to a multiple of 8 by default):
+    the row order ``vface_im2col`` writes, so the plain GEMM of its window matrix with this is the convolution.  NOT
+    ``pack_conv_window``: that one puts 64-channel chunks first when Cin_pad % 64 == 0 (the implicit GEMM's order), which is another
+    order from two chunks (Cin_pad = 128) on."""
+    cout, cin, kh, kw = w.shape
+    cp = cin_pad if cin_pad is not None else (cin + 7) // 8 * 8
+    taps = torch.zeros(cout, kh * kw, cp, dtype=w.dtype)
+    taps[..., :cin] = w.permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
     return taps.reshape(cout, kh * kw * cp).contiguous()
 
 

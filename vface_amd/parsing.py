@@ -2,7 +2,7 @@
 
 ``REFace/scripts/VFace_inference_batch.py:251, 292-294`` calls ``faceParsing_demo`` -> ``FaceParser.forward`` -> ``BiSeNet`` over
 ``Resnet18`` (``pretrained/face_parsing/{face_parsing_demo,model,resnet}.py``) once per frame, in fp32, with a host round trip.
-``ParseEngine`` runs the same network for a whole batch of frames, after ``RaftEngine``:
+``ParseEngine`` runs the same network for a whole batch of frames, on ``convnet.ConvNetEngine`` as ``RaftEngine`` does:
 
   * eval-mode BatchNorm (eps 1e-5) is folded into every convolution on the host, in fp64 (all of them are bias-free, the ResNet's
     ``downsample.1`` and the gates' ``bn_atten`` included);
@@ -20,11 +20,12 @@ a frame's label map does not depend on which frames share its batch.  No CPU fal
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict
 
 import torch
 
-from . import hip, packing
+from . import hip
+from .convnet import ConvNetEngine, fold_bn      # (fold_bn: re-exported, the CPU restatement of the network folds with it)
 
 N_CLASSES = 19
 HEAD_COLS = 32                       # the class head's padded width = the byte table's length
@@ -48,99 +49,41 @@ def identity_table() -> torch.Tensor:
     return torch.arange(HEAD_COLS, dtype=torch.uint8)
 
 
-def fold_bn(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, var: torch.Tensor,
-            eps: float = BN_EPS) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``BatchNorm(eval)(conv(x, w))`` == ``conv(x, w') + b'``: (w', b') in fp64 (an exact refactoring in real arithmetic)."""
-    scale = gamma.double() / torch.sqrt(var.double() + eps)
-    return w.double() * scale.reshape(-1, *([1] * (w.dim() - 1))), beta.double() - mean.double() * scale
-
-
-class ParseEngine:
+class ParseEngine(ConvNetEngine):
     """Executes ``BiSeNet(n_classes=19)`` on device buffers.  ``sd``: its state dict (any float dtype, any device)."""
+    split_k = False      # a frame's labels must not depend on its batch (see ConvNetEngine.split_k)
 
     def __init__(self, sd: Dict[str, torch.Tensor], dtype: torch.dtype = torch.float16, device="cuda:0",
                  window_budget_bytes: int = 256 << 20):
-        hip.load()      # no CPU fallback: fail here if the library is missing
-        hip.dtype_code(dtype)
-        self.dtype, self.dev = dtype, torch.device(device)
+        super().__init__(dtype, device)
         self.window_budget = window_budget_bytes
-        sd = {k: v.detach().double().cpu() for k, v in sd.items() if torch.is_floating_point(v)}
-        self.P: Dict[str, dict] = {}
+        sd = {k: v.detach().double().cpu() for k, v in sd.items() if torch.is_floating_point(v)}      # BatchNorm is folded in fp64
         r = "cp.resnet"
-        self._add(sd, f"{r}.conv1", f"{r}.bn1", cin_pad=8)
+        self.add_conv(sd, f"{r}.conv1", f"{r}.bn1", cin_pad=8)
         for li in range(1, 5):
             for bi in (0, 1):
                 b = f"{r}.layer{li}.{bi}"
-                self._add(sd, f"{b}.conv1", f"{b}.bn1")
-                self._add(sd, f"{b}.conv2", f"{b}.bn2")
+                self.add_conv(sd, f"{b}.conv1", f"{b}.bn1")
+                self.add_conv(sd, f"{b}.conv2", f"{b}.bn2")
                 if f"{b}.downsample.0.weight" in sd:
-                    self._add(sd, f"{b}.downsample.0", f"{b}.downsample.1")
+                    self.add_conv(sd, f"{b}.downsample.0", f"{b}.downsample.1")
         for arm in ("cp.arm16", "cp.arm32"):
-            self._add(sd, f"{arm}.conv.conv", f"{arm}.conv.bn")
-            self._add(sd, f"{arm}.conv_atten", f"{arm}.bn_atten", pooled=True)
-        self._add(sd, "cp.conv_avg.conv", "cp.conv_avg.bn", pooled=True)
-        self._add(sd, "cp.conv_head32.conv", "cp.conv_head32.bn")
-        self._add(sd, "cp.conv_head16.conv", "cp.conv_head16.bn")
-        self._add(sd, "ffm.convblk.conv", "ffm.convblk.bn")
-        self._add(sd, "ffm.conv1", pooled=True)
-        self._add(sd, "ffm.conv2", pooled=True)
-        self._add(sd, "conv_out.conv.conv", "conv_out.conv.bn")
-        self._add(sd, "conv_out.conv_out", cout_pad=HEAD_COLS)
+            self.add_conv(sd, f"{arm}.conv.conv", f"{arm}.conv.bn")
+            self.add_conv(sd, f"{arm}.conv_atten", f"{arm}.bn_atten", pooled=True)
+        self.add_conv(sd, "cp.conv_avg.conv", "cp.conv_avg.bn", pooled=True)
+        self.add_conv(sd, "cp.conv_head32.conv", "cp.conv_head32.bn")
+        self.add_conv(sd, "cp.conv_head16.conv", "cp.conv_head16.bn")
+        self.add_conv(sd, "ffm.convblk.conv", "ffm.convblk.bn")
+        self.add_conv(sd, "ffm.conv1", pooled=True)
+        self.add_conv(sd, "ffm.conv2", pooled=True)
+        self.add_conv(sd, "conv_out.conv.conv", "conv_out.conv.bn")
+        self.add_conv(sd, "conv_out.conv_out", cout_pad=HEAD_COLS)
         self.n_classes = int(sd["conv_out.conv_out.weight"].shape[0])
         if self.n_classes > HEAD_COLS:
             raise hip.VFaceHipError(f"the class head holds at most {HEAD_COLS} classes; got {self.n_classes}")
         self.tables = {True: seg12_table().to(self.dev), False: identity_table().to(self.dev)}
 
-    # ---- weights --------------------------------------------------------------------------------------------------------
-    def _add(self, sd, name, bn: Optional[str] = None, cin_pad: Optional[int] = None, cout_pad: Optional[int] = None,
-             pooled: bool = False):
-        w = sd[name + ".weight"]
-        b = torch.zeros(w.shape[0], dtype=torch.float64)
-        if bn is not None:
-            w, b = fold_bn(w, sd[bn + ".weight"], sd[bn + ".bias"], sd[bn + ".running_mean"], sd[bn + ".running_var"])
-        cout, cin, kh, kw = w.shape
-        if pooled:      # a 1x1 convolution on a pooled vector: fp32 [N, K]
-            self.P[name] = {"w": w.reshape(cout, cin).float().contiguous().to(self.dev),
-                            "b": b.float().to(self.dev) if bn is not None else None, "cout": cout, "cin": cin}
-            return
-        if cout_pad is not None and cout_pad > cout:
-            w = torch.cat([w, torch.zeros(cout_pad - cout, cin, kh, kw, dtype=w.dtype)], 0)
-            b = torch.cat([b, torch.zeros(cout_pad - cout, dtype=b.dtype)])
-        w = w.float()
-        if (kh, kw) == (3, 3):
-            wp, kind = packing.pack_conv3x3(w, cin_pad), "conv3"
-        else:       # explicit window matrix / plain GEMM: K order (tap, channel), channels zero-padded
-            cp = cin_pad if cin_pad is not None else (cin + 7) // 8 * 8
-            t = torch.zeros(w.shape[0], kh * kw, cp)
-            t[..., :cin] = w.permute(0, 2, 3, 1).reshape(w.shape[0], kh * kw, cin)
-            wp, kind = t.reshape(w.shape[0], kh * kw * cp).contiguous(), "gemm"
-        self.P[name] = {"w": wp.to(self.dev, self.dtype), "b": b.float().to(self.dev) if bn is not None else None, "kh": kh, "kw": kw,
-                        "cout": w.shape[0], "cin": cin, "kind": kind}
-
     # ---- building blocks -------------------------------------------------------------------------------------------------
-    def _buf(self, rows, cols, dtype=None):
-        return torch.empty(rows, cols, dtype=dtype or self.dtype, device=self.dev)
-
-    def _conv3(self, name, x, out, *, nimg, H, W, ldx, stride=1, upsample=False):
-        p = self.P[name]
-        hip.conv3x3(x, p["w"], out, nimg=nimg, H=H, W=W, cin=p["cin"], cout=p["cout"], ldx=ldx, ldy=out.stride(0), stride=stride,
-                    upsample=upsample, bias=p["b"])
-
-    def _window(self, name, x, out, *, nimg, H, W, C_, ldx, stride=1, out32=False):
-        """kh x kw convolution, 'same' padding, through the explicit window matrix (a 1x1 stride-1 window needs none)."""
-        p = self.P[name]
-        kh, kw = p["kh"], p["kw"]
-        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-        M, K = nimg * OH * OW, kh * kw * C_
-        if kh == kw == 1 and stride == 1:
-            a, lda = x, ldx
-        else:
-            a = self._buf(M, K)
-            hip.im2col(x, a, nimg=nimg, H=H, W=W, C_=C_, kh=kh, kw=kw, stride=stride, pad_y=(kh - 1) // 2, pad_x=(kw - 1) // 2, ldx=ldx)
-            lda = K
-        hip.gemm(a, p["w"], out, M=M, N=p["cout"], K=K, lda=lda, ldc=out.stride(0), bias=p["b"],
-                 flags=hip.EPI_OUT_F32 if out32 else 0, split_k=False)
-
     def _relu(self, x, *, M, hw, C_, residual=None, y=None):
         hip.channel_norm_act(x, y if y is not None else x, M=M, hw=hw, C_=C_, act=hip.ACT_RELU, residual=residual)
 
@@ -158,22 +101,13 @@ class ParseEngine:
         """AttentionRefinementModule (model.py:82-89) and the add that follows it (:122 / :127), in place in its output."""
         hw, M = H * W, nimg * H * W
         feat = self._buf(M, 128)
-        self._conv3(f"{arm}.conv.conv", x, feat, nimg=nimg, H=H, W=W, ldx=cin)
+        self.conv3(f"{arm}.conv.conv", x, feat, nimg=nimg, H=H, W=W, ldx=cin)
         self._relu(feat, M=M, hw=hw, C_=128)
         g = self._pooled(f"{arm}.conv_atten", self._means(feat, nimg=nimg, hw=hw, C_=128), nimg=nimg, lda=256, sa=2, act=hip.ACT_SIGMOID)
         hip.channel_gate(feat, g, feat, M=M, hw=hw, C_=128, rvec=rvec, rten=rten)
         return feat
 
     # ---- the network -----------------------------------------------------------------------------------------------------
-    def tokens8(self, img: torch.Tensor) -> torch.Tensor:
-        """Normalised images [N, 3, H, W] (any float type) -> the 8-channel token rows the stem reads."""
-        if not img.is_cuda:
-            raise hip.VFaceHipError("the face parser runs on the GPU: images must be device tensors (no CPU fallback)")
-        N, C_, H, W = img.shape
-        out = self._buf(N * H * W, 8)
-        hip.nchw_to_nhwc(img.float().contiguous(), out, N=N, C_=C_, hw=H * W, cpad=8)
-        return out
-
     @staticmethod
     def check_size(H: int, W: int):
         if H % 32 or W % 32 or min(H, W) < 64:
@@ -196,8 +130,8 @@ class ParseEngine:
         step = max(1, min(F, self.window_budget // per_frame))
         for f0 in range(0, F, step):
             n = min(step, F - f0)
-            self._window(f"{r}.conv1", x8[f0 * H * W:(f0 + n) * H * W], x[f0 * h2 * w2:(f0 + n) * h2 * w2], nimg=n, H=H, W=W, C_=8, ldx=8,
-                         stride=2)
+            self.window(f"{r}.conv1", x8[f0 * H * W:(f0 + n) * H * W], x[f0 * h2 * w2:(f0 + n) * h2 * w2], nimg=n, H=H, W=W, C_=8, ldx=8,
+                        stride=2)
         self._relu(x, M=F * h2 * w2, hw=h2 * w2, C_=64)
         h, w = h2 // 2, w2 // 2
         t = self._buf(F * h * w, 64)
@@ -213,10 +147,10 @@ class ParseEngine:
                 oh, ow = (h - 1) // st + 1, (w - 1) // st + 1
                 M = F * oh * ow
                 t = self._buf(M, cout)
-                self._conv3(f"{b}.conv1", x, t, nimg=F, H=h, W=w, ldx=x.stride(0), stride=st)
+                self.conv3(f"{b}.conv1", x, t, nimg=F, H=h, W=w, ldx=x.stride(0), stride=st)
                 self._relu(t, M=M, hw=oh * ow, C_=cout)
                 t2 = self._buf(M, cout)
-                self._conv3(f"{b}.conv2", t, t2, nimg=F, H=oh, W=ow, ldx=cout)
+                self.conv3(f"{b}.conv2", t, t2, nimg=F, H=oh, W=ow, ldx=cout)
                 if li == 2 and bi == 1:      # feat8 is the left half of the fusion module's input [feat8 | feat_cp8]
                     cat = self._buf(M, 256)
                     y = cat[:, :128]
@@ -224,7 +158,7 @@ class ParseEngine:
                     y = t2
                 if f"{b}.downsample.0" in self.P:      # relu(bn(conv1x1 stride s (x)) + residual)
                     s = self._buf(M, cout)
-                    self._window(f"{b}.downsample.0", x, s, nimg=F, H=h, W=w, C_=c0, ldx=x.stride(0), stride=st)
+                    self.window(f"{b}.downsample.0", x, s, nimg=F, H=h, W=w, C_=c0, ldx=x.stride(0), stride=st)
                     self._relu(s, M=M, hw=oh * ow, C_=cout, residual=t2, y=y)
                 else:                                      # relu(x + residual)
                     self._relu(x, M=M, hw=oh * ow, C_=cout, residual=t2, y=y)
@@ -237,25 +171,25 @@ class ParseEngine:
         avg = self._pooled("cp.conv_avg.conv", self._means(f32_, nimg=F, hw=h32 * w32, C_=512), nimg=F, lda=1024, sa=2, act=hip.ACT_RELU)
         s32 = self._arm("cp.arm32", f32_, nimg=F, H=h32, W=w32, cin=512, rvec=avg)            # feat32_arm + avg_up
         up32 = self._buf(F * h16 * w16, 128)
-        self._conv3("cp.conv_head32.conv", s32, up32, nimg=F, H=h32, W=w32, ldx=128, upsample=True)
+        self.conv3("cp.conv_head32.conv", s32, up32, nimg=F, H=h32, W=w32, ldx=128, upsample=True)
         self._relu(up32, M=F * h16 * w16, hw=h16 * w16, C_=128)
         s16 = self._arm("cp.arm16", f16, nimg=F, H=h16, W=w16, cin=256, rten=up32)            # feat16_arm + feat32_up
         M8 = F * h8 * w8
-        self._conv3("cp.conv_head16.conv", s16, cat[:, 128:], nimg=F, H=h16, W=w16, ldx=128, upsample=True)
+        self.conv3("cp.conv_head16.conv", s16, cat[:, 128:], nimg=F, H=h16, W=w16, ldx=128, upsample=True)
         hip.channel_norm_act(cat[:, 128:], cat[:, 128:], M=M8, hw=h8 * w8, C_=128, act=hip.ACT_RELU, ldx=256, ldy=256)
         # feature fusion (:206-216): feat * atten + feat
         feat = self._buf(M8, 256)
-        self._window("ffm.convblk.conv", cat, feat, nimg=F, H=h8, W=w8, C_=256, ldx=256)
+        self.window("ffm.convblk.conv", cat, feat, nimg=F, H=h8, W=w8, C_=256, ldx=256)
         self._relu(feat, M=M8, hw=h8 * w8, C_=256)
         a1 = self._pooled("ffm.conv1", self._means(feat, nimg=F, hw=h8 * w8, C_=256), nimg=F, lda=512, sa=2, act=hip.ACT_RELU)
         a2 = self._pooled("ffm.conv2", a1, nimg=F, lda=64, sa=1, act=hip.ACT_SIGMOID)
         hip.channel_gate(feat, a2, feat, M=M8, hw=h8 * w8, C_=256, add_x=True)
         # head (:50-53): 3x3 + ReLU, then the 1x1 to the classes, fp32
         mid = self._buf(M8, 256)
-        self._conv3("conv_out.conv.conv", feat, mid, nimg=F, H=h8, W=w8, ldx=256)
+        self.conv3("conv_out.conv.conv", feat, mid, nimg=F, H=h8, W=w8, ldx=256)
         self._relu(mid, M=M8, hw=h8 * w8, C_=256)
         out = torch.empty(M8, HEAD_COLS, dtype=torch.float32, device=self.dev)
-        self._window("conv_out.conv_out", mid, out, nimg=F, H=h8, W=w8, C_=256, ldx=256, out32=True)
+        self.window("conv_out.conv_out", mid, out, nimg=F, H=h8, W=w8, C_=256, ldx=256, out32=True)
         return out
 
     @torch.no_grad()

@@ -9,6 +9,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
+from ...convnet import EngineOwner
 from .resnet import Resnet18
 
 SEG_MEAN = (0.485, 0.456, 0.406)      # model.py:15-16; the pre-filter kernel holds the same constants
@@ -56,7 +57,7 @@ class FeatureFusionModule(nn.Module):
         self.conv2 = nn.Conv2d(cout // 4, cout, kernel_size=1, bias=False)
 
 
-class BiSeNet(nn.Module):
+class BiSeNet(EngineOwner, nn.Module):
     def __init__(self, n_classes: int = 19, compute_dtype: torch.dtype = torch.float16):
         super().__init__()
         self.cp = ContextPath()
@@ -66,23 +67,11 @@ class BiSeNet(nn.Module):
         self.conv_out32 = BiSeNetOutput(128, 64, n_classes)
         self.n_classes = n_classes
         self.compute_dtype = compute_dtype
-        self._engine = None
         self.eval()
 
-    @property
-    def engine(self):
-        if self._engine is None:
-            from ...parsing import ParseEngine
-            self._engine = ParseEngine(self.state_dict(), self.compute_dtype, next(self.parameters()).device)
-        return self._engine
-
-    def load_state_dict(self, *a, **k):
-        self._engine = None
-        return super().load_state_dict(*a, **k)
-
-    def _apply(self, fn, *a, **k):
-        self._engine = None
-        return super()._apply(fn, *a, **k)
+    def _make_engine(self):
+        from ...parsing import ParseEngine
+        return ParseEngine(self.state_dict(), self.compute_dtype, next(self.parameters()).device)
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor, size: Optional[tuple] = None) -> torch.Tensor:
