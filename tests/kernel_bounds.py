@@ -1,8 +1,14 @@
-"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py): seeded 16-bit inputs, the
-unit in the last place of a 16-bit type, sentinel-filled buffers that show a store outside a kernel's slot, the element-wise bound
-check that names the worst element, and the attention kernel's fp64 reference with its per-element bound.  Plain functions, nothing
-collected by pytest."""
+"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py, test_gemm_conv_gpu.py):
+seeded 16-bit inputs, the unit in the last place of a 16-bit type, sentinel-filled buffers that show a store outside a kernel's slot,
+the element-wise bound check that names the worst element, and the fp64 references with their per-element bounds: the attention
+kernel's (``attention_ref_and_bound``), the GEMM family's with its epilogues, split-K and GEGLU (``gemm_ref_and_bound``), the
+convolutions' (``conv_ref_and_bound``) and the column statistics' (``colstats_ref_and_bound``).  Every bound is built from fp64
+quantities of the reference alone; test_attention_bound_cpu.py and test_gemm_bound_cpu.py show that each admits a model of the
+kernel's rounding points and refuses one-line defects of it.  Plain functions, nothing collected by pytest."""
+import math
+
 import torch
+import torch.nn.functional as F
 
 U32 = 2.0 ** -24                                   # fp32 unit roundoff
 TINY32 = 2.0 ** -126                               # smallest normal fp32: what a flushed subnormal intermediate can lose
@@ -117,3 +123,174 @@ def attention_ref_and_bound(q, k, v, scale, dt, chunk_bytes=4.0e8):
         o_all.append(o)
         b_all.append(b)
     return torch.cat(o_all), torch.cat(b_all)
+
+
+# ------------------------------------------------------------------------------------------------ GEMM and convolution
+ACC_ULPS = 1.0            # fp32 roundings allowed per accumulated product, in units of U32 (see gemm_ref_and_bound)
+GELU_AS_ABS = 7.5e-8      # |error| of Phi from Abramowitz & Stegun 7.1.26 (csrc/common.hpp, gelu_erf_f)
+
+
+def unit_roundoff(dt):
+    return 2.0 ** -(MANT[dt][0] + 1)
+
+
+def _pre_and_e32(S, A, K, terms, splits):
+    """``pre`` and the fp32 part of the bound from the fp64 sum of products S, the sum of their magnitudes A and the epilogue's
+    fp64 addends (absent ones left out)."""
+    pre, mag = S.clone(), S.abs()
+    for t in terms:
+        pre = pre + t
+        mag = mag + t.abs()
+    e32 = (K + 8) * ACC_ULPS * U32 * A + 3 * U32 * (mag + pre.abs())
+    if splits > 1:
+        e32 = e32 + (splits + 1) * U32 * A
+    return pre, e32
+
+
+def _rounded(pre, e32, dt, out_f32):
+    return e32 + (U32 * pre.abs() if out_f32 else 0.5 * ulp(pre.abs() + e32, dt))
+
+
+def gelu64(g):
+    return 0.5 * g * (1.0 + torch.erf(g / math.sqrt(2.0)))
+
+
+def _geglu(pre, e32, dt):
+    """out = val gelu(gate) from the two halves of ``pre`` (value columns first), both carrying ``e32``.  With e_v, e_g the two
+    halves of e32: |gelu(g + d) - gelu(g)| <= |gelu'(g)| |d| + 0.4 d^2 (gelu'' = phi(g) (2 - g^2), at most 2 phi(0) = 0.798 in
+    magnitude), gelu_erf_f differs from gelu by |g| (7.5e-8 + 8 U32) (Phi's absolute error, plus v_rcp, v_exp and the ten fused
+    multiply-adds, each relative to a quantity of at most 1/2), then one fp32 product and the rounding."""
+    no = pre.shape[1] // 2
+    val, g, ev, eg = pre[:, :no], pre[:, no:], e32[:, :no], e32[:, no:]
+    phi = torch.exp(-0.5 * g * g) / math.sqrt(2.0 * math.pi)
+    d1 = 0.5 * (1.0 + torch.erf(g / math.sqrt(2.0))) + g * phi
+    out = val * gelu64(g)
+    dgelu = d1.abs() * eg + 0.4 * eg * eg + (g.abs() + eg) * (GELU_AS_ABS + 8 * U32)
+    b = (val.abs() + ev) * dgelu + ev * gelu64(g).abs() + 2 * U32 * out.abs()
+    return out, b + 0.5 * ulp(out.abs() + b, dt)
+
+
+def gemm_ref_and_bound(a, w, dt, *, bias=None, rowbias=None, rows_per_sample=1, residual=None, out_f32=False, splits=1, geglu=False,
+                       a_err=None):
+    """``vface_gemm`` in fp64 and what a correct kernel may differ by, per element.  ``a [M, K]`` (for the dual-source form: the two
+    sources side by side), ``w [N, K]``: the 16-bit operands; ``bias [N]``, ``rowbias [M / rows_per_sample, N]`` fp32; ``residual
+    [M, N]`` 16-bit or fp32.  ``geglu``: ``w`` and ``bias`` in the module's order (value rows, then gate rows); the result has N / 2
+    columns.  Returns ``(ref, bound)``, fp64.  With u the unit roundoff of ``dt``, S = sum_k a w and A = sum_k |a| |w|:
+
+      pre   = S + bias + rowbias + residual
+      e32   = (K + 8) U32 A + 3 U32 (|S| + |bias| + |rowbias| + |residual| + |pre|)  [+ (splits + 1) U32 A]
+      bound = e32 + 0.5 ulp(|pre| + e32, dt)          16-bit output
+      bound = e32 + U32 |pre|                         fp32 output (``out_f32``: VFACE_EPI_OUT_F32 and the out32 carrier)
+
+    * (K + 8) U32 A: the products of two 16-bit values are exact in fp32; K of them summed in fp32 in ANY order (within a
+      v_mfma_f32_16x16x32, across its 32-deep steps, across K tiles) are off by at most (K - 1) U32 A to first order; + 8 covers the
+      second order up to K = 2^16 and whatever the instruction's internal alignment drops -- the term attention_ref_and_bound uses
+      for the same instruction.  ACC_ULPS = 1 is this reading: one HALF fp32 ulp (U32) per addition.
+    * 3 U32 (...): the epilogue adds (acc + bias) + rowbias, + residual in fp32, each at most U32 of its result, a result never
+      larger than the sum of the magnitudes it was made from; absent addends add nothing.
+    * split-K: the partial sums are fp32 and are added in order, then the epilogue as before: (splits + 1) U32 A more.
+    * ``a_err`` (fp64 [M, N], optional): what the operands themselves may be off by, already multiplied through |w| -- the
+      convolutions' fused input normalisation passes it (conv_ref_and_bound).
+    * one rounding to ``dt`` at the largest magnitude the bound admits; the fp32 forms store the sum itself (U32 |pre| stands for
+      the third epilogue add where the residual is absent, and for nothing else)."""
+    a64, w64 = a.double(), w.double()
+    K = a64.shape[1]
+    S, A = a64 @ w64.T, a64.abs() @ w64.abs().T
+    terms = []
+    if bias is not None:
+        terms.append(bias.double()[None, :].expand_as(S))
+    if rowbias is not None:
+        terms.append(rowbias.double().repeat_interleave(rows_per_sample, 0)[:S.shape[0]])
+    if residual is not None:
+        terms.append(residual.double())
+    pre, e32 = _pre_and_e32(S, A, K, terms, splits)
+    if a_err is not None:
+        e32 = e32 + a_err
+    if geglu:
+        assert residual is None and rowbias is None and not out_f32
+        return _geglu(pre, e32, dt)
+    return pre, _rounded(pre, e32, dt, out_f32)
+
+
+def conv_windows(x64, KH, KW, stride, upsample, pad):
+    """``x64 [nimg, C, H, W]`` -> ``(cols [nimg * OH * OW, KH * KW * C] in (tap, channel) order, OH, OW)``: nearest x2 upsampling
+    first if asked, zero padding ``pad`` = (top, bottom, left, right)."""
+    if upsample:
+        x64 = x64.repeat_interleave(2, 2).repeat_interleave(2, 3)
+    pt, pb, pl, pr = pad
+    xp = F.pad(x64, (pl, pr, pt, pb))
+    nimg, C, HP, WP = xp.shape
+    OH, OW = (HP - KH) // stride + 1, (WP - KW) // stride + 1
+    cols = F.unfold(xp, (KH, KW), stride=stride)                                  # [nimg, C * KH * KW, OH * OW], (channel, tap)
+    cols = cols.reshape(nimg, C, KH * KW, OH * OW).permute(0, 3, 2, 1).reshape(nimg * OH * OW, KH * KW * C)
+    return cols, OH, OW
+
+
+def conv_ref_and_bound(x, w, dt, *, stride=1, upsample=False, pad=(1, 1, 1, 1), bias=None, rowbias=None, residual=None, x2=None,
+                       w2=None, scale_shift=None, silu=False, out_f32=False, splits=1):
+    """``vface_conv3x3`` / ``vface_conv3x3_plus_1x1`` / one ``vface_upsample2x_conv3x3_phase`` in fp64 with the per-element bound of
+    gemm_ref_and_bound: the same form with K = taps Cin + C2 and A the same convolution of |x| with |w|.  ``x [nimg, Cin, H, W]``,
+    ``w [Cout, Cin, KH, KW]`` 16-bit (a phase: its 2 x 2 pre-summed kernel AS ROUNDED to ``dt``, ``pad`` = (1 - py, py, 1 - px, px));
+    ``pad`` = (0, 1, 0, 1) is VFACE_CONV_PAD_TRAILING; ``x2 [M, C2]``, ``w2 [Cout, C2]``: the fused 1x1 shortcut; ``rowbias [nimg,
+    Cout]``; ``residual [M, Cout]``.  Returns ``([M = nimg OH OW, Cout], bound)`` in NHWC row order.
+
+    ``scale_shift [nimg, Cin, 2]`` fp32 (+ ``silu``): the fused GroupNorm input.  The reference operand is o = act(x a + b) in fp64,
+    zero padding applied AFTER it; the kernel's is round_dt(act32(x a + b)), off by at most
+      d = u |o| + r |o| + 2 U32 (|x a| + |b|) |act'(x a + b)|
+    (the rounding to ``dt``; r = cpu_fp32_rel_error of the SiLU on the case's own arguments, 0 without it; the fp32 product and sum
+    in front of it through the activation's slope), and sum |w| d goes into the bound (``a_err``), with A taken from |o| + d."""
+    x64, w64 = x.double(), w.double()
+    nimg, cin = x64.shape[:2]
+    cout, _, KH, KW = w64.shape
+    d = None
+    if scale_shift is not None:
+        ab = scale_shift.double()
+        a_, b_ = ab[:, :, 0][:, :, None, None], ab[:, :, 1][:, :, None, None]
+        t = x64 * a_ + b_
+        if silu:
+            sg = torch.sigmoid(t)
+            o, slope = t * sg, (sg * (1.0 + t * (1.0 - sg))).abs()
+            r = cpu_fp32_rel_error(F.silu, (x.float() * scale_shift[:, :, 0][:, :, None, None] + scale_shift[:, :, 1][:, :, None, None]))
+        else:
+            o, slope, r = t, torch.ones_like(t), 0.0
+        d = (unit_roundoff(dt) + r) * o.abs() + 2 * U32 * ((x64 * a_).abs() + b_.abs()) * slope
+        x64 = o
+    cols, OH, OW = conv_windows(x64, KH, KW, stride, upsample, pad)
+    wk = w64.permute(0, 2, 3, 1).reshape(cout, KH * KW * cin)
+    a_err = None
+    if d is not None:
+        dcols, _, _ = conv_windows(d, KH, KW, stride, upsample, pad)
+        a_err = dcols @ wk.abs().T
+        acols = cols.abs() + dcols
+    else:
+        acols = cols.abs()
+    if x2 is not None:
+        cols, acols, wk = torch.cat([cols, x2.double()], 1), torch.cat([acols, x2.double().abs()], 1), torch.cat([wk, w2.double()], 1)
+    K = cols.shape[1]
+    S, A = cols @ wk.T, acols @ wk.abs().T
+    terms = []
+    if bias is not None:
+        terms.append(bias.double()[None, :].expand_as(S))
+    if rowbias is not None:
+        terms.append(rowbias.double().repeat_interleave(OH * OW, 0))
+    if residual is not None:
+        terms.append(residual.double())
+    pre, e32 = _pre_and_e32(S, A, K, terms, splits)
+    if a_err is not None:
+        e32 = e32 + a_err
+    return pre, _rounded(pre, e32, dt, out_f32)
+
+
+def colstats_ref_and_bound(stored, slice_rows):
+    """The (sum, sum of squares) a producer's epilogue leaves per statistics slice and output column.  ``stored [M, N]``: the values
+    as stored (read back from the device: the 16-bit output, or the fp32 carrier where there is one); ``slice_rows``: one index
+    tensor of rows per slice.  Returns ``(ref [slices, N, 2], bound)`` fp64: fp32 sums of ``rows`` terms in any order, the squares
+    rounded (or fused) in fp32 -- (rows + 4) U32 sum |v| and (rows + 4) U32 sum v^2."""
+    v = stored.double()
+    ref, bound = [], []
+    for rows in slice_rows:
+        s = v[rows]
+        k = (len(rows) + 4) * U32
+        ref.append(torch.stack([s.sum(0), (s * s).sum(0)], -1))
+        bound.append(torch.stack([k * s.abs().sum(0), k * (s * s).sum(0)], -1))
+    return torch.stack(ref), torch.stack(bound)
