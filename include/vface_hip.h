@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VFACE_ABI_VERSION 7   /* 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
+#define VFACE_ABI_VERSION 8   /* 8: 7 minus the composite hooked-attn1 call and its workspace query (a hooked attn1 is a sequence of single-kernel calls issued by the caller), nothing else changed; 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
 
 #define VFACE_OK 0
 #define VFACE_ERR_ARG (-1)
@@ -63,7 +63,7 @@ extern "C" {
  *  through the patch-staged kernel's 256-row tile -- same bits as the default kernel, measured 3-18 % SLOWER on the UNet's shapes
  *  (tools/bench_kernels.py "patch256"): an A/B switch, never chosen automatically) */
 
-/* fusion modes of the attn1 hook (pnp_utils.py:133-262) understood by vface_attn1_forward */
+/* fusion modes of the attn1 hook (pnp_utils.py:133-262): which single-kernel calls the caller issues between the projection and vface_attention */
 #define VFACE_FUSION_NONE 0       /* switch_on == False, or unpatched CrossAttention.forward */
 #define VFACE_FUSION_REPLACE 1    /* :133-143 and chunks == 2 (:259-262): q,k of every chunk <- chunk 0 */
 #define VFACE_FUSION_LINEAR 2     /* "fft"/"flow_fix"/"fft_vfixed"/"mix": q,k <- own*W_a + chunk0*W_b (folded weights) */
@@ -364,25 +364,6 @@ int vface_pooled_linear(const float* a, int64_t lda, int sa, const float* W, con
  *   ncls .. ld - 1 may hold anything); out [nframes][H][W] uint8 = table[first maximal class].  ld % 4 == 0. */
 int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h, int w, int ncls, const uint8_t* table,
                              uint8_t* out, int H, int W, void* stream);
-
-/* The hooked self-attention as one call (pnp_utils.py:94-287, the closure installed on attn1):
- *   x [B][n][d] (already LayerNorm'd), B = chunks * F laid out [uncond ; cond ; recon]
- *   Wqkv [3d][d]  = rows of to_q | to_k | to_v
- *   Wlin [2d][2d] = folded weights of a LINEAR fusion (rows q|k, columns [own x | chunk-0 x]) or NULL
- *   out = to_out(attention) + bo + rowbias[sample] + residual
- * flow != NULL (and h*w == n): chunk 1's fused q,k are smoothed by vface_flow_warp before attention
- * (pnp_utils.py:201-218).  v_fixed: v of chunks 1,2 <- their first frame (fft_vfixed :255-256).
- * halo_qk / halo_flow: previous rank's last-frame fused q|k [n][2d] and the flow into this rank's frame 0.
- * tail_qk (optional out): this rank's last-frame fused q|k, to hand to the next rank.
- * workspace: vface_attn1_workspace_bytes() bytes.  s32: fp32 residual / fp32 output of the out-projection. */
-size_t vface_attn1_workspace_bytes(int B, int n, int d, int chunks);
-int vface_attn1_forward(const void* x, int64_t ldx, const void* Wqkv, const void* Wlin, const void* Wo,
-                        const float* bo, const float* rowbias, int ld_rowbias, const void* residual, int64_t ldr,
-                        void* out, int64_t ldo, int B, int n, int d, int heads, int chunks, int fusion,
-                        int v_fixed, const float* flow, int h, int w, float alpha, float one_minus_alpha,
-                        int warp_flags, const void* halo_qk, const float* halo_flow, void* tail_qk,
-                        const int32_t* qk_map, const int32_t* v_map, void* workspace, size_t workspace_bytes,
-                        const void* zeros, int dtype, void* stream, const vface_stream32* s32);
 
 /* The FeedForward third of BasicTransformerBlock._forward in ONE launch (REFace/ldm/modules/attention.py:243 `x = ff(norm3(x)) + x`,
  * FeedForward / GEGLU :37-64, LayerNorm :233):  out = W2 (a * gelu(g)) + b2 + x,  [a ; g] = W1 LN(x) + b1.

@@ -36,7 +36,7 @@ def test_library_exports_every_declared_symbol():
     for name in decls:
         assert hasattr(lib, name), f"{name} declared in include/vface_hip.h but not exported"
     lib.vface_abi_version.restype = ctypes.c_int
-    assert lib.vface_abi_version() == 7
+    assert lib.vface_abi_version() == 8
 
 
 def test_ctypes_table_matches_header():
@@ -108,7 +108,6 @@ def test_every_entry_point_rejects_null_arguments_without_a_gpu():
         checked += 1
     assert checked >= 15
     assert lib.vface_splitk_workspace_bytes(0, 0, 0, 0, 0) == 0
-    assert lib.vface_attn1_workspace_bytes(0, 0, 0, 0) == 0
     assert lib.vface_attention_shared_scores_supported(40, 3) == 1 and lib.vface_attention_shared_scores_supported(80, 3) == 0
 
 

@@ -424,35 +424,30 @@ def test_timestep_embedding_pack_and_ddim():
 
 
 @pytest.mark.parametrize("mode", ["plain", "replace", "fft", "flow_fix"])
-def test_attn1_forward_level0_vs_reference_golden(mode):
-    """The hooked attn1 as one C call at the real level-0 shape (d=320, 8 heads, n=4096, F=2) against the
-    reference-generated fixture (strided token slice)."""
-    h = hip()
-    from vface_amd.packing import fold_fsai, pack_qkv
+def test_engine_attn1_sequence_level0_vs_reference_golden(mode):
+    """The hooked attn1 as the engine sequences it (UNetEngine._attn1_qkv_att + _attn1_out, 16-bit output, no residual) at the real
+    level-0 shape (d=320, 8 heads, n=4096, F=2) against the reference-generated fixture (strided token slice)."""
+    from vface_amd.engine import HookCfg, UNetEngine, plan_fusion
+    from vface_amd.packing import pack_qkv
     from vface_amd.utils import synth
     g = load_golden("attn_module")
-    F_, n, d = 2, 4096, 320
+    F_, n, d, heads = 2, 4096, 320, 8
     B = 3 * F_
     sd = synth.synth_state_dict({"attn1.to_q.weight": (d, d), "attn1.to_k.weight": (d, d),
                                  "attn1.to_v.weight": (d, d), "attn1.to_out.0.weight": (d, d),
                                  "attn1.to_out.0.bias": (d,)})
-    x = synth.synth_normal("attnmod.x", (B, n, d)).half().to(DEV)
-    wqkv = pack_qkv(sd["attn1.to_q.weight"], sd["attn1.to_k.weight"], sd["attn1.to_v.weight"]).half().to(DEV)
-    wlin = fold_fsai(sd["attn1.to_q.weight"], sd["attn1.to_k.weight"], 0.8).half().to(DEV)
-    wo = sd["attn1.to_out.0.weight"].half().to(DEV)
-    bo = sd["attn1.to_out.0.bias"].to(DEV)
-    ws = torch.empty(h.attn1_workspace_bytes(B, n, d, 3), dtype=torch.uint8, device=DEV)
-    out = torch.empty(B, n, d, dtype=torch.float16, device=DEV)
-    kw = dict(B=B, n=n, d=d, heads=8, chunks=3, ldx=d, ldo=d, workspace=ws)
-    if mode == "plain":
-        h.attn1_forward(x, wqkv, None, wo, bo, out, fusion=h.FUSION_NONE, **kw)
-    elif mode == "replace":
-        qk_map = torch.arange(B, dtype=torch.int32) % F_
-        h.attn1_forward(x, wqkv, None, wo, bo, out, fusion=h.FUSION_REPLACE, qk_map=qk_map.to(DEV), **kw)
-    else:
-        flow = synth.synth_flow(F_ - 1, 64, 64).to(DEV) if mode == "flow_fix" else None
-        h.attn1_forward(x, wqkv, wlin, wo, bo, out, fusion=h.FUSION_LINEAR, flow=flow, h=64, w=64, alpha=0.8, **kw)
-    assert rel_l2(out[:, ::128].cpu().float(), g[mode]) < 1e-3
+    x = synth.synth_normal("attnmod.x", (B, n, d)).half().to(DEV).reshape(B * n, d)
+    eng = UNetEngine(None, torch.float16, device=DEV)
+    p = {"c": d, "wqkv": pack_qkv(sd["attn1.to_q.weight"], sd["attn1.to_k.weight"], sd["attn1.to_v.weight"]).half().to(DEV),
+         "wo": {"w": sd["attn1.to_out.0.weight"].half().to(DEV), "b": sd["attn1.to_out.0.bias"].to(DEV)},
+         "wlin": {}, "qk_src": (sd["attn1.to_q.weight"], sd["attn1.to_k.weight"])}
+    flow = synth.synth_flow(F_ - 1, 64, 64).to(DEV) if mode == "flow_fix" else None
+    cfg = None if mode == "plain" else HookCfg(chunks=3, fusion=mode, flow=flow, split_ratio_fft=0.8, alpha=0.8)
+    pl = plan_fusion(cfg, B, n)
+    out = torch.empty(B * n, d, dtype=torch.float16, device=DEV)
+    att = eng._attn1_qkv_att(x, torch.empty(B * n, 3 * d, dtype=torch.float16, device=DEV), p, pl, B, n, heads, projected=False)
+    eng._attn1_out(att, p, None, n, out)
+    assert rel_l2(out.reshape(B, n, d)[:, ::128].cpu().float(), g[mode]) < 1e-3
 
 
 @pytest.mark.parametrize("N_,cout", [(2, 320), (3, 640)])

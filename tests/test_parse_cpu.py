@@ -140,7 +140,7 @@ def test_fill_parser_keeps_the_network_alive():
 def test_new_entries_in_header_ctypes_and_library():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vface_hip.h")).read(), flags=re.S)
     lib = hip.load()
-    assert lib.vface_abi_version() == 7
+    assert lib.vface_abi_version() == 8
     for name in NEW_ENTRIES:
         m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", src, flags=re.S)
         assert m, f"{name} is not declared in include/vface_hip.h"

@@ -842,28 +842,6 @@ def test_drop_source_half_of_inversion_is_bit_identical(small):
     assert xb.shape[0] == F_ and torch.equal(xa[:F_], xb)
 
 
-@pytest.mark.parametrize("mode", ["off", "in_replace", "in_fft", "in_flow_fix", "in_fft_vfixed"])
-def test_decomposed_attn1_equals_one_call_form_bit_for_bit(small, mode):
-    """bench.py's instrumented pass issues the launches of ``vface_attn1_forward`` call by call (UNetEngine._attn1_qkv_att + _attn1_out)
-    to time the projections and the attention kernel separately: same kernels, same parameters, same order -> same bits."""
-    ldm, sampler, _ = small
-    F_, h, w = 2, 32, 32
-    x = synth.synth_normal("small.x", (6, 9, h, w)).to(DEV)
-    ctx = synth.synth_normal("small.ctx", (6, 1, 768)).to(DEV)
-    t = torch.full((6,), 481, dtype=torch.long, device=DEV)
-    flow = [synth.synth_flow(F_ - 1, h, w)[i][None] for i in range(F_ - 1)]
-    _register(sampler, mode, flow)
-    eng = ldm.unet.engine
-    try:
-        eng.decompose_attn1 = False
-        a = ldm.apply_model(x, t, ctx).clone()
-        eng.decompose_attn1 = True
-        b = ldm.apply_model(x, t, ctx).clone()
-    finally:
-        eng.decompose_attn1 = False
-    assert torch.equal(a, b), (a - b).abs().max().item()
-
-
 def _sampler_batch(tag, F_, h):
     """Seeded inputs of the sampler's batch: x, inv, inpaint, mask [F, ., h, h], ctx [3F, 1, 768] (uncond ; cond ; target), flow."""
     return dict(x=synth.synth_normal(f"{tag}.x", (F_, 4, h, h)), inv=synth.synth_normal(f"{tag}.inv", (F_, 4, h, h)),

@@ -34,7 +34,6 @@ def main():
     sampler.make_schedule(50, ddim_eta=0.0, verbose=False)
     eng = ldm.unet.engine
     eng.use_graph = False
-    eng.decompose_attn1 = True
     F_, h = a.frames, a.res // 8
     sampler.flow_gate = "reference" if h == 64 else "flow_hw"
     sampler.hook_plan = HookPlan(fusion=a.fusion, enabled=a.fusion != "none")

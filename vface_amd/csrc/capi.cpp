@@ -2,13 +2,11 @@
 #include "../../include/vface_hip.h"
 
 #include <hip/hip_runtime.h>
-#include <math.h>
 
 #include "vface_kernels.hpp"
 
 namespace {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
 GemmParams plain_gemm(const void* A, long lda, const void* Wt, long ldw, int M, int N, int K, const float* bias,
                       void* C, long ldc, const void* zeros) {
@@ -299,94 +297,6 @@ int vface_pooled_linear(const float* a, int64_t lda, int sa, const float* W, con
 int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h, int w, int ncls, const uint8_t* table,
                              uint8_t* out, int H, int W, void* stream) {
     return vf_launch_upsample_argmax_u8(logits, ld, nframes, h, w, ncls, table, out, H, W, S(stream));
-}
-
-size_t vface_attn1_workspace_bytes(int B, int n, int d, int chunks) {
-    if (B <= 0 || n <= 0 || d <= 0 || chunks <= 0) return 0;
-    const size_t F = (size_t)B / chunks;
-    return align256((size_t)B * n * 3 * d * 2) + align256(F * n * 2 * d * 2) + align256((size_t)B * n * d * 2);
-}
-
-int vface_attn1_forward(const void* x, int64_t ldx, const void* Wqkv, const void* Wlin, const void* Wo,
-                        const float* bo, const float* rowbias, int ld_rowbias, const void* residual, int64_t ldr,
-                        void* out, int64_t ldo, int B, int n, int d, int heads, int chunks, int fusion,
-                        int v_fixed, const float* flow, int h, int w, float alpha, float one_minus_alpha,
-                        int warp_flags, const void* halo_qk, const float* halo_flow, void* tail_qk,
-                        const int32_t* qk_map, const int32_t* v_map, void* workspace, size_t workspace_bytes,
-                        const void* zeros, int dtype, void* stream, const vface_stream32* s32) {
-    if (!x || !Wqkv || !Wo || (!out && !(s32 && s32->out32)) || !workspace || !zeros) return VFACE_ERR_ARG;
-    if (B <= 0 || n <= 0 || d <= 0 || heads <= 0 || chunks <= 0 || d % heads) return VFACE_ERR_ARG;
-    if (dtype != VFACE_F16 && dtype != VFACE_BF16) return VFACE_ERR_DTYPE;
-    if (fusion != VFACE_FUSION_NONE && B % chunks) return VFACE_ERR_SHAPE;
-    if (workspace_bytes < vface_attn1_workspace_bytes(B, n, d, chunks)) return VFACE_ERR_WORKSPACE;
-    if (fusion == VFACE_FUSION_REPLACE && !qk_map) return VFACE_ERR_ARG;
-    if (fusion == VFACE_FUSION_LINEAR && (!Wlin || (d % 64))) return VFACE_ERR_SHAPE;
-    if (v_fixed && !v_map) return VFACE_ERR_ARG;
-    const bool warp = fusion == VFACE_FUSION_LINEAR && flow != nullptr;
-    if (warp && (h * w != n || chunks < 2 || chunks > 3)) return VFACE_ERR_SHAPE;      // (2: a batch without the recon third)
-    hipStream_t st = S(stream);
-    const size_t esz = 2;
-    const long F = B / chunks, Fn = F * n;
-    char* ws = static_cast<char*>(workspace);
-    char* qkv = ws;
-    char* T = qkv + align256((size_t)B * n * 3 * d * esz);
-    char* att = T + align256((size_t)Fn * 2 * d * esz);
-    const char* xb = static_cast<const char*>(x);
-    const char* wq = static_cast<const char*>(Wqkv);
-    int rc;
-    auto at = [&](char* base, long row, long col, long ld) { return base + ((size_t)row * ld + col) * esz; };
-
-    if (fusion == VFACE_FUSION_NONE) {
-        GemmParams p = plain_gemm(x, ldx, Wqkv, d, B * n, 3 * d, d, nullptr, qkv, 3 * d, zeros);
-        if ((rc = vf_launch_gemm(p, dtype, st))) return rc;
-    } else {
-        // chunk 0: q, k, v as projected (pnp_utils.py:106,127-128)
-        GemmParams p0 = plain_gemm(x, ldx, Wqkv, d, (int)Fn, 3 * d, d, nullptr, qkv, 3 * d, zeros);
-        if ((rc = vf_launch_gemm(p0, dtype, st))) return rc;
-        // other chunks: v only -- their q, k are overwritten by the fusion
-        GemmParams pv = plain_gemm(xb + (size_t)Fn * ldx * esz, ldx, wq + (size_t)2 * d * d * esz, d, (int)(B * n - Fn),
-                                   d, d, nullptr, at(qkv, Fn, 2 * d, 3 * d), 3 * d, zeros);
-        if ((rc = vf_launch_gemm(pv, dtype, st))) return rc;
-        if (fusion == VFACE_FUSION_LINEAR) {
-            // fused q|k of chunk c >= 1: [x_c | x_0] (K = 2d) times the folded weights
-            for (int c = 1; c < chunks; ++c) {
-                const bool to_tmp = warp && c == 1;
-                GemmParams pf = plain_gemm(xb + (size_t)c * Fn * ldx * esz, ldx, Wlin, 2 * d, (int)Fn, 2 * d, 2 * d,
-                                           nullptr, to_tmp ? T : at(qkv, c * Fn, 0, 3 * d), to_tmp ? 2 * d : 3 * d,
-                                           zeros);
-                pf.A2 = x; pf.lda2 = ldx; pf.K1 = d; pf.a2_row_mod = 0;
-                if ((rc = vf_launch_gemm(pf, dtype, st))) return rc;
-            }
-            if (warp) {
-                if (tail_qk) {
-                    rc = vf_launch_copy2d(T + (size_t)(F - 1) * n * 2 * d * esz, 2 * d, tail_qk, 2 * d, n, 2 * d, dtype, st);
-                    if (rc) return rc;
-                }
-                rc = vf_launch_flow_warp(T, 2 * d, (long)n * 2 * d, halo_qk, 2 * d, flow, halo_flow,
-                                         at(qkv, Fn, 0, 3 * d), 3 * d, (long)n * 3 * d, (int)F, h, w, 2 * d, alpha,
-                                         one_minus_alpha, warp_flags, nullptr, nullptr, dtype, st);
-                if (rc) return rc;
-            }
-        }
-    }
-    AttnParams a{};
-    a.Q = qkv; a.K = qkv + (size_t)d * esz; a.V = qkv + (size_t)2 * d * esz;
-    a.ldq = a.ldk = a.ldv = 3 * d; a.bsq = a.bsk = a.bsv = (long)n * 3 * d;
-    a.qk_map = (fusion == VFACE_FUSION_REPLACE) ? qk_map : nullptr;
-    a.v_map = v_fixed ? v_map : nullptr;
-    a.O = att; a.ldo = d; a.bso = (long)n * d;
-    a.B = B; a.heads = heads; a.n = n; a.nk = n; a.dh = d / heads;
-    if (fusion == VFACE_FUSION_REPLACE && vf_attention_shared_scores_supported(d / heads, chunks)) {
-        // every chunk attends with q,k of chunk 0 (pnp_utils.py:136-142): softmax once per frame, `chunks` value sets
-        a.qk_map = nullptr; a.B = (int)F; a.v_sets = chunks; a.set_stride = (int)F;
-    }
-    a.scale = 1.0f / sqrtf((float)(d / heads));
-    if ((rc = vf_launch_attention(a, dtype, st))) return rc;
-    GemmParams po = plain_gemm(att, d, Wo, d, B * n, d, d, bo, out, ldo, zeros);
-    po.rowbias = rowbias; po.rows_per_sample = n; po.ld_rowbias = ld_rowbias;
-    po.residual = residual; po.ldr = ldr;
-    apply_s32(po, s32);
-    return vf_launch_gemm(po, dtype, st);
 }
 
 int vface_ffn_fused_supported(int64_t M, int C) { return vf_ffn_fused_supported((long)M, C) ? 1 : 0; }

@@ -190,12 +190,12 @@ def fold_qk(kind: str, param: float, wq: torch.Tensor, wk: torch.Tensor) -> torc
 
 
 def qkv_attention(qkv: torch.Tensor, att: torch.Tensor, *, B: int, n: int, d: int, heads: int, **maps):
-    """Self-attention over a ``[rows, 3d]`` q|k|v buffer of n-token samples into ``att`` ``[rows, d]``, as ``vface_attn1_forward``
-    (capi.cpp) sets it up; ``maps``: ``hip.attention``'s sample maps / value sets."""
+    """Self-attention over a ``[rows, 3d]`` q|k|v buffer of n-token samples into ``att`` ``[rows, d]``: q, k and v are the column
+    thirds of one buffer, the softmax scale is ``dh ** -0.5`` formed in fp32; ``maps``: ``hip.attention``'s sample maps / value sets."""
     dh = d // heads
     hip.attention(qkv, qkv[:, d:], qkv[:, 2 * d:], att, B=B, heads=heads, n=n, nk=n, dh=dh, ldq=3 * d, ldk=3 * d, ldv=3 * d,
                   bsq=n * 3 * d, bsk=n * 3 * d, bsv=n * 3 * d, ldo=d, bso=n * d,
-                  scale=float(np.float32(1.0) / np.sqrt(np.float32(dh))), **maps)   # fp32 arithmetic, as capi.cpp computes it
+                  scale=float(np.float32(1.0) / np.sqrt(np.float32(dh))), **maps)   # (fp32 arithmetic: it fixes the bits)
 
 
 def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, rowbias=None, residual=None,
@@ -229,66 +229,6 @@ def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, 
              rowbias=rowbias, rows_per_sample=n, residual=residual, ldr=residual.stride(0) if residual is not None else 0,
              residual32=residual32, out32=out32)
     return o
-
-
-COMPUTE_DTYPE = torch.float16  # module-level default for standalone module calls
-
-
-def attn_module_forward(mod, x: torch.Tensor, context: Optional[torch.Tensor], cfg: Optional[HookCfg]):
-    """``CrossAttention.forward`` / the hooked closure for a stand-alone module call on ``[B, n, d]`` CUDA
-    tensors (attention.py:179-221, pnp_utils.py:94-287).  Returns the 16-bit result, as autocast does."""
-    dt = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else COMPUTE_DTYPE
-    pk = mod._packed(dt)
-    B, n, d_in = x.shape
-    d = mod.heads * mod.dim_head
-    dev = x.device
-
-    def to16(t):
-        t = t.contiguous()
-        if t.dtype == dt:
-            return t
-        o = torch.empty(t.shape, dtype=dt, device=dev)
-        hip.cast_f32(t.float(), o)
-        return o
-
-    x16 = to16(x).reshape(B * n, d_in)
-    out = torch.empty(B * n, mod.to_out[0].weight.shape[0], dtype=dt, device=dev)
-    if context is None:
-        pl = plan_fusion(cfg, B, n)
-        if pl["staged"]:
-            staged_attn1(x16, pk["wqkv"], pk["wo"], pk["bo"], out, B=B, n=n, d=d, heads=mod.heads, mode=pl["staged"])
-            return out.reshape(B, n, -1)
-        chunks = pl["chunks"]
-        wlin = None
-        if pl["wlin"]:
-            key = (pl["wlin"][0], round(float(pl["wlin"][1]), 9))
-            if key not in pk["wlin"]:
-                pk["wlin"][key] = fold_qk(*key, mod.to_q.weight, mod.to_k.weight).to(device=dev, dtype=dt).contiguous()
-            wlin = pk["wlin"][key]
-        c = B // chunks
-        qk_map = sample_map("qk_replace", B, c).to(dev) if pl["fusion"] == hip.FUSION_REPLACE else None
-        v_map = sample_map("v_fixed", B, c).to(dev) if pl["v_fixed"] else None
-        ws = torch.empty(hip.attn1_workspace_bytes(B, n, d, chunks), dtype=torch.uint8, device=dev)
-        flow = pl["flow"]
-        hw = pl["warp_hw"] or (0, 0)
-        hip.attn1_forward(x16, pk["wqkv"], wlin, pk["wo"], pk["bo"], out, B=B, n=n, d=d, heads=mod.heads,
-                          chunks=chunks, fusion=pl["fusion"], ldx=d_in, ldo=out.shape[1], workspace=ws,
-                          v_fixed=pl["v_fixed"], flow=flow, h=hw[0], w=hw[1], alpha=pl["alpha"], qk_map=qk_map,
-                          v_map=v_map)
-    else:
-        m = context.shape[1]
-        c16 = to16(context).reshape(B * m, context.shape[2])
-        q = torch.empty(B * n, d, dtype=dt, device=dev)
-        k = torch.empty(B * m, d, dtype=dt, device=dev)
-        v = torch.empty(B * m, d, dtype=dt, device=dev)
-        hip.gemm(x16, pk["wq"], q, M=B * n, N=d, K=d_in, lda=d_in, ldc=d)
-        hip.gemm(c16, pk["wk"], k, M=B * m, N=d, K=c16.shape[1], lda=c16.shape[1], ldc=d)
-        hip.gemm(c16, pk["wv"], v, M=B * m, N=d, K=c16.shape[1], lda=c16.shape[1], ldc=d)
-        att = torch.empty(B * n, d, dtype=dt, device=dev)
-        hip.attention(q, k, v, att, B=B, heads=mod.heads, n=n, nk=m, dh=mod.dim_head, ldq=d, ldk=d, ldv=d, bsq=n * d,
-                      bsk=m * d, bsv=m * d, ldo=d, bso=n * d, scale=mod.scale)
-        hip.gemm(att, pk["wo"], out, M=B * n, N=out.shape[1], K=d, lda=d, ldc=out.shape[1], bias=pk["bo"])
-    return out.reshape(B, n, -1)
 
 
 def _phase_form_pays(hw_in: int, cout: int) -> bool:
@@ -342,7 +282,6 @@ class UNetEngine(_StepReplay):
         self.concat32 = os.environ.get("VFACE_CONCAT32", "0") == "1"
         self.interior16 = os.environ.get("VFACE_INTERIOR16", "1") != "0"      # (see _st; VFACE_INTERIOR16=0: fp32 interior sums, A/B)
         self._shape_ok: Dict[tuple, bool] = {}         # (_supported)
-        self.decompose_attn1 = False                   # bench.py's instrumented pass: vface_attn1_forward's launches call by call
         # the batch holds only the first `live_chunks` chunks of the hooks' three (the sampler's dead-branch elimination leaves
         # the recon third out: DDIMSampler.drop_dead_branches); None = every chunk is there
         self.live_chunks: Optional[int] = None
@@ -660,25 +599,13 @@ class UNetEngine(_StepReplay):
             kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid}
             return staged_attn1(xln, p["wqkv"], p["wo"]["w"], p["wo"]["b"], out, B=N, n=n, d=d, heads=heads,
                                 mode=pl["staged"], rowbias=a2vec, chunks=pl["chunks"], edit=edit, **kw)
-        fusion, chunks, hw = pl["fusion"], pl["chunks"], pl["warp_hw"]
-        if (hw is not None and self.halo_exchange is not None) or self.decompose_attn1 or pl["hook_chunks"] != chunks:
-            # the launches of the one call below, issued from here: a sharded clip (the boundary exchange sits between them); bench.py's
-            # instrumented pass (HIP events around the projections and the attention kernel separately); a batch without its last
-            # chunk (the shared-score attention must run the FULL hook's instantiation with fewer live sets to keep the bits of the
-            # full batch -- vface_attn1_forward only knows the chunks it is handed)
-            att = self._attn1_qkv_att(xln, self._new(N * n, 3 * d), p, pl, N, n, heads, projected=False)
-            self._attn1_out(att, p, a2vec, n, out, **res_kw)
-            return out32 if s32 else out
-        ws = torch.empty(hip.attn1_workspace_bytes(N, n, d, chunks), dtype=torch.uint8, device=self.device)
-        hip.attn1_forward(xln, p["wqkv"], self._wlin(p, *pl["wlin"]) if pl["wlin"] else None, p["wo"]["w"], p["wo"]["b"], out,
-                          B=N, n=n, d=d, heads=heads, chunks=chunks, fusion=fusion, ldx=xln.stride(0), ldo=d, workspace=ws,
-                          rowbias=a2vec, v_fixed=pl["v_fixed"], flow=pl["flow"], h=hw[0] if hw else 0, w=hw[1] if hw else 0,
-                          alpha=pl["alpha"], qk_map=self._map("qk_replace", N, N // chunks) if fusion == hip.FUSION_REPLACE else None,
-                          v_map=self._map("v_fixed", N, N // chunks) if pl["v_fixed"] else None, **res_kw)
+        att = self._attn1_qkv_att(xln, self._new(N * n, 3 * d), p, pl, N, n, heads, projected=False)
+        self._attn1_out(att, p, a2vec, n, out, **res_kw)
         return out32 if s32 else out
 
     def _attn1_out(self, att: torch.Tensor, p: dict, a2vec: torch.Tensor, n: int, out: Optional[torch.Tensor], **res_kw):
-        """attn1's out-projection + bias + attn2's row bias + residual, as ``vface_attn1_forward`` ends (no split-K workspace)."""
+        """The end of a hooked attn1: its out-projection + bias + attn2's row bias + residual as one GEMM without a split-K workspace.
+        ``out`` 16-bit, or None with ``residual32`` / ``out32`` (the fp32 residual stream)."""
         d = p["c"]
         hip.gemm(att, p["wo"]["w"], out, M=att.shape[0], N=d, K=d, lda=d, ldc=out.stride(0) if out is not None else 0, ldw=d,
                  bias=p["wo"]["b"], rowbias=a2vec, rows_per_sample=n, split_k=False, **res_kw)
@@ -699,11 +626,16 @@ class UNetEngine(_StepReplay):
 
     def _attn1_qkv_att(self, ln: Optional[torch.Tensor], qkv: torch.Tensor, p: dict, pl: dict, N: int, n: int, heads: int, *,
                        projected: bool) -> torch.Tensor:
-        """The middle of a hooked attn1, from the LayerNorm output ``ln`` to the attention output ``[N n, d]``: the launch sequence
-        of ``vface_attn1_forward`` (capi.cpp) without its out-projection -- the same kernels with the same parameters in the same
-        order, hence the same bits (tests/test_kernels_gpu.py).  ``projected``: the fused front already wrote chunk 0's q|k|v and
-        the other chunks' v into ``qkv`` (``_st_front``; ``ln`` is then only needed by the linear fusions); otherwise those two GEMMs
-        (one over the whole batch when no hook edits it) are issued here.
+        """A hooked attn1 (pnp_utils.py:94-287) from the LayerNorm output ``ln`` to the attention output ``[N n, d]`` -- the one launch
+        sequence of every non-staged plan (``_attn1_out`` or a fused tail ends it):
+          no hook      one q|k|v projection over the batch, attention;
+          replace      chunk 0's q|k|v and the other chunks' v, attention with every chunk reading chunk 0's q, k (scores once per
+                       frame where the kernel has that form, else through the q|k sample map);
+          linear       (fft / flow_fix / fft_vfixed / mix) the same two projections, then chunk k >= 1's q|k as ONE dual-source GEMM
+                       ``[own | chunk 0] @ wlin`` (``_fused_qk``); flow_fix warps chunk 1's along the flow on the way into ``qkv``
+                       (``_warp``); fft_vfixed reads v through the first-frame map.
+        ``projected``: the fused front already wrote chunk 0's q|k|v and the other chunks' v into ``qkv`` (``_st_front``; ``ln`` is then
+        only needed by the linear fusions); otherwise those two GEMMs (one over the whole batch when no hook edits it) are issued here.
         Frames sharded across ranks and a flow warp: the one-neighbour boundary exchange sits between chunk 1's
         fused projection and the warp, and the launches that do not depend on it are issued behind its start."""
         d = p["c"]
@@ -788,9 +720,9 @@ class UNetEngine(_StepReplay):
         and the producer's column statistics of ``x`` and a width the kernel takes.  Returns the block's last running sum
         (16-bit, proj_out's operand), or None when this layer does not qualify (the caller then runs the separate launches), or
         True when ``post = (out16 | None, colstats | None, out32)`` was given and the tail launch also ran proj_out + ``x`` into it.
-        What follows the front is the launch sequence of ``vface_attn1_forward`` (capi.cpp) minus its first two GEMMs
-        (``_attn1_qkv_att``: the dual-source projections of the hook's linear fusions read the LayerNorm output the front also
-        writes then), the out-projection into the fp32 stream, then norm3 + FeedForward."""
+        What follows the front is the hooked attn1 behind its projections (``_attn1_qkv_att`` with ``projected=True``: the
+        dual-source projections of the hook's linear fusions read the LayerNorm output the front also writes then), the
+        out-projection into the fp32 stream, then norm3 + FeedForward."""
         c, N, n, M = p["c"], x.N, x.hw, x.M
         if not self.fuse_front or p.get("front_w") is None or x.t32 is None or x.cs is None or not self._front_ok(M, c, n):
             return None

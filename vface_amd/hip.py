@@ -89,10 +89,6 @@ SIGNATURES = {
     "vface_channel_gate": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "vface_pooled_linear": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "vface_upsample_argmax_u8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
-    "vface_attn1_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
-    "vface_attn1_forward": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32,
-                                      _i32, _i32, _i32, _i32, _vp, _i32, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _vp,
-                                      _vp, _vp, _sz, _vp, _i32, _vp, _s32p]),
     "vface_ffn_fused_supported": (C.c_int, [_i64, _i32]),
     "vface_ffn_fused": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
     "vface_attn_out_ffn_fused": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp,
@@ -147,7 +143,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    if lib.vface_abi_version() != 7:
+    if lib.vface_abi_version() != 8:
         raise VFaceHipError("libvface_hip.so ABI version mismatch")
     _lib = lib
     return lib
@@ -633,22 +629,6 @@ def upsample_argmax_u8(logits: torch.Tensor, table: torch.Tensor, *, F: int, h: 
     rc = load().vface_upsample_argmax_u8(_p(logits), logits.stride(0), F, h, w, ncls, _p(table), _p(out), H, W, _stream())
     _check(rc, "vface_upsample_argmax_u8")
     return out
-
-
-def attn1_workspace_bytes(B: int, n: int, d: int, chunks: int) -> int:
-    return int(load().vface_attn1_workspace_bytes(B, n, d, chunks))
-
-
-def attn1_forward(x, wqkv, wlin, wo, bo, out, *, B, n, d, heads, chunks, fusion, ldx, ldo, workspace, rowbias=None,
-                  residual=None, ldr=0, v_fixed=False, flow=None, h=0, w=0, alpha=0.8, cuda_recip_div=False,
-                  halo_qk=None, halo_flow=None, tail_qk=None, qk_map=None, v_map=None, residual32=None, out32=None):
-    rc = load().vface_attn1_forward(_p(x), ldx, _p(wqkv), _p(wlin), _p(wo), _p(bo), _p(rowbias),
-                                    rowbias.stride(0) if rowbias is not None else 0, _p(residual), ldr, _p(out), ldo,
-                                    B, n, d, heads, chunks, fusion, int(v_fixed), _p(flow), h, w, float(alpha),
-                                    float(1.0 - alpha), int(cuda_recip_div), _p(halo_qk), _p(halo_flow), _p(tail_qk),
-                                    _p(qk_map), _p(v_map), _p(workspace), workspace.numel() * workspace.element_size(),
-                                    _p(zeros_page(x.device)), dtype_code(x.dtype), _stream(), _s32(residual32, out32))
-    _check(rc, "vface_attn1_forward")
 
 
 def ffn_fused_supported(M: int, C_: int) -> bool:

@@ -91,8 +91,8 @@ class CrossAttention(nn.Module):
             raise NotImplementedError("attention masks are not used on the VFace path (pnp_utils.py:276-280 is dead)")
         if not x.is_cuda:
             raise hip.VFaceHipError("CrossAttention.forward needs CUDA tensors: no CPU fallback on the VFace path")
-        from ...engine import attn_module_forward
-        return attn_module_forward(self, x, context, _cfg)
+        from ...module_exec import cross_attention_forward
+        return cross_attention_forward(self, x, context, _cfg)
 
 
 class BasicTransformerBlock(nn.Module):

@@ -1,6 +1,7 @@
 """Stand-alone ``forward`` of the container modules of the drop-in surface (SURVEY 8b "module surface"):
 ``ResBlock`` / ``Downsample`` / ``Upsample`` / ``TimestepEmbedSequential`` (openaimodel.py:74-160, 255-275),
-``SpatialTransformer`` / ``BasicTransformerBlock`` / ``FeedForward`` / ``GEGLU`` (attention.py:37-64, 239-243, 278-289).
+``SpatialTransformer`` / ``BasicTransformerBlock`` / ``CrossAttention`` / ``FeedForward`` / ``GEGLU`` (attention.py:37-64, 179-221,
+239-243, 278-289).
 
 Inside ``UNetModel.forward`` these layers are executed by ``UNetEngine`` as one fused kernel sequence (stacked
 embedding projections, in-place concatenation, ...); a caller that invokes a sub-module directly gets the same
@@ -15,7 +16,7 @@ from typing import Optional
 import torch
 
 from . import hip
-from .engine import Act, UNetEngine
+from .engine import Act, HookCfg, UNetEngine, plan_fusion, staged_attn1
 
 
 def _engine_for(module, x: torch.Tensor) -> UNetEngine:
@@ -187,6 +188,47 @@ def transformer_block_forward(mod, x: torch.Tensor, context: Optional[torch.Tens
     a2 = _a2vec(eng, sd, "", context, B, d, P)
     t2, t2_32 = eng._block(t0, p, mod.attn1, a2, B, n, None, want32=True)
     return t2_32.reshape(B, n, d).to(x.dtype)
+
+
+def cross_attention_forward(mod, x: torch.Tensor, context: Optional[torch.Tensor], cfg: Optional[HookCfg]) -> torch.Tensor:
+    """``CrossAttention.forward`` / the hooked closure on ``[B, n, d]`` tokens (attention.py:179-221, pnp_utils.py:94-287): self-attention
+    (``context=None``) is the engine's hooked attn1 sequence without a row bias or a residual; a context of any length is three
+    projections, ``vface_attention`` with nk = its length and to_out.  Returns the 16-bit result, as autocast does."""
+    eng, _ = _engine_for(mod, x)
+    pk = mod._packed(eng.dtype)
+    B, n, d_in = x.shape
+    d = mod.heads * mod.dim_head
+
+    def to16(t):
+        t = t.contiguous()
+        if t.dtype == eng.dtype:
+            return t
+        o = torch.empty(t.shape, dtype=eng.dtype, device=eng.device)
+        hip.cast_f32(t.float(), o)
+        return o
+
+    x16 = to16(x).reshape(B * n, d_in)
+    out = eng._new(B * n, mod.to_out[0].weight.shape[0])
+    if context is None:
+        pl = plan_fusion(cfg, B, n)
+        if pl["staged"]:
+            staged_attn1(x16, pk["wqkv"], pk["wo"], pk["bo"], out, B=B, n=n, d=d, heads=mod.heads, mode=pl["staged"])
+        else:
+            p = {"c": d, "wqkv": pk["wqkv"], "wo": {"w": pk["wo"], "b": pk["bo"]}, "wlin": pk["wlin"],
+                 "qk_src": (mod.to_q.weight, mod.to_k.weight)}
+            att = eng._attn1_qkv_att(x16, eng._new(B * n, 3 * d), p, pl, B, n, mod.heads, projected=False)
+            eng._attn1_out(att, p, None, n, out)
+    else:
+        m = context.shape[1]
+        c16 = to16(context).reshape(B * m, context.shape[2])
+        q, k, v, att = eng._new(B * n, d), eng._new(B * m, d), eng._new(B * m, d), eng._new(B * n, d)
+        hip.gemm(x16, pk["wq"], q, M=B * n, N=d, K=d_in, lda=d_in, ldc=d)
+        hip.gemm(c16, pk["wk"], k, M=B * m, N=d, K=c16.shape[1], lda=c16.shape[1], ldc=d)
+        hip.gemm(c16, pk["wv"], v, M=B * m, N=d, K=c16.shape[1], lda=c16.shape[1], ldc=d)
+        hip.attention(q, k, v, att, B=B, heads=mod.heads, n=n, nk=m, dh=mod.dim_head, ldq=d, ldk=d, ldv=d, bsq=n * d,
+                      bsk=m * d, bsv=m * d, ldo=d, bso=n * d, scale=mod.scale)
+        hip.gemm(att, pk["wo"], out, M=B * n, N=out.shape[1], K=d, lda=d, ldc=out.shape[1], bias=pk["bo"])
+    return out.reshape(B, n, -1)
 
 
 def feedforward_forward(mod, x: torch.Tensor) -> torch.Tensor:

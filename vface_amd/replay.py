@@ -199,7 +199,7 @@ class _StepReplay:
     # Every engine switch that changes the captured launch sequence: part of the graph key, so that toggling one on a live engine
     # does not replay a stale graph (tests/test_host_cpu.py holds every VFACE_* switch of the initialisers against this list)
     _GRAPH_SWITCHES = ("stream32", "fuse_gn", "fuse_ffn", "fuse_front", "fuse_tail", "fuse_post", "fuse_temb", "fuse_out", "concat32",
-                       "interior16", "live_chunks", "share_prefix", "decompose_attn1")
+                       "interior16", "live_chunks", "share_prefix")
 
     def _hook_signature(self):
         """(signature, flows): everything the hooked attn1 layers contribute to the launch sequence -- the HookCfg fields and
