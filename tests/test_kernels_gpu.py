@@ -425,7 +425,7 @@ def test_timestep_embedding_pack_and_ddim():
 
 @pytest.mark.parametrize("mode", ["plain", "replace", "fft", "flow_fix"])
 def test_engine_attn1_sequence_level0_vs_reference_golden(mode):
-    """The hooked attn1 as the engine sequences it (UNetEngine._attn1_qkv_att + _attn1_out, 16-bit output, no residual) at the real
+    """The hooked attn1 as the engine sequences it (UNetEngine._attn1: _attn1_att + _attn1_out, 16-bit output, no residual) at the real
     level-0 shape (d=320, 8 heads, n=4096, F=2) against the reference-generated fixture (strided token slice)."""
     from vface_amd.engine import HookCfg, UNetEngine, plan_fusion
     from vface_amd.packing import pack_qkv
@@ -445,9 +445,47 @@ def test_engine_attn1_sequence_level0_vs_reference_golden(mode):
     cfg = None if mode == "plain" else HookCfg(chunks=3, fusion=mode, flow=flow, split_ratio_fft=0.8, alpha=0.8)
     pl = plan_fusion(cfg, B, n)
     out = torch.empty(B * n, d, dtype=torch.float16, device=DEV)
-    att = eng._attn1_qkv_att(x, torch.empty(B * n, 3 * d, dtype=torch.float16, device=DEV), p, pl, B, n, heads, projected=False)
-    eng._attn1_out(att, p, None, n, out)
+    eng._attn1(x, None, p, pl, None, B, n, heads, out=out)
     assert rel_l2(out.reshape(B, n, d)[:, ::128].cpu().float(), g[mode]) < 1e-3
+
+
+@pytest.mark.parametrize("mode", ["temporal", "adaIn"])
+def test_engine_attn1_staged_plan_is_its_launches_by_hand_split_k_included(mode):
+    """The staged hook modes through ``UNetEngine._attn1`` (a stand-alone attention: no row bias, no residual) at d = 1280, 8 heads,
+    n = 64, B = 6 (three chunks of two frames) == the same launches written out here: the q|k|v projection and the out-projection
+    with ``hip.gemm``'s default split-K (the other plans launch theirs without), the edit kernels, ``qkv_attention`` without maps.
+    This is the smallest shape at which the staged out-projection really splits K (asserted), so a lost flag changes the bits."""
+    h = hip()
+    from vface_amd.engine import HookCfg, UNetEngine, plan_fusion, qkv_attention
+    d, heads, n, B = 1280, 8, 64, 6
+    assert h.load().vface_splitk_workspace_bytes(384, 1280, 1280, 0, 64) > 0
+    dt = torch.float16
+    x = rnd((B * n, d), 1, dt).to(DEV)
+    wqkv, wo = rnd((3 * d, d), 2, dt, 1 / math.sqrt(d)).to(DEV), rnd((d, d), 3, dt, 1 / math.sqrt(d)).to(DEV)
+    bo = rnd((d,), 4, torch.float32, 0.1).to(DEV)
+    eng = UNetEngine(None, dt, device=DEV)
+    p = {"c": d, "wqkv": wqkv, "wo": {"w": wo, "b": bo}, "wlin": {}, "qk_src": None}
+    pl = plan_fusion(HookCfg(chunks=3, fusion=mode), B, n)
+    assert pl["staged"] == mode
+    got = torch.empty(B * n, d, dtype=dt, device=DEV)
+    eng._attn1(x, None, p, pl, None, B, n, heads, out=got)
+
+    Fn = B // 3 * n
+    qkv = torch.empty(B * n, 3 * d, dtype=dt, device=DEV)
+    h.gemm(x, wqkv, qkv, M=B * n, N=3 * d, K=d, lda=d, ldc=3 * d)
+    if mode == "temporal":
+        h.temporal_gauss(qkv, qkv[Fn:], qkv[2 * Fn:], F=B // 3, n=n, C_=2 * d, ld_src=3 * d, fs_src=n * 3 * d, ld_dst=3 * d,
+                         fs_dst=n * 3 * d)
+    else:
+        for col in (0, d):
+            for ch in (1, 2):
+                own = qkv[ch * Fn:(ch + 1) * Fn, col:col + d]
+                h.adain_fusion(qkv[:Fn, col:col + d], own, own, rows=Fn, C_=d, lda=3 * d, ldb=3 * d, ldd=3 * d)
+    att = torch.empty(B * n, d, dtype=dt, device=DEV)
+    qkv_attention(qkv, att, B=B, n=n, d=d, heads=heads)
+    want = torch.empty(B * n, d, dtype=dt, device=DEV)
+    h.gemm(att, wo, want, M=B * n, N=d, K=d, lda=d, ldc=d, bias=bo, rows_per_sample=n)
+    assert torch.isfinite(want.float()).all() and torch.equal(got, want)
 
 
 @pytest.mark.parametrize("N_,cout", [(2, 320), (3, 640)])
@@ -1544,7 +1582,7 @@ def test_attention_wave_count_and_query_tiling_do_not_change_bits(dh, n, B):
 
 
 # ------------------------------------------------------------------ the frame-mixing kernels of the staged hook modes
-# Buffers laid out as engine.staged_attn1 lays them: one qkv buffer [3 F n, 3d], q|k = C_ = 2d columns at ld = 3d, frame stride
+# Buffers laid out as UNetEngine._attn1_att lays them: one qkv buffer [3 F n, 3d], q|k = C_ = 2d columns at ld = 3d, frame stride
 # n 3d, chunk k at rows [k F n, (k + 1) F n).  The whole buffer starts as a sentinel pattern, so a write outside the q|k columns
 # of the target chunks shows.
 # (U32, ulp() and sentinel() live in tests/kernel_bounds.py, shared with test_glue_kernels_gpu.py)
@@ -1643,7 +1681,7 @@ def _adain_bound(dt, a64, b64):
 
 
 def _adain_case(dt, rows, C, a, b):
-    """The engine's call (engine.staged_attn1): a = chunk 0's q (or k) columns, b = dst = chunk k's, in place, ld = 3C, in a buffer
+    """The engine's call (UNetEngine._staged_edit): a = chunk 0's q (or k) columns, b = dst = chunk k's, in place, ld = 3C, in a buffer
     [2 rows, 3C] that starts as a sentinel pattern; the fused slot is the k slot (columns [C, 2C)).  Bound: _adain_bound."""
     h = hip()
     host = sentinel(2 * rows, 3 * C, dt)

@@ -1,10 +1,10 @@
 """Frame sharding on the MI355X box.
 
-* STRICT (gating): every shard of a clip runs through the sharded order of ``UNetEngine._attn1_qkv_att`` (the boundary
+* STRICT (gating): every shard of a clip runs through the sharded order of ``UNetEngine._attn1_att`` (the boundary
   exchange between chunk 1's fused projection and the warp) -- the only code that differs between 1 and N ranks -- one after
   another in ONE process, with an in-memory loop-back exchange (``parallel.LoopbackShard``); each shard's eps must equal the
   unsharded run bit for bit (``torch.equal``), for an even and an uneven split, entered behind the fused front
-  (``_st_front``: what these 64-channel models take by default) and behind the separate launches (``_attn1``).
+  (``_st``'s fused front: what these 64-channel models take by default) and behind the separate launches (``_attn1``).
 * DIAGNOSTIC (non-gating on bit-identity): two PROCESSES time-slicing the one visible GPU, gloo host staging for the
   halo -- a rehearsal of the multi-process control flow.  The production backend is "nccl" (RCCL over xGMI), one
   process per GPU: bench.py --gpus N --fusion flow_fix."""
@@ -85,7 +85,7 @@ def _shard_inputs(total, h, w, f0, fc, dev, sampler_batch=False):
 def test_loopback_shards_equal_unsharded_bit_for_bit(total, world, fuse_front):
     """One process, one GPU: ranks 0..world-1 of the real engine (flow_fix on the input-block attn1) run in order, the
     boundary slabs handed over in memory.  torch.equal against the unsharded run.  ``fuse_front``: the hooked level-0 layers
-    reach the sharded order from ``_st_front`` (True) or from ``_attn1`` (False), unsharded and sharded runs alike."""
+    reach the sharded order behind ``_st``'s fused front (True) or from ``_attn1`` (False), unsharded and sharded runs alike."""
     from vface_amd.ldm.models.diffusion.ddim_w_inv import DDIMSampler
     from vface_amd.ldm.models.diffusion.ddpm import LatentDiffusion
     from vface_amd.ldm.models.pnp_utils import register_spa_attn_injection as reg

@@ -22,7 +22,7 @@ import os
 
 import numpy as np
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
@@ -173,7 +173,7 @@ def sample_map(kind: str, B: int, c: int) -> torch.Tensor:
     if kind == "qk_replace":
         return idx % c
     if kind in ("share_qk", "share_v"):
-        # _st_front_shared with a warp: slot 0 = chunk 1's warped q|k, slot 1 = chunk 0's q|k and the v of chunks 0, 1
+        # the shared rows with a warp (UNetEngine._rows): slot 0 = chunk 1's warped q|k, slot 1 = chunk 0's q|k and the v of chunks 0, 1
         m = torch.where(idx < c, idx + c, idx)            # chunk 0 reads slot 1 (q|k and v)
         if kind == "share_qk":
             m = torch.where((idx >= c) & (idx < 2 * c), idx - c, m)      # chunk 1's q|k: slot 0 (its v stays in slot 1 = itself)
@@ -198,37 +198,15 @@ def qkv_attention(qkv: torch.Tensor, att: torch.Tensor, *, B: int, n: int, d: in
                   scale=float(np.float32(1.0) / np.sqrt(np.float32(dh))), **maps)   # (fp32 arithmetic: it fixes the bits)
 
 
-def staged_attn1(x16: torch.Tensor, wqkv, wo, bo, out, *, B, n, d, heads, mode, rowbias=None, residual=None,
-                 residual32=None, out32=None, chunks: int = 3, edit: Optional[Callable] = None):
-    """Hooked attn1 for fusion modes that edit q,k with their own kernels ("temporal", "adaIn"; pnp_utils.py:145-160):
-    full projection -> edit chunk 1 / chunk 2 q,k in the qkv buffer -> attention -> out-projection.
-    ``edit(qkv, F)``: replaces the built-in edit (a frame-sharded forward: ``UNetEngine._staged_sharded_edit``)."""
-    dev, dt = x16.device, x16.dtype
-    c = B // chunks          # (chunks < 3: the batch came without its last chunk(s), plan_fusion `live`)
-    Fn = c * n
-    qkv = torch.empty(B * n, 3 * d, dtype=dt, device=dev)
-    hip.gemm(x16, wqkv, qkv, M=B * n, N=3 * d, K=x16.shape[1], lda=x16.stride(0), ldc=3 * d)
-    if edit is not None:
-        edit(qkv, c)
-    elif mode == "temporal" and chunks > 1:
-        hip.temporal_gauss(qkv, qkv[Fn:], qkv[2 * Fn:] if chunks > 2 else None, F=c, n=n, C_=2 * d, ld_src=3 * d, fs_src=n * 3 * d,
-                           ld_dst=3 * d, fs_dst=n * 3 * d)
-    elif mode == "temporal":
-        pass
-    elif mode == "adaIn":
-        for col in (0, d):  # q then k
-            for ch in range(1, chunks):
-                own = qkv[ch * Fn:(ch + 1) * Fn, col:col + d]
-                hip.adain_fusion(qkv[:Fn, col:col + d], own, own, rows=Fn, C_=d, lda=3 * d, ldb=3 * d, ldd=3 * d)
-    else:
-        raise ValueError(mode)
-    att = torch.empty(B * n, d, dtype=dt, device=dev)
-    qkv_attention(qkv, att, B=B, n=n, d=d, heads=heads)
-    o = out if out is not None else out32
-    hip.gemm(att, wo, out, M=B * n, N=o.shape[1], K=d, lda=d, ldc=out.stride(0) if out is not None else 0, bias=bo,
-             rowbias=rowbias, rows_per_sample=n, residual=residual, ldr=residual.stride(0) if residual is not None else 0,
-             residual32=residual32, out32=out32)
-    return o
+@dataclass(frozen=True)
+class _Rows:
+    """Where a SpatialTransformer pass keeps its chunks: the whole batch, chunk after chunk, or the ``[A ; C]`` rows of
+    ``UNetEngine._shared_block`` (A stands for chunks 0 AND 1).  Row numbers; built in one place, ``UNetEngine._rows``."""
+    own: tuple       # per chunk: the first of its own rows in the LayerNorm output and in the projections' q|k|v rows
+    qk: tuple        # per chunk: the first row of the attention's q|k|v buffer its fused q|k goes to; None: not needed
+    lead: int        # rows of that buffer in front of the projections' (the slot of a warped chunk 1 that has no rows of its own)
+    maps: tuple      # the attention's sample maps (q|k, v) as ``sample_map`` kinds, None: identity
+    tail: tuple      # per tail launch: (first output row, rows, first attention-output row, first row-bias sample)
 
 
 def _phase_form_pays(hw_in: int, cout: int) -> bool:
@@ -301,6 +279,9 @@ class UNetEngine(_StepReplay):
         # the ~70 vector instructions per 1-KiB patch piece sit in the K-tile period's critical path -- 28.22 vs 27.49 ms per
         # DDIM step (conv 9.46 vs 7.77 ms, gn_apply 0 vs 1.0 ms), DESIGN 4 -- so it is opt-in.
         self.fuse_gn = os.environ.get("VFACE_FUSE_GN", "off")
+        self._halo_k = 0                               # ordinal of the next boundary exchange of this forward (_halo_start)
+        self._a2_lru: Dict[int, tuple] = {}            # (context_projections: a few contexts, most recently used last)
+        self._a2_cache: Optional[tuple] = None         # the entry a graph capture pins in front of them (replay._capture)
         self._init_replay()
         hip.load()
 
@@ -584,31 +565,30 @@ class UNetEngine(_StepReplay):
         return plan_fusion(getattr(attn1, "_vface_cfg", None), N, n, self.halo_hw if self.halo_exchange is not None else None,
                            self.live_chunks)
 
-    def _attn1(self, xln: torch.Tensor, resid: torch.Tensor, p: dict, pl: dict, a2vec: torch.Tensor, N: int, n: int,
-               heads: int) -> torch.Tensor:
-        """``resid`` 16-bit -> 16-bit result; ``resid`` fp32 (the residual stream) -> fp32 result, no 16-bit copy.  ``pl``: ``_hook_plan``."""
+    def _attn1(self, xln: torch.Tensor, resid: Optional[torch.Tensor], p: dict, pl: dict, a2vec: Optional[torch.Tensor], N: int,
+               n: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A hooked attn1 behind the separate launches, every plan ``pl`` (``_hook_plan``): ``_attn1_att``, then ``_attn1_out``.
+        ``resid`` 16-bit -> 16-bit result; ``resid`` fp32 (the residual stream) -> fp32 result, no 16-bit copy; ``resid`` None: a
+        stand-alone attention (``module_exec``), no residual, into the 16-bit ``out``."""
         d = p["c"]
-        s32 = resid.dtype == torch.float32
-        out = None if s32 else self._new(N * n, d)
-        out32 = self._new(N * n, d, torch.float32) if s32 else None
-        res_kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid, "ldr": resid.stride(0)}
-        if pl["staged"]:
-            # frames sharded across ranks: the edit exchanges what it needs from the other ranks (temporal: +-2 frames; adaIn:
-            # the row partials of the global std) between the projection and the attention
-            edit = self._staged_sharded_edit(pl["staged"], n, d, pl["chunks"]) if self.halo_exchange is not None else None
-            kw = {"residual32": resid, "out32": out32} if s32 else {"residual": resid}
-            return staged_attn1(xln, p["wqkv"], p["wo"]["w"], p["wo"]["b"], out, B=N, n=n, d=d, heads=heads,
-                                mode=pl["staged"], rowbias=a2vec, chunks=pl["chunks"], edit=edit, **kw)
-        att = self._attn1_qkv_att(xln, self._new(N * n, 3 * d), p, pl, N, n, heads, projected=False)
-        self._attn1_out(att, p, a2vec, n, out, **res_kw)
-        return out32 if s32 else out
+        res_kw = {}
+        if resid is not None and resid.dtype == torch.float32:
+            res_kw = {"residual32": resid, "out32": self._new(N * n, d, torch.float32)}
+        elif resid is not None:
+            out, res_kw = self._new(N * n, d), {"residual": resid, "ldr": resid.stride(0)}
+        att = self._attn1_att(xln, self._new(N * n, 3 * d), p, pl, N // pl["chunks"], n, heads)
+        self._attn1_out(att, p, pl, a2vec, n, out, **res_kw)
+        return res_kw.get("out32", out)
 
-    def _attn1_out(self, att: torch.Tensor, p: dict, a2vec: torch.Tensor, n: int, out: Optional[torch.Tensor], **res_kw):
-        """The end of a hooked attn1: its out-projection + bias + attn2's row bias + residual as one GEMM without a split-K workspace.
-        ``out`` 16-bit, or None with ``residual32`` / ``out32`` (the fp32 residual stream)."""
+    def _attn1_out(self, att: torch.Tensor, p: dict, pl: dict, a2vec: Optional[torch.Tensor], n: int, out: Optional[torch.Tensor],
+                   **res_kw):
+        """The end of a hooked attn1: its out-projection + bias + attn2's row bias + residual as one GEMM.  ``out`` 16-bit, or None
+        with ``residual32`` / ``out32`` (the fp32 residual stream).  Split-K belongs to the plan: the staged modes ("temporal",
+        "adaIn") launch with it allowed (and do split at d = 1280, n = 64), every other plan without a workspace."""
         d = p["c"]
-        hip.gemm(att, p["wo"]["w"], out, M=att.shape[0], N=d, K=d, lda=d, ldc=out.stride(0) if out is not None else 0, ldw=d,
-                 bias=p["wo"]["b"], rowbias=a2vec, rows_per_sample=n, split_k=False, **res_kw)
+        o = out if out is not None else res_kw["out32"]
+        hip.gemm(att, p["wo"]["w"], out, M=att.shape[0], N=o.shape[1], K=d, lda=d, ldc=out.stride(0) if out is not None else 0, ldw=d,
+                 bias=p["wo"]["b"], rowbias=a2vec, rows_per_sample=n, split_k=pl["staged"] is not None, **res_kw)
 
     def _fused_qk(self, own: torch.Tensor, first: torch.Tensor, wlin: torch.Tensor, dst: torch.Tensor, rows: int, d: int):
         """The dual-source q|k projection of a linear hook fusion: ``[own | first]`` (K = 2d; ``first``: chunk 0's rows
@@ -624,36 +604,63 @@ class UNetEngine(_StepReplay):
                       fs_dst=n * 3 * d, alpha=pl["alpha"], prev=halo, ld_prev=2 * d,
                       flow_prev=self.halo_flow if halo is not None else None)
 
-    def _attn1_qkv_att(self, ln: Optional[torch.Tensor], qkv: torch.Tensor, p: dict, pl: dict, N: int, n: int, heads: int, *,
-                       projected: bool) -> torch.Tensor:
-        """A hooked attn1 (pnp_utils.py:94-287) from the LayerNorm output ``ln`` to the attention output ``[N n, d]`` -- the one launch
-        sequence of every non-staged plan (``_attn1_out`` or a fused tail ends it):
+    def _rows(self, pl: dict, F_: int, n: int, L: Optional[int] = None) -> _Rows:
+        """The row layout of a pass under plan ``pl`` with F_ frames of n tokens per chunk: the whole batch, or (``L``: its chunks)
+        the ``[A ; C]`` rows of ``_shared_block``.  Shared, the attention runs over [A ; C] as it stands -- chunk 1's FSAI(q0, q0)
+        is q0 -- unless the flow warp makes chunk 1's q|k differ from chunk 0's: then over three sample slots -- slot 0 = the warped
+        q|k of chunk 1, slot 1 = A (q|k of chunk 0, v of chunks 0 and 1), slot 2 = C -- addressed through the sample maps.  Its
+        tail, where attn2's row bias separates chunk 0 from chunk 1, is two launches: rows A with chunk 0's bias -> chunk 0, rows
+        [A ; C] with chunk 1's and 2's -> chunks 1, 2."""
+        Fn = F_ * n
+        qk_map = "qk_replace" if pl["fusion"] == hip.FUSION_REPLACE else None
+        if L is None:
+            own = tuple(ch * Fn for ch in range(pl["chunks"]))
+            return _Rows(own, own, 0, (qk_map, "v_fixed" if pl["v_fixed"] else None), ((0, pl["chunks"] * Fn, 0, 0),))
+        warp = pl["warp_hw"] is not None
+        assert (L == 3 or not warp) and not pl["v_fixed"]
+        lead = Fn if warp else 0
+        return _Rows((0, 0, Fn)[:L], (None, 0 if warp else None, lead + Fn)[:L], lead,
+                     ("share_qk", "share_v") if warp else (qk_map, None), ((0, Fn, 0, 0), (Fn, (L - 1) * Fn, lead, F_)))
+
+    def _attn1_att(self, ln: Optional[torch.Tensor], buf: torch.Tensor, p: dict, pl: dict, F_: int, n: int, heads: int,
+                   lay: Optional[_Rows] = None, projected: bool = False) -> torch.Tensor:
+        """A hooked attn1 (pnp_utils.py:94-287) from the LayerNorm output ``ln`` through the q|k|v buffer ``buf`` to the attention
+        output -- the one launch sequence of every plan, on the whole batch and on the shared rows (``lay``: ``_rows``, default the
+        whole batch of F_ frames per chunk); ``_attn1_out`` or a fused tail ends it:
           no hook      one q|k|v projection over the batch, attention;
           replace      chunk 0's q|k|v and the other chunks' v, attention with every chunk reading chunk 0's q, k (scores once per
                        frame where the kernel has that form, else through the q|k sample map);
           linear       (fft / flow_fix / fft_vfixed / mix) the same two projections, then chunk k >= 1's q|k as ONE dual-source GEMM
-                       ``[own | chunk 0] @ wlin`` (``_fused_qk``); flow_fix warps chunk 1's along the flow on the way into ``qkv``
-                       (``_warp``); fft_vfixed reads v through the first-frame map.
-        ``projected``: the fused front already wrote chunk 0's q|k|v and the other chunks' v into ``qkv`` (``_st_front``; ``ln`` is then
-        only needed by the linear fusions); otherwise those two GEMMs (one over the whole batch when no hook edits it) are issued here.
+                       ``[own | chunk 0] @ wlin`` (``_fused_qk``); flow_fix warps chunk 1's along the flow on the way into ``buf``
+                       (``_warp``); fft_vfixed reads v through the first-frame map;
+          staged       (temporal / adaIn, pnp_utils.py:145-160: edits that are neither a sample map nor a folded weight) the full
+                       projection with split-K allowed, the edit of chunk k >= 1's q, k by its own kernels (``_staged_edit``), attention.
+        ``projected``: the fused front already wrote chunk 0's q|k|v and the other chunks' v (``_st``; ``ln`` is then only needed by
+        the linear fusions); otherwise those GEMMs (one over the whole batch when no hook edits it) are issued here, K = ``ln``'s width.
         Frames sharded across ranks and a flow warp: the one-neighbour boundary exchange sits between chunk 1's
-        fused projection and the warp, and the launches that do not depend on it are issued behind its start."""
+        fused projection and the warp, and the launches that do not depend on it are issued behind its start.  This order decides
+        whether the ranks' calls pair up and where the hipGraph segments are cut (``replay._GraphSegments``)."""
         d = p["c"]
         fusion, chunks = pl["fusion"], pl["chunks"]
-        F_ = N // chunks
         Fn = F_ * n
+        lay = lay or self._rows(pl, F_, n)
+        qkv = buf[lay.lead:]
 
-        def project():
+        def project(split_k=False):
             if projected:
                 return
-            g = lambda a, w, o, M, Nn: hip.gemm(a, w, o, M=M, N=Nn, K=d, lda=ln.stride(0), ldc=3 * d, ldw=d, split_k=False)
+            M, K = qkv.shape[0], ln.shape[1]
+            g = lambda a, w, o, rows, cols: hip.gemm(a, w, o, M=rows, N=cols, K=K, lda=ln.stride(0), ldc=3 * d, ldw=K, split_k=split_k)
             if fusion == hip.FUSION_NONE:
-                g(ln, p["wqkv"], qkv, N * n, 3 * d)
+                g(ln, p["wqkv"], qkv, M, 3 * d)
             else:
                 g(ln, p["wqkv"], qkv, Fn, 3 * d)                                         # chunk 0: q, k, v as projected
-                g(ln[Fn:], p["wqkv"][2 * d:], qkv[Fn:, 2 * d:], N * n - Fn, d)          # other chunks: v only, the fusion writes their q, k
+                g(ln[Fn:], p["wqkv"][2 * d:], qkv[Fn:, 2 * d:], M - Fn, d)              # other chunks: v only, the fusion writes their q, k
 
-        if fusion != hip.FUSION_LINEAR:
+        if pl["staged"]:
+            project(split_k=True)
+            self._staged_edit(pl["staged"], qkv, F_, n, d, chunks)
+        elif fusion != hip.FUSION_LINEAR:
             project()
         else:
             wlin = self._wlin(p, *pl["wlin"])
@@ -661,8 +668,12 @@ class UNetEngine(_StepReplay):
             # every rank of a sharded clip takes part in the boundary exchange, a one-frame shard (no local field) too
             sharded = warp and self.halo_exchange is not None
             T = self._new(Fn, 2 * d) if warp else None
-            fused = lambda ch: self._fused_qk(ln[ch * Fn:], ln, wlin, T if (warp and ch == 1) else qkv[ch * Fn:(ch + 1) * Fn, :2 * d],
-                                              Fn, d)
+
+            def fused(ch):          # (own rows, then the structure rows = chunk 0's LayerNorm output)
+                if lay.qk[ch] is not None:
+                    dst = T if (warp and ch == 1) else buf[lay.qk[ch]:lay.qk[ch] + Fn, :2 * d]
+                    self._fused_qk(ln[lay.own[ch]:], ln, wlin, dst, Fn, d)
+
             halo = None
             if sharded:
                 fused(1)
@@ -675,27 +686,25 @@ class UNetEngine(_StepReplay):
             if sharded:
                 halo = self._halo_finish(handle)
             if warp:
-                self._warp(T, qkv[Fn:2 * Fn, :2 * d], pl, F_, n, d, halo)
-        att = self._new(N * n, d)
-        v_map = self._map("v_fixed", N, F_) if pl["v_fixed"] else None
-        hc = pl["hook_chunks"]
-        if fusion == hip.FUSION_REPLACE and chunks > 1 and hip.load().vface_attention_shared_scores_supported(d // heads, hc):
-            # every chunk attends with q,k of chunk 0 (pnp_utils.py:136-142): softmax once per frame, one value set per chunk
-            qkv_attention(qkv, att, B=F_, n=n, d=d, heads=heads, v_map=v_map, v_sets=hc, v_sets_live=chunks, set_stride=F_)
+                self._warp(T, buf[lay.qk[1]:lay.qk[1] + Fn, :2 * d], pl, F_, n, d, halo)
+        att = self._new(buf.shape[0], d)
+        S, hc = buf.shape[0] // n, pl["hook_chunks"]
+        qk_map, v_map = (self._map(kind, S, F_) if kind else None for kind in lay.maps)
+        if fusion == hip.FUSION_REPLACE and S > F_ and hip.load().vface_attention_shared_scores_supported(d // heads, hc):
+            # every chunk attends with q,k of chunk 0 (pnp_utils.py:136-142): softmax once per frame, one value set per chunk there
+            qkv_attention(buf, att, B=F_, n=n, d=d, heads=heads, v_map=v_map, v_sets=hc, v_sets_live=S // F_, set_stride=F_)
         else:
-            qkv_attention(qkv, att, B=N, n=n, d=d, heads=heads,
-                          qk_map=self._map("qk_replace", N, F_) if fusion == hip.FUSION_REPLACE else None, v_map=v_map)
+            qkv_attention(buf, att, B=S, n=n, d=d, heads=heads, qk_map=qk_map, v_map=v_map)
         return att
 
-    def _block(self, t0: torch.Tensor, p: dict, attn1, a2vec: torch.Tensor, N: int, n: int, hw, want32: bool = False):
+    def _block(self, t0: torch.Tensor, p: dict, pl: dict, heads: int, a2vec: torch.Tensor, N: int, n: int, want32: bool = False):
         """BasicTransformerBlock._forward (attention.py:239-243) on the block's running sum ``t0`` ``[N*n, c]`` (fp32 when the
         residual stream is on, else 16-bit): returns its last value as the 16-bit operand of the next projection (and, if
-        ``want32``, as fp32 too).  ``a2vec``: the single-token cross-attention's contribution, fp32 ``[N, c]``."""
+        ``want32``, as fp32 too).  ``pl``: ``_hook_plan``; ``a2vec``: the single-token cross-attention's contribution, fp32 ``[N, c]``."""
         c, M = p["c"], t0.shape[0]
         ln = self._new(M, c)
         hip.layernorm(t0, p["ln1"][0], p["ln1"][1], ln, M=M, C_=c, ldx=c, ldy=c)
-        t1 = self._attn1(ln, t0, p, self._hook_plan(attn1, N, n), a2vec, N, n, attn1.heads)
-        return self._ffn(t1, p, n, want32)
+        return self._ffn(self._attn1(ln, t0, p, pl, a2vec, N, n, heads), p, n, want32)
 
     def _ffn(self, t1: torch.Tensor, p: dict, n: int, want32: bool = False):
         """``x + ff(norm3(x))`` (attention.py:243) on the block's running sum ``t1`` (fp32 with the residual stream, else 16-bit)."""
@@ -714,49 +723,10 @@ class UNetEngine(_StepReplay):
         self._gemm(ff, p["ff2"], t2, hw=n, out32=t2_32, **self._resid(t1))
         return (t2, t2_32) if want32 else t2
 
-    def _st_front(self, x: Act, p: dict, attn1, a2vec: torch.Tensor, post=None):
-        """The SpatialTransformer up to and including its transformer block, with the FRONT -- GroupNorm-apply, proj_in,
-        LayerNorm (norm1) and attn1's projection -- as ONE launch (csrc/stfront.hip) instead of four: needs the fp32 carrier
-        and the producer's column statistics of ``x`` and a width the kernel takes.  Returns the block's last running sum
-        (16-bit, proj_out's operand), or None when this layer does not qualify (the caller then runs the separate launches), or
-        True when ``post = (out16 | None, colstats | None, out32)`` was given and the tail launch also ran proj_out + ``x`` into it.
-        What follows the front is the hooked attn1 behind its projections (``_attn1_qkv_att`` with ``projected=True``: the
-        dual-source projections of the hook's linear fusions read the LayerNorm output the front also writes then), the
-        out-projection into the fp32 stream, then norm3 + FeedForward."""
-        c, N, n, M = p["c"], x.N, x.hw, x.M
-        if not self.fuse_front or p.get("front_w") is None or x.t32 is None or x.cs is None or not self._front_ok(M, c, n):
-            return None
-        pl = self._hook_plan(attn1, N, n)
-        if pl["staged"]:
-            return None      # "temporal" / "adaIn" edit a full q,k,v buffer with their own kernels
-        d, fusion = c, pl["fusion"]
-        Fn = N // pl["chunks"] * n
-        ab = hip.groupnorm_coeffs_from_cols(x.cs, p["gn"][0], p["gn"][1], nimg=N, hw=n, C_=c, eps=1e-6)
-        t0 = self._new(M, c, torch.float32)
-        qkv = self._new(M, 3 * d)
-        ln = self._new(M, c) if fusion == hip.FUSION_LINEAR else None
-        hip.st_front(x.t32, ab, p["front_w"], p["proj_in"]["b"], p["ln1"][0], p["ln1"][1], t0, qkv, M=M, C_=c, hw=n, NQ=3 * d,
-                     rows_full=M if fusion == hip.FUSION_NONE else Fn, nq_lo=0 if fusion == hip.FUSION_NONE else 2 * d, ln=ln)
-        att = self._attn1_qkv_att(ln, qkv, p, pl, N, n, attn1.heads, projected=True)
-        if self.fuse_tail and p.get("tail_w") is not None and n % 128 == 0 and self._ffn_ok(M, c):
-            # to_out + bias + attn2's row bias + residual -> norm3 -> FeedForward -> + x in ONE launch: t1 never exists in HBM
-            if self.fuse_post and p.get("tail_post") and post is not None and (post[0] is not None or post[2] is not None):
-                hip.attn_out_ffn_proj_fused(att, t0, a2vec, p["tail_w"], p["wo"]["b"], p["ln3"][0], p["ln3"][1], p["ff1"]["b"], p["ff2p"],
-                                            p["ff2"]["b"], p["proj_out"]["b"], x.t32, post[0], post[2], post[1], M=M, C_=c,
-                                            rows_per_sample=n)
-                return True
-            t2 = self._new(M, c)
-            hip.attn_out_ffn_fused(att, t0, a2vec, p["tail_w"], p["wo"]["b"], p["ln3"][0], p["ln3"][1], p["ff1"]["b"], p["ff2p"],
-                                   p["ff2"]["b"], t2, M=M, C_=c, rows_per_sample=n)
-            return t2
-        t1 = self._new(M, c, torch.float32)
-        self._attn1_out(att, p, a2vec, n, None, residual32=t0, out32=t1)
-        return self._ffn(t1, p, n)
-
     # ------------------------------------------------------------------ chunks 0 and 1 of the sampler's batch share their prefix
-    def _share_ok(self, block, h: Act) -> bool:
+    def _share_ok(self, block, h: Act, pl: dict) -> bool:
         """Can input block 1 -- ``[ResBlock, SpatialTransformer]`` -- of a ``[x ; x ; inv_t]`` batch run its chunk-0 / chunk-1
-        prefix once (``_shared_block``)?  Needs the whole batch (no dead-branch elimination), the fused front and the fused
+        prefix once (``_shared_block``)?  ``pl``: the ``_hook_plan`` of its attn1 over the whole batch.  Needs the whole batch (no dead-branch elimination), the fused front and the fused
         tail with ``proj_out`` behind it (the launches whose operands can be handed over as row ranges), and a hook mode whose
         chunk-1 edit is either the identity on identical inputs (none, ``replace``, ``fft``, ``mix``) or the flow warp."""
         L = 3 if self.live_chunks is None else self.live_chunks      # chunks in the batch: 3, or 2 = [uncond ; cond] (dead-branch elimination)
@@ -778,10 +748,6 @@ class UNetEngine(_StepReplay):
         cfg = getattr(attn1, "_vface_cfg", None)
         if cfg is not None and cfg.switch_on and cfg.chunks != 3:
             return False
-        try:
-            pl = self._hook_plan(attn1, h.N, n)
-        except Exception:
-            return False          # (the whole-batch path raises it where the caller expects it)
         if pl["staged"] or pl["v_fixed"]:
             return False
         if L == 2:
@@ -791,15 +757,17 @@ class UNetEngine(_StepReplay):
             return pl["fusion"] == hip.FUSION_NONE or (pl["fusion"] == hip.FUSION_LINEAR and pl["warp_hw"] is None)
         return pl["fusion"] in (hip.FUSION_NONE, hip.FUSION_REPLACE, hip.FUSION_LINEAR)
 
-    def _shared_block(self, block, h: Act, out, emb_all: torch.Tensor, a2_all: torch.Tensor) -> Act:
+    def _shared_block(self, block, h: Act, out, emb_all: torch.Tensor, a2_all: torch.Tensor, pl: Optional[dict] = None) -> Act:
         """Input block 1 of the sampler's ``[uncond ; cond ; recon]`` batch (ddim_w_inv.py:632-655: ``x_in = cat([x, x, inv_t])``,
         ``t_in = cat([t] * 3)``): the ResBlock and everything of the SpatialTransformer in front of attn2's row bias see the same
         numbers for chunks 0 and 1, and every kernel here is batch-invariant -- so they run on the LAST 2F samples (a contiguous
-        row range of the 3F-sample buffers) and chunk 0 reads chunk 1's rows.  ``h``: input block 0's output over all 3F samples
-        (the skip connection needs it whole).  Chunks 0 and 2 come out bit-identical to the whole-batch launches; chunk 1 too
+        row range of the 3F-sample buffers) and chunk 0 reads chunk 1's rows: ``_st`` on the ``[A ; C]`` row layout (``_rows``).
+        ``h``: input block 0's output over all 3F samples (the skip connection needs it whole); ``pl``: the plan ``_share_ok`` was
+        asked with.  Chunks 0 and 2 come out bit-identical to the whole-batch launches; chunk 1 too
         under ``flow_fix`` / ``replace`` / no hook; under ``fft`` / ``mix`` its q,k ARE chunk 0's (what the reference's
         ``combine_fft_high_low(q0, q1)`` returns for q1 = q0 up to its FFT's fp32 rounding, face_swap_utils.py:425-464) instead of
-        the folded-weight projection of the same rows."""
+        the folded-weight projection of the same rows.  With two live chunks the batch is [uncond ; cond] alone and the rows are A
+        only (``_share_ok`` admits the hook modes that leave chunk 1 equal to chunk 0 here)."""
         P = self._packed
         (_, pre_r, _), (_, pre_s, mod) = block
         L = 3 if self.live_chunks is None else self.live_chunks
@@ -808,75 +776,14 @@ class UNetEngine(_StepReplay):
         hv = Act(h.t[Fn:] if h.t is not None else None, (L - 1) * F_, h.H, h.W, h.cs[Fn // 64:], h.t32[Fn:])
         co = P[pre_r]["conv2"]["cout"]
         r = self._res(hv, P[pre_r], emb_all[F_:], self._new_target(hv.M, co, hv.hw, need16=False))
-        p = P[pre_s]
-        a, b = p["a2_slice"]
-        self._st_front_shared(r, p, mod.transformer_blocks[0].attn1, a2_all[:, a:b], out, F_, L)
+        self._st(r, P[pre_s], mod, a2_all, out, pl, shared=L)
         return Act(out[0], h.N, h.H, h.W, out[1], out[2])
-
-    def _st_front_shared(self, x: Act, p: dict, attn1, a2vec: torch.Tensor, post, F_: int, L: int = 3) -> None:
-        """``_st_front`` for ``_shared_block``: ``x`` holds the 2F samples [A ; C] -- A stands for chunks 0 AND 1, C is chunk 2 --,
-        ``a2vec`` / ``post`` cover all 3F.  Front, dual-source projections and (hook permitting) attention on 2F; the tail, where
-        attn2's row bias separates chunk 0 from chunk 1, as two launches: rows A with chunk 0's bias -> chunk 0, rows [A ; C]
-        with chunk 1's and 2's -> chunks 1, 2.  ``L = 2``: the batch is [uncond ; cond] alone, ``x`` holds A only (``_share_ok``
-        admits the hook modes that leave chunk 1 equal to chunk 0 here)."""
-        c, n = p["c"], x.hw
-        d, heads = c, attn1.heads
-        Fn = F_ * n
-        M2, M3 = (L - 1) * Fn, 3 * Fn
-        pl = self._hook_plan(attn1, L * F_, n)
-        fusion = pl["fusion"]
-        warp = pl["warp_hw"] is not None
-        assert L == 3 or not warp
-        sharded = warp and self.halo_exchange is not None
-        ab = hip.groupnorm_coeffs_from_cols(x.cs, p["gn"][0], p["gn"][1], nimg=(L - 1) * F_, hw=n, C_=c, eps=1e-6)
-        t0 = self._new(M2, c, torch.float32)
-        # with a warp, chunk 1's q|k differ from chunk 0's: the attention then runs over three sample slots -- slot 0 = the warped
-        # q|k of chunk 1, slot 1 = A (q|k of chunk 0, v of chunks 0 and 1), slot 2 = C -- addressed through the sample maps
-        qkv3 = self._new(M3, 3 * d) if warp else None
-        qkv = qkv3[Fn:] if warp else self._new(M2, 3 * d)
-        ln = self._new(M2, c) if (fusion == hip.FUSION_LINEAR and L == 3) else None
-        hip.st_front(x.t32, ab, p["front_w"], p["proj_in"]["b"], p["ln1"][0], p["ln1"][1], t0, qkv, M=M2, C_=c, hw=n, NQ=3 * d,
-                     rows_full=M2 if fusion == hip.FUSION_NONE else Fn, nq_lo=0 if fusion == hip.FUSION_NONE else 2 * d, ln=ln)
-        if fusion == hip.FUSION_LINEAR and L == 3:
-            wlin = self._wlin(p, *pl["wlin"])
-            # (own rows, then the structure rows = A, chunk 0's LayerNorm output)
-            if warp:
-                T = self._new(Fn, 2 * d)
-                self._fused_qk(ln, ln, wlin, T, Fn, d)                             # chunk 1 (its own rows are A's)
-                halo = None
-                if sharded:
-                    handle = self._halo_start(T[(F_ - 1) * n:])
-                self._fused_qk(ln[Fn:], ln, wlin, qkv[Fn:, :2 * d], Fn, d)         # chunk 2
-                if sharded:
-                    halo = self._halo_finish(handle)
-                self._warp(T, qkv3[:Fn, :2 * d], pl, F_, n, d, halo)
-            else:
-                self._fused_qk(ln[Fn:], ln, wlin, qkv[Fn:, :2 * d], Fn, d)         # chunk 2; chunk 1's FSAI(q0, q0) is q0
-        if warp:
-            att = self._new(M3, d)
-            qkv_attention(qkv3, att, B=3 * F_, n=n, d=d, heads=heads, qk_map=self._map("share_qk", 3 * F_, F_),
-                          v_map=self._map("share_v", 3 * F_, F_))
-            att_0, att_12 = att, att[Fn:]
-        else:
-            att = self._new(M2, d)
-            if fusion == hip.FUSION_REPLACE and hip.load().vface_attention_shared_scores_supported(d // heads, 3):
-                qkv_attention(qkv, att, B=F_, n=n, d=d, heads=heads, v_sets=3, v_sets_live=2, set_stride=F_)
-            else:
-                qkv_attention(qkv, att, B=(L - 1) * F_, n=n, d=d, heads=heads,
-                              qk_map=self._map("qk_replace", 2 * F_, F_) if fusion == hip.FUSION_REPLACE else None)
-            att_0, att_12 = att, att
-        o16, cs, o32 = post
-        for r0, rows, a_, s0 in ((0, Fn, att_0, 0), (Fn, (L - 1) * Fn, att_12, F_)):
-            hip.attn_out_ffn_proj_fused(a_, t0, a2vec[s0:], p["tail_w"], p["wo"]["b"], p["ln3"][0], p["ln3"][1], p["ff1"]["b"], p["ff2p"],
-                                        p["ff2"]["b"], p["proj_out"]["b"], x.t32, o16[r0:] if o16 is not None else None,
-                                        o32[r0:] if o32 is not None else None, cs[r0 // 64:] if cs is not None else None,
-                                        M=rows, C_=c, rows_per_sample=n)
 
     def _halo_start(self, tail: torch.Tensor, kind: str = "exchange"):
         """``halo_exchange.start_exchange`` (``kind`` "temporal" / "gather": ``start_temporal`` / ``start_gather``) with the
         exchange's ordinal inside this forward stated first (FrameShard.set_index)."""
         ex = self.halo_exchange
-        k = getattr(self, "_halo_k", 0)
+        k = self._halo_k
         self._halo_k = k + 1
         if hasattr(ex, "set_index"):
             ex.set_index(k)
@@ -894,49 +801,46 @@ class UNetEngine(_StepReplay):
             ev.append((e0, e1))
         return got
 
-    def _staged_sharded_edit(self, mode: str, n: int, d: int, chunks: int):
-        """The q|k edit of ``staged_attn1`` on a frame shard (``halo_exchange``: this rank holds global frames [first, first + F)
-        of ``total``), as ``edit(qkv, F)``: the same kernels on the same numbers as the unsharded edit, with the exchange between
-        the projection and the edit -- hence the unsharded rows, bit for bit.
+    def _staged_edit(self, mode: str, qkv: torch.Tensor, F_: int, n: int, d: int, chunks: int):
+        """The q|k edit of the staged hook modes in the projected ``qkv`` buffer ``[chunks F_ n, 3d]`` (pnp_utils.py:145-160): chunk
+        k >= 1's q, k from chunk 0's and its own (``chunks`` < 3: the batch came without its last chunk(s), ``plan_fusion`` ``live``).
+        temporal: a 5-tap Gaussian over the frames; adaIn: per-token AdaIN with the global unbiased std, q then k.
+        On a frame shard (``halo_exchange``: this rank holds global frames [first, first + F_) of ``total``) the same kernels run on
+        the same numbers, with an exchange in front of the edit -- hence the unsharded rows, bit for bit:
         temporal: chunk 0's first two and last two frames go to the other ranks, the two frames before and after the shard come
           back (``start_temporal``), and the halo form of the Gaussian reads them (``vface_temporal_gauss_halo``).
         adaIn: every (q | k, chunk) pair's row partials (``vface_adain_rows``) are gathered over the ranks in ONE exchange
           (``start_gather``: global row order), then each pair's global std and scale (``vface_adain_reduce_scale``)."""
-        ex = self.halo_exchange
-        first, total = ex.first, ex.total
-
-        def temporal(qkv, F_):
-            if chunks < 2:
-                return                              # (chunk 0 alone: nothing to smooth, nothing to exchange -- on every rank)
-            Fn, lo = F_ * n, min(F_, 2)
+        if mode not in ("temporal", "adaIn"):
+            raise ValueError(mode)
+        Fn, ex = F_ * n, self.halo_exchange
+        pairs = [(col, ch) for col in (0, d) for ch in range(1, chunks)] if mode == "adaIn" else []     # q then k
+        own = lambda col, ch: qkv[ch * Fn:(ch + 1) * Fn, col:col + d]
+        if chunks < 2:
+            return                                  # (chunk 0 alone: nothing to edit, nothing to exchange -- on every rank)
+        if mode == "temporal" and ex is None:
+            hip.temporal_gauss(qkv, qkv[Fn:], qkv[2 * Fn:] if chunks > 2 else None, F=F_, n=n, C_=2 * d, ld_src=3 * d, fs_src=n * 3 * d,
+                               ld_dst=3 * d, fs_dst=n * 3 * d)
+        elif mode == "temporal":
+            lo = min(F_, 2)
             edges = self._new(4 * n, 2 * d)
             hip.copy2d(qkv, edges, rows=lo * n, cols=2 * d, ld_src=3 * d, ld_dst=2 * d)
             hip.copy2d(qkv[(F_ - lo) * n:], edges[(4 - lo) * n:], rows=lo * n, cols=2 * d, ld_src=3 * d, ld_dst=2 * d)
             halo = self._halo_finish(self._halo_start(edges.view(4, n, 2 * d), "temporal")).reshape(4 * n, 2 * d)
-            hip.temporal_gauss_halo(qkv, halo if first > 0 else None, halo[2 * n:] if first + F_ < total else None, qkv[Fn:],
-                                    qkv[2 * Fn:] if chunks > 2 else None, F=F_, first=first, F_total=total, n=n, C_=2 * d,
+            hip.temporal_gauss_halo(qkv, halo if ex.first > 0 else None, halo[2 * n:] if ex.first + F_ < ex.total else None, qkv[Fn:],
+                                    qkv[2 * Fn:] if chunks > 2 else None, F=F_, first=ex.first, F_total=ex.total, n=n, C_=2 * d,
                                     ld_src=3 * d, fs_src=n * 3 * d, ld_dst=3 * d, fs_dst=n * 3 * d, ld_halo=2 * d, fs_halo=n * 2 * d)
-
-        def adain(qkv, F_):
-            pairs = [(col, ch) for col in (0, d) for ch in range(1, chunks)]      # (the unsharded edit's order)
-            if not pairs:
-                return
-            Fn = F_ * n
+        elif ex is None:
+            for col, ch in pairs:
+                hip.adain_fusion(qkv[:Fn, col:col + d], own(col, ch), own(col, ch), rows=Fn, C_=d, lda=3 * d, ldb=3 * d, ldd=3 * d)
+        else:
             part = torch.empty(len(pairs), Fn, 2, dtype=torch.float64, device=qkv.device)
             ws = [torch.empty(hip.adain_rows_workspace_bytes(Fn, d), dtype=torch.uint8, device=qkv.device) for _ in pairs]
             for i, (col, ch) in enumerate(pairs):
-                own = qkv[ch * Fn:(ch + 1) * Fn, col:col + d]
-                hip.adain_rows(qkv[:Fn, col:col + d], own, part[i], ws[i], rows=Fn, C_=d, lda=3 * d, ldb=3 * d)
+                hip.adain_rows(qkv[:Fn, col:col + d], own(col, ch), part[i], ws[i], rows=Fn, C_=d, lda=3 * d, ldb=3 * d)
             glob = self._halo_finish(self._halo_start(part, "gather"))
             for i, (col, ch) in enumerate(pairs):
-                hip.adain_reduce_scale(glob[i], ws[i], qkv[ch * Fn:(ch + 1) * Fn, col:col + d], partial_rows=glob.shape[1], rows=Fn,
-                                       C_=d, ldd=3 * d)
-
-        if mode == "temporal":
-            return temporal
-        if mode == "adaIn":
-            return adain
-        raise ValueError(mode)
+                hip.adain_reduce_scale(glob[i], ws[i], own(col, ch), partial_rows=glob.shape[1], rows=Fn, C_=d, ldd=3 * d)
 
     def _supported(self, rule, *shape) -> bool:
         """A host-side shape rule of the library (``hip.*_supported``) per shape, asked once (a ctypes call per block per forward
@@ -953,37 +857,72 @@ class UNetEngine(_StepReplay):
     def _front_ok(self, M: int, c: int, n: int) -> bool:
         return self._supported(hip.st_front_supported, M, c, n)
 
-    def _st(self, x: Act, p: dict, mod, a2_all: torch.Tensor, tgt) -> Act:
-        """SpatialTransformer.forward + BasicTransformerBlock._forward (attention.py:278-289, 239-243).
+    def _st(self, x: Act, p: dict, mod, a2_all: torch.Tensor, tgt, pl: Optional[dict] = None, shared: Optional[int] = None) -> Act:
+        """SpatialTransformer.forward + BasicTransformerBlock._forward (attention.py:278-289, 239-243): the one walk of the layer.
         With the fp32 residual stream the block's running sum (``x`` after proj_in, after attn1 + attn2) exists in fp32
-        only -- LayerNorm and the next residual add read that; its last value feeds proj_out as a 16-bit operand."""
-        N, n, c = x.N, x.hw, p["c"]
+        only -- LayerNorm and the next residual add read that; its last value feeds proj_out as a 16-bit operand.
+        The FRONT -- GroupNorm-apply, proj_in, LayerNorm (norm1) and attn1's projection -- is ONE launch (csrc/stfront.hip) where
+        ``x`` has the fp32 carrier and its producer's column statistics, the kernel takes the width and the hook plan is not a
+        staged one (those edit a full q,k,v buffer); else the separate launches and ``_block``.  Behind the fused front come the
+        hooked attn1 behind its projections (``_attn1_att``; the dual-source projections of the hook's linear fusions read the
+        LayerNorm output the front also writes then) and one of three tails: attn1's out-projection + norm3 + FeedForward +
+        proj_out + ``x`` in one launch, the same without proj_out, or ``_attn1_out`` + ``_ffn``.
+        ``pl``: the layer's ``_hook_plan`` where the caller has it already.  ``shared``: ``x`` holds the [A ; C] rows of a
+        ``_shared_block`` of that many chunks, ``a2_all`` / ``tgt`` cover all of them (``_share_ok`` has said that the fused front
+        and the one-launch tail apply)."""
+        attn1 = mod.transformer_blocks[0].attn1
+        n, c, M = x.hw, p["c"], x.M
+        N = x.N if shared is None else x.N // (shared - 1) * shared
+        pl = pl or self._hook_plan(attn1, N, n)
+        F_ = N // (shared or pl["chunks"])
+        lay = self._rows(pl, F_, n, shared)
+        a, b = p["a2_slice"]
+        a2vec = a2_all[:, a:b]
         s32 = self.stream32 and c % 8 == 0
-        a, b = p["a2_slice"]
-        t2 = None
-        if s32:
-            tgt = self._new_target(x.M, c, x.hw) if tgt is None else tgt
-            t2 = self._st_front(x, p, mod.transformer_blocks[0].attn1, a2_all[:, a:b], post=tgt)
-        if t2 is not None:
-            out, cs, o32 = tgt
-            if t2 is not True:
-                self._gemm(t2, p["proj_out"], out, colstats=cs, hw=x.H * x.W, out32=o32, **self._resid(x))
-            return Act(out, x.N, x.H, x.W, cs, o32)
-        g = self._gn(x, p["gn"], 1e-6, False)
-        # interior16: the block's INTERIOR running sums (t0 after proj_in, t1 after attention) of the 640- / 1280-channel blocks in 16
-        # bits -- 12 B per element less through HBM per block (proj_in, two LayerNorms, to_out's residual in and out, ff.net[2]'s
-        # residual); the main residual stream (x_in + proj_out) stays fp32.  Emulated cost on the whole UNet: 1.2400e-3 vs 1.2236e-3
-        # (tests/precision_budget.py `si_min_c`; the level-0 blocks, where it would cost 4x that, keep t1 in registers anyway)
-        wide = s32 and not (self.interior16 and c >= 640)
-        t0 = self._new(x.M, c, torch.float32 if wide else None)
-        if wide:
-            self._gemm(g.t, p["proj_in"], None, hw=x.H * x.W, out32=t0)
+        out, cs, o32 = self._new_target(M, c, n) if tgt is None else tgt
+        fusion = pl["fusion"]
+        if s32 and self.fuse_front and p.get("front_w") is not None and x.t32 is not None and x.cs is not None and \
+                self._front_ok(M, c, n) and not pl["staged"]:
+            ab = hip.groupnorm_coeffs_from_cols(x.cs, p["gn"][0], p["gn"][1], nimg=x.N, hw=n, C_=c, eps=1e-6)
+            t0 = self._new(M, c, torch.float32)
+            buf = self._new(lay.lead + M, 3 * c)
+            ln = self._new(M, c) if fusion == hip.FUSION_LINEAR and any(r is not None for r in lay.qk[1:]) else None
+            hip.st_front(x.t32, ab, p["front_w"], p["proj_in"]["b"], p["ln1"][0], p["ln1"][1], t0, buf[lay.lead:], M=M, C_=c, hw=n,
+                         NQ=3 * c, rows_full=M if fusion == hip.FUSION_NONE else F_ * n, nq_lo=0 if fusion == hip.FUSION_NONE else 2 * c,
+                         ln=ln)
+            att = self._attn1_att(ln, buf, p, pl, F_, n, attn1.heads, lay, projected=True)
+            t2 = None
+            if self.fuse_tail and p.get("tail_w") is not None and n % 128 == 0 and self._ffn_ok(M, c):
+                # to_out + bias + attn2's row bias + residual -> norm3 -> FeedForward -> + x in ONE launch: t1 never exists in HBM
+                if self.fuse_post and p.get("tail_post") and (out is not None or o32 is not None):
+                    for r0, rows, at0, s0 in lay.tail:
+                        hip.attn_out_ffn_proj_fused(att[at0:], t0, a2vec[s0:], p["tail_w"], p["wo"]["b"], p["ln3"][0], p["ln3"][1],
+                                                    p["ff1"]["b"], p["ff2p"], p["ff2"]["b"], p["proj_out"]["b"], x.t32,
+                                                    out[r0:] if out is not None else None, o32[r0:] if o32 is not None else None,
+                                                    cs[r0 // 64:] if cs is not None else None, M=rows, C_=c, rows_per_sample=n)
+                    return Act(out, N, x.H, x.W, cs, o32)
+                t2 = self._new(M, c)
+                hip.attn_out_ffn_fused(att, t0, a2vec, p["tail_w"], p["wo"]["b"], p["ln3"][0], p["ln3"][1], p["ff1"]["b"], p["ff2p"],
+                                       p["ff2"]["b"], t2, M=M, C_=c, rows_per_sample=n)
+            else:
+                t1 = self._new(M, c, torch.float32)
+                self._attn1_out(att, p, pl, a2vec, n, None, residual32=t0, out32=t1)
+                t2 = self._ffn(t1, p, n)
         else:
-            self._gemm(g.t, p["proj_in"], t0, hw=x.H * x.W)
-        a, b = p["a2_slice"]
-        t2 = self._block(t0, p, mod.transformer_blocks[0].attn1, a2_all[:, a:b], N, n, (x.H, x.W))
-        out, cs, o32 = self._new_target(x.M, c, x.hw) if tgt is None else tgt
-        self._gemm(t2, p["proj_out"], out, colstats=cs, hw=x.H * x.W, out32=o32, **self._resid(x))
+            g = self._gn(x, p["gn"], 1e-6, False)
+            # interior16: the block's INTERIOR running sums (t0 after proj_in, t1 after attention) of the 640- / 1280-channel blocks in 16
+            # bits -- 12 B per element less through HBM per block (proj_in, two LayerNorms, to_out's residual in and out, ff.net[2]'s
+            # residual); the main residual stream (x_in + proj_out) stays fp32.  Emulated cost on the whole UNet: 1.2400e-3 vs 1.2236e-3
+            # (tests/precision_budget.py `si_min_c`; the level-0 blocks, where it would cost 4x that, keep t1 in registers anyway)
+            wide = s32 and not (self.interior16 and c >= 640)
+            t0 = self._new(M, c, torch.float32 if wide else None)
+            if wide:
+                self._gemm(g.t, p["proj_in"], None, hw=n, out32=t0)
+            else:
+                self._gemm(g.t, p["proj_in"], t0, hw=n)
+            t2 = self._block(t0, p, pl, attn1.heads, a2vec, N, n)
+        assert not shared, "_share_ok admits only the layers whose tail launch includes proj_out"
+        self._gemm(t2, p["proj_out"], out, colstats=cs, hw=n, out32=o32, **self._resid(x))
         return Act(out, x.N, x.H, x.W, cs, o32)
 
     # ------------------------------------------------------------------ the forward
@@ -992,28 +931,22 @@ class UNetEngine(_StepReplay):
         ``to_out(to_v(ctx))``, as fp32 row-bias matrices."""
         P, N = self._packed, timesteps.shape[0]
         mc = self.unet.model_channels
+        temb = self._new(N, mc)
+        hip.timestep_embedding(timesteps.to(device=self.device, dtype=torch.int64).contiguous(), temb, mc)
+        e0, emb = self._new(N, 4 * mc), self._new(N, 4 * mc)
+        emb_all = self._new(N, P["emb_all"]["n"], torch.float32)
         if self.fuse_temb and hip.linear_small_supported(N, 4 * mc, mc) and hip.linear_small_supported(N, P["emb_all"]["n"], 4 * mc):
             # three launches of the few-row kernel (csrc/linear_small.hip) instead of three GEMMs + two SiLUs; each SiLU acts on its
             # layer's fp32 sum
-            temb = self._new(N, mc)
-            hip.timestep_embedding(timesteps.to(device=self.device, dtype=torch.int64).contiguous(), temb, mc)
-            e0 = self._new(N, 4 * mc)
             hip.linear_small(temb, P["time_embed.0"]["w"], P["time_embed.0"]["b"], e0, M=N, N=4 * mc, K=mc, silu=True)
-            emb = self._new(N, 4 * mc)
             hip.linear_small(e0, P["time_embed.2"]["w"], P["time_embed.2"]["b"], emb, M=N, N=4 * mc, K=4 * mc, silu=True)
-            emb_all = self._new(N, P["emb_all"]["n"], torch.float32)
             hip.linear_small(emb, P["emb_all"]["w"], P["emb_all"].get("b"), emb_all, M=N, N=P["emb_all"]["n"], K=4 * mc)
-            return emb_all, self.context_projections(context, N)
-        temb = self._new(N, mc)
-        hip.timestep_embedding(timesteps.to(device=self.device, dtype=torch.int64).contiguous(), temb, mc)
-        e0 = self._new(N, 4 * mc)
-        self._gemm(temb, P["time_embed.0"], e0)
-        hip.silu(e0, e0)
-        emb = self._new(N, 4 * mc)
-        self._gemm(e0, P["time_embed.2"], emb)
-        hip.silu(emb, emb)
-        emb_all = self._new(N, P["emb_all"]["n"], torch.float32)
-        self._gemm(emb, P["emb_all"], emb_all, flags=hip.EPI_OUT_F32)
+        else:
+            self._gemm(temb, P["time_embed.0"], e0)
+            hip.silu(e0, e0)
+            self._gemm(e0, P["time_embed.2"], emb)
+            hip.silu(emb, emb)
+            self._gemm(emb, P["emb_all"], emb_all, flags=hip.EPI_OUT_F32)
         return emb_all, self.context_projections(context, N)
 
     def context_projections(self, context: torch.Tensor, N: int) -> torch.Tensor:
@@ -1024,8 +957,8 @@ class UNetEngine(_StepReplay):
         # (one entry per context OBJECT, a few of them: two loops interleaved through one engine -- this batch's sampling and the
         #  next batch's inversion, DDIMSampler.sample_while_inverting -- alternate two contexts and would evict a single entry at
         #  every step of the eager path)
-        cache = self.__dict__.setdefault("_a2_lru", {})
-        cached = self.__dict__.get("_a2_cache") or cache.get(id(context))
+        cache = self._a2_lru
+        cached = self._a2_cache or cache.get(id(context))
         if cached is not None and cached[0] is context and cached[1] == context._version and cached[2] is P:
             return cached[3]
         ctx = context.reshape(N, -1)
@@ -1111,9 +1044,11 @@ class UNetEngine(_StepReplay):
         h = x
         for i, block in enumerate(blocks_in):
             j = nb - 1 - i
-            if i == 1 and self.share_prefix and self._share_ok(block, h):
-                h = self._shared_block(block, h, part(j, h_ch[j], cats[j].shape[1]), emb_all, a2_all)
-                continue
+            if i == 1 and self.share_prefix and block[-1][0] == "st":
+                pl = self._hook_plan(block[-1][2].transformer_blocks[0].attn1, h.N, h.hw)
+                if self._share_ok(block, h, pl):
+                    h = self._shared_block(block, h, part(j, h_ch[j], cats[j].shape[1]), emb_all, a2_all, pl)
+                    continue
             h = run(block, h, part(j, h_ch[j], cats[j].shape[1]))
         h = run(mid, h, part(0, 0, h_ch[0]))
         for j, block in enumerate(blocks_out):

@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 
 from . import hip
-from .engine import Act, HookCfg, UNetEngine, plan_fusion, staged_attn1
+from .engine import Act, HookCfg, UNetEngine, plan_fusion
 
 
 def _engine_for(module, x: torch.Tensor) -> UNetEngine:
@@ -186,7 +186,7 @@ def transformer_block_forward(mod, x: torch.Tensor, context: Optional[torch.Tens
     if _several_tokens(context):
         return _block_several_tokens(eng, mod, sd, "", p, t0, context, B, n, P, want32=True)[1].reshape(B, n, d).to(x.dtype)
     a2 = _a2vec(eng, sd, "", context, B, d, P)
-    t2, t2_32 = eng._block(t0, p, mod.attn1, a2, B, n, None, want32=True)
+    t2, t2_32 = eng._block(t0, p, eng._hook_plan(mod.attn1, B, n), mod.attn1.heads, a2, B, n, want32=True)
     return t2_32.reshape(B, n, d).to(x.dtype)
 
 
@@ -210,14 +210,9 @@ def cross_attention_forward(mod, x: torch.Tensor, context: Optional[torch.Tensor
     x16 = to16(x).reshape(B * n, d_in)
     out = eng._new(B * n, mod.to_out[0].weight.shape[0])
     if context is None:
-        pl = plan_fusion(cfg, B, n)
-        if pl["staged"]:
-            staged_attn1(x16, pk["wqkv"], pk["wo"], pk["bo"], out, B=B, n=n, d=d, heads=mod.heads, mode=pl["staged"])
-        else:
-            p = {"c": d, "wqkv": pk["wqkv"], "wo": {"w": pk["wo"], "b": pk["bo"]}, "wlin": pk["wlin"],
-                 "qk_src": (mod.to_q.weight, mod.to_k.weight)}
-            att = eng._attn1_qkv_att(x16, eng._new(B * n, 3 * d), p, pl, B, n, mod.heads, projected=False)
-            eng._attn1_out(att, p, None, n, out)
+        p = {"c": d, "wqkv": pk["wqkv"], "wo": {"w": pk["wo"], "b": pk["bo"]}, "wlin": pk["wlin"],
+             "qk_src": (mod.to_q.weight, mod.to_k.weight)}
+        eng._attn1(x16, None, p, plan_fusion(cfg, B, n), None, B, n, mod.heads, out=out)
     else:
         m = context.shape[1]
         c16 = to16(context).reshape(B * m, context.shape[2])

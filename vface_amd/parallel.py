@@ -9,7 +9,7 @@ exchange step here, issued between the hooked ``attn1``'s projection and its edi
   k) moves one hop down the chain -- point-to-point ``isend/irecv`` (xGMI is point-to-point, so a one-hop shift costs one link
   transfer), or an all-gather of the slabs when ``mode="allgather"`` (``start_exchange``).  The transfer is started right after
   chunk 1's fused projection and waited for just before the warp, so it overlaps chunk 2's projection
-  (see ``UNetEngine._attn1_qkv_att``).
+  (see ``UNetEngine._attn1_att``).
 * ``temporal`` smooths chunk 0's q|k over +-2 frames: rank r needs the two frames before and the two after its range, in both
   directions, at EVERY hooked layer (``start_temporal``): each rank sends its first two frames down and its last two up
   (point-to-point), or -- with ``mode="allgather"``, or when a shard holds fewer than two frames, so that a needed frame may
@@ -301,7 +301,7 @@ class LoopbackShard(FrameShard):
     """All shards of a clip run ONE AFTER ANOTHER in one process on one GPU: rank r's boundary slabs are kept in memory
     (in call order -- one per hooked level-0 layer and UNet call) and handed to rank r+1 when it runs.  The chain has
     no cycle (rank 0 needs nothing), so running the ranks in order needs no concurrency.  Same engine code path as the
-    RCCL exchange (``UNetEngine._attn1_qkv_att``), which makes it the strict bit-for-bit test of that path
+    RCCL exchange (``UNetEngine._attn1_att``), which makes it the strict bit-for-bit test of that path
     (tests/test_sharded_gpu.py) and a way to walk a clip that does not fit one batch through one GPU."""
 
     def __init__(self, rank: int, world: int, total_frames: int, store: dict):

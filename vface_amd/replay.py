@@ -79,7 +79,7 @@ class _GraphSegments:
                 pass
             self.cur = None
 
-    # ---- the exchange interface (parallel.FrameShard), as seen by UNetEngine._attn1_qkv_att while capturing
+    # ---- the exchange interface (parallel.FrameShard), as seen by UNetEngine._attn1_att while capturing
     def set_index(self, k: int) -> None:
         self.index = int(k)
 
@@ -535,7 +535,7 @@ class _StepReplay:
                 cfgs.append(cfg)
         own_flows = [f.clone() for f in flows]
         saved_flows = [c.flow for c in cfgs]
-        saved_cache = getattr(self, "_a2_cache", None)
+        saved_cache = self._a2_cache
         real_exchange, real_halo_flow = self.halo_exchange, self.halo_flow
         own_halo_flow = real_halo_flow.clone() if (real_exchange is not None and real_halo_flow is not None) else None
         seg, eps_warm, counting, ok, pool_bytes = None, None, None, True, 0
