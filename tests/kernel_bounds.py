@@ -1,15 +1,22 @@
-"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py, test_gemm_conv_gpu.py):
-seeded 16-bit inputs, the unit in the last place of a 16-bit type, sentinel-filled buffers that show a store outside a kernel's slot,
-the element-wise bound check that names the worst element, and the fp64 references with their per-element bounds: the attention
-kernel's (``attention_ref_and_bound``), the GEMM family's with its epilogues, split-K and GEGLU (``gemm_ref_and_bound``), the
-convolutions' (``conv_ref_and_bound``) and the column statistics' (``colstats_ref_and_bound``).  Every bound is built from fp64
-quantities of the reference alone; test_attention_bound_cpu.py and test_gemm_bound_cpu.py show that each admits a model of the
-kernel's rounding points and refuses one-line defects of it.  Plain functions, nothing collected by pytest."""
+"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py, test_gemm_conv_gpu.py,
+test_transformer_kernels_gpu.py): seeded 16-bit inputs, the unit in the last place of a 16-bit type, sentinel-filled buffers and the
+``Framed`` output view / ``strided`` input view that show a store outside a kernel's slot or a leading dimension mistaken for a
+width, the element-wise bound check that names the worst element, and the fp64 references with their per-element bounds: the
+attention kernel's (``attention_ref_and_bound``), the GEMM family's with its epilogues, split-K and GEGLU (``gemm_ref_and_bound``),
+the convolutions' (``conv_ref_and_bound``), the column statistics' (``colstats_ref_and_bound``), LayerNorm's
+(``layernorm_ref_and_bound``), the GroupNorm family's (``gn_stats_ref_and_bound`` from pixels with the conditioning term of the
+one-pass sums, ``gn_cols_ref_and_bound`` from column sums, ``gn_apply_ref_and_bound`` from the device's statistics),
+``linear_small_ref_and_bound``, and the fused chains' stage by stage (``st_front_t0_`` / ``st_front_qkv_ref_and_bound``,
+``ffn_ref_and_bound`` for PLAIN / PRE / POST) with ``round_operand`` for a value rounded once as the next operand.  Every bound is
+built from fp64 quantities of the reference alone; test_attention_bound_cpu.py, test_gemm_bound_cpu.py and
+test_transformer_bound_cpu.py show that each admits a model of the kernel's rounding points and refuses one-line defects of it.
+Plain functions, nothing collected by pytest."""
 import math
 
 import torch
 import torch.nn.functional as F
 
+DEV = "cuda"
 U32 = 2.0 ** -24                                   # fp32 unit roundoff
 TINY32 = 2.0 ** -126                               # smallest normal fp32: what a flushed subnormal intermediate can lose
 MANT = {torch.float16: (10, -14), torch.bfloat16: (7, -126), torch.float32: (23, -126)}   # explicit mantissa bits, smallest normal exponent
@@ -41,6 +48,51 @@ def same_bits(a, b):
     return torch.equal(a.contiguous().view(view), b.contiguous().view(view))
 
 
+class Framed:
+    """A ``[rows, cols]`` view inside a sentinel buffer (``lead`` extra trailing dimension for the statistics' pairs)."""
+
+    def __init__(self, rows, cols, dt, pair=False):
+        self.rows, self.cols, self.ld, self.pair = rows, cols, cols + 24, pair
+        k = 2 if pair else 1
+        self.keep = sentinel(rows + 3, self.ld * k, dt)
+        self.dev = self.keep.to(DEV)
+
+    def _v(self, t):
+        if self.pair:
+            return t.view(self.rows + 3, self.ld, 2)[1:1 + self.rows, 8:8 + self.cols]
+        return t[1:1 + self.rows, 8:8 + self.cols]
+
+    @property
+    def view(self):
+        return self._v(self.dev)
+
+    @property
+    def stats_arg(self):
+        """what ``hip.gemm(colstats=...)`` takes: its ``stride(0) // 2`` is the leading dimension"""
+        return self.dev.view(self.rows + 3, self.ld, 2)[1:, 8:]
+
+    def result(self, what, rows=None):
+        """The view's content on the CPU, after the check that nothing outside it (or outside ``rows`` of it) changed."""
+        torch.cuda.synchronize()
+        allv = self.dev.cpu()
+        got = self._v(allv).clone()
+        expect = self.keep.clone()
+        if rows is None:
+            self._v(expect).copy_(got)
+        else:
+            self._v(expect)[rows] = got[rows]
+        assert same_bits(allv, expect), f"{what}: a store outside the output view"
+        self.keep = expect
+        return got
+
+
+def strided(x, off):
+    """``x [rows, cols]`` on the device as a view ``off`` columns into a buffer ``2 off`` wider (the rest NaN)."""
+    buf = torch.full((x.shape[0], x.shape[1] + 2 * off), float("nan"), dtype=x.dtype)
+    buf[:, off:off + x.shape[1]] = x
+    return buf.to(DEV)[:, off:off + x.shape[1]]
+
+
 def assert_within(got, ref64, bound, what):
     """Every element of ``got`` within ``bound`` of the fp64 reference; on failure the message names the worst element."""
     got64 = got.double()
@@ -56,6 +108,17 @@ def assert_within(got, ref64, bound, what):
         raise AssertionError(f"{what}: {int(bad.sum())} of {err.numel()} out of bound; worst at {idx}: got {float(got64.flatten()[worst])!r} "
                              f"ref {float(ref64.flatten()[worst])!r} err {float(err.flatten()[worst]):.3e} bound {float(b.flatten()[worst]):.3e}")
     return err
+
+
+WORST = {}                                         # family -> worst err / bound seen (printed; a record of headroom, no threshold)
+
+
+def note(family, err, bound):
+    """Print and keep the worst error / bound of a family: a record of headroom, never a threshold."""
+    r = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
+    WORST[family] = max(WORST.get(family, 0.0), r)
+    print(f"[headroom] {family}: worst err / bound {r:.3f} (so far {WORST[family]:.3f})")
+    return r
 
 
 def cpu_fp32_rel_error(fn, x32, factor=4.0, **kw):
@@ -134,9 +197,12 @@ def unit_roundoff(dt):
     return 2.0 ** -(MANT[dt][0] + 1)
 
 
-def _pre_and_e32(S, A, K, terms, splits):
+def _pre_and_e32(S, A, K, terms, splits, init=None, init_mag=None):
     """``pre`` and the fp32 part of the bound from the fp64 sum of products S, the sum of their magnitudes A and the epilogue's
-    fp64 addends (absent ones left out)."""
+    fp64 addends (absent ones left out).  ``init``: the accumulator's initial value -- one more term of the sum, carried through
+    all K additions, so its magnitude (``init_mag``, default |init|) joins A."""
+    if init is not None:
+        S, A = S + init, A + (init.abs() if init_mag is None else init_mag)
     pre, mag = S.clone(), S.abs()
     for t in terms:
         pre = pre + t
@@ -155,7 +221,7 @@ def gelu64(g):
     return 0.5 * g * (1.0 + torch.erf(g / math.sqrt(2.0)))
 
 
-def _geglu(pre, e32, dt):
+def _geglu(pre, e32, dt, rounded=True):
     """out = val gelu(gate) from the two halves of ``pre`` (value columns first), both carrying ``e32``.  With e_v, e_g the two
     halves of e32: |gelu(g + d) - gelu(g)| <= |gelu'(g)| |d| + 0.4 d^2 (gelu'' = phi(g) (2 - g^2), at most 2 phi(0) = 0.798 in
     magnitude), gelu_erf_f differs from gelu by |g| (7.5e-8 + 8 U32) (Phi's absolute error, plus v_rcp, v_exp and the ten fused
@@ -167,11 +233,11 @@ def _geglu(pre, e32, dt):
     out = val * gelu64(g)
     dgelu = d1.abs() * eg + 0.4 * eg * eg + (g.abs() + eg) * (GELU_AS_ABS + 8 * U32)
     b = (val.abs() + ev) * dgelu + ev * gelu64(g).abs() + 2 * U32 * out.abs()
-    return out, b + 0.5 * ulp(out.abs() + b, dt)
+    return out, (b + 0.5 * ulp(out.abs() + b, dt) if rounded else b)
 
 
 def gemm_ref_and_bound(a, w, dt, *, bias=None, rowbias=None, rows_per_sample=1, residual=None, out_f32=False, splits=1, geglu=False,
-                       a_err=None):
+                       a_err=None, init=None, init_mag=None, rounded=True):
     """``vface_gemm`` in fp64 and what a correct kernel may differ by, per element.  ``a [M, K]`` (for the dual-source form: the two
     sources side by side), ``w [N, K]``: the 16-bit operands; ``bias [N]``, ``rowbias [M / rows_per_sample, N]`` fp32; ``residual
     [M, N]`` 16-bit or fp32.  ``geglu``: ``w`` and ``bias`` in the module's order (value rows, then gate rows); the result has N / 2
@@ -191,8 +257,11 @@ def gemm_ref_and_bound(a, w, dt, *, bias=None, rowbias=None, rows_per_sample=1, 
     * split-K: the partial sums are fp32 and are added in order, then the epilogue as before: (splits + 1) U32 A more.
     * ``a_err`` (fp64 [M, N], optional): what the operands themselves may be off by, already multiplied through |w| -- the
       convolutions' fused input normalisation passes it (conv_ref_and_bound).
+    * ``init`` (fp64 [M, N], optional; ``init_mag`` its magnitude where the kernel carries more than |init|): what the accumulator
+      starts from where a fused kernel loads a residual or a bias straight into it -- a term of the sum like the products.
     * one rounding to ``dt`` at the largest magnitude the bound admits; the fp32 forms store the sum itself (U32 |pre| stands for
-      the third epilogue add where the residual is absent, and for nothing else)."""
+      the third epilogue add where the residual is absent, and for nothing else).  ``rounded=False`` (GEGLU only): without the
+      final rounding -- the fused chains round the hidden activations as the next operand (``round_operand``)."""
     a64, w64 = a.double(), w.double()
     K = a64.shape[1]
     S, A = a64 @ w64.T, a64.abs() @ w64.abs().T
@@ -203,12 +272,12 @@ def gemm_ref_and_bound(a, w, dt, *, bias=None, rowbias=None, rows_per_sample=1, 
         terms.append(rowbias.double().repeat_interleave(rows_per_sample, 0)[:S.shape[0]])
     if residual is not None:
         terms.append(residual.double())
-    pre, e32 = _pre_and_e32(S, A, K, terms, splits)
+    pre, e32 = _pre_and_e32(S, A, K, terms, splits, init, init_mag)
     if a_err is not None:
         e32 = e32 + a_err
     if geglu:
         assert residual is None and rowbias is None and not out_f32
-        return _geglu(pre, e32, dt)
+        return _geglu(pre, e32, dt, rounded)
     return pre, _rounded(pre, e32, dt, out_f32)
 
 
@@ -294,3 +363,261 @@ def colstats_ref_and_bound(stored, slice_rows):
         ref.append(torch.stack([s.sum(0), (s * s).sum(0)], -1))
         bound.append(torch.stack([k * s.abs().sum(0), k * (s * s).sum(0)], -1))
     return torch.stack(ref), torch.stack(bound)
+
+
+# ------------------------------------------------------------------------------------------------ norms and the fused transformer chains
+U64 = 2.0 ** -53          # fp64 unit roundoff (the GroupNorm folds)
+GN_PIX = 128              # pixels per workgroup of gn_partial_kernel (csrc/pointwise.hip)
+
+
+def as_16bit(ref64, e32, dt):
+    """The bound of a 16-bit output whose fp32 value is within ``e32`` of ``ref64``: one rounding at the largest magnitude admitted."""
+    return e32 + 0.5 * ulp(ref64.abs() + e32, dt)
+
+
+def round_operand(o64, e, dt):
+    """A value rounded to ``dt`` ONCE as the next GEMM's operand, the rounding modelled as EXACT except near a tie.  ``o64``: the
+    fp64 value, ``e``: what the kernel's fp32 value may differ from it by.  Returns ``(r, d)``: r = o64 rounded to nearest even in
+    ``dt`` (computed in fp64 on the type's own grid, no double rounding) and d = what the kernel's operand may differ from r by:
+    0 where no rounding tie of ``dt`` lies within e of o64 (both round to the same value), q + e otherwise (q the spacing of ``dt``
+    at |o64| + e: a tie between the two values moves the result by one spacing, several of them by no more than e + q).
+    This is what makes a stage behind a rounding as tight as the stage itself: the alternative u |o| (every operand off by half a
+    spacing) is the size of the rounding, which the reference can reproduce, not of the kernel's error, which it cannot."""
+    q = ulp(o64.abs() + e, dt)
+    t = o64 / q
+    r = torch.round(t) * q                                           # round half to even, exact: q is a power of two
+    tie = ((t - torch.floor(t)) - 0.5).abs() * q
+    return r, torch.where(tie <= e, q + e, torch.zeros_like(o64))
+
+
+def _rsqrt_interval(var, dvar, eps):
+    """rstd = (var + eps)^-1/2 and how far a variance within ``dvar`` of ``var`` -- clamped at 0 as the kernels do -- moves it."""
+    r = 1.0 / torch.sqrt(var + eps)
+    lo = 1.0 / torch.sqrt(var + dvar + eps)
+    hi = 1.0 / torch.sqrt(torch.clamp(var - dvar, min=0.0) + eps)
+    return r, torch.maximum(hi - r, r - lo)
+
+
+def layernorm_ref_and_bound(x, gamma, beta, eps, dt, x_err=None, rounded=True):
+    """``vface_layernorm`` (and the LayerNorm stage of stfront.hip / ffn.hip: the same two passes on the fp32 tile) in fp64 and what
+    a correct kernel may differ by, per element.  ``x [M, C]`` 16-bit or fp32, ``gamma, beta [C]`` fp32.  Returns ``(y, bound)``.
+    With d = x - mean, var = mean(d^2), rstd = (var + eps)^-1/2, t = d rstd gamma, y = t + beta and m1 = mean |x|:
+
+      dmu   = (C + 2) U32 m1                        the fp32 sum of C terms in any order ((C - 1) U32 sum |x|), the division
+      dvar  = dmu^2 + (C + 8) U32 var + U32 (var + eps)
+              -- a constant shift of every d_i by dmu leaves sum d_i^2 unchanged to FIRST order (sum d = 0): the mean's error
+              enters the variance squared; the subtraction's own rounding U32 |d_i| twice, the C squares and their fp32 sum
+              (C + 3) U32 var, the division and the addition of eps
+      drstd = what dvar moves rstd by (interval, no linearisation: a constant row has var = 0) + r rstd,
+              r = cpu_fp32_rel_error(rsqrt) on the case's own var + eps
+      e32   = rstd |gamma| (dmu + U32 |d|) + |gamma d| drstd + 2 U32 |t| + U32 (|t| + |beta|)
+              -- THE MEAN'S ERROR ENTERS THROUGH rstd |gamma|: a constant row of value v has rstd = eps^-1/2 = 316 and gets
+              316 |gamma| (C + 2) U32 |v|, the wide bound it deserves; two products and the sum (or its fused form)
+      bound = e32 + 0.5 ulp(|y| + e32, dt)          one rounding (``rounded=False``: e32 alone, for ``round_operand``)
+
+    ``x_err`` (fp64 [M, C], optional): what the INPUT may be off by (a fused kernel normalising its own accumulator tile).  To
+    first order dy_i = rstd gamma_i (dx_i - mean(dx) - xh_i mean(xh dx)), xh = d rstd, so
+      e32 += rstd |gamma_i| (x_err_i + mean(x_err) + |xh_i| mean(|xh| x_err))."""
+    x64, g64, b64 = x.double(), gamma.double()[None, :], beta.double()[None, :]
+    C = x64.shape[1]
+    mu = x64.mean(1, keepdim=True)
+    d = x64 - mu
+    var = (d * d).mean(1, keepdim=True)
+    dmu = (C + 2) * U32 * x64.abs().mean(1, keepdim=True)
+    dvar = dmu * dmu + (C + 8) * U32 * var + U32 * (var + eps)
+    rstd, drstd = _rsqrt_interval(var, dvar, eps)
+    drstd = drstd + cpu_fp32_rel_error(torch.rsqrt, (var + eps).float()) * rstd
+    t = d * rstd * g64
+    y = t + b64
+    e32 = rstd * g64.abs() * (dmu + U32 * d.abs()) + (g64 * d).abs() * drstd + 2 * U32 * t.abs() + U32 * (t.abs() + b64.abs())
+    if x_err is not None:
+        xh = (d * rstd).abs()
+        e32 = e32 + rstd * g64.abs() * (x_err + x_err.mean(1, keepdim=True) + xh * (xh * x_err).mean(1, keepdim=True))
+    return y, (as_16bit(y, e32, dt) if rounded else e32)
+
+
+def gn_sum_depth(C, groups, hw):
+    """How many fp32 additions one term passes through in gn_partial_kernel: a thread's pixel loop (ceil(min(hw, 128) / PP) terms,
+    PP = 256 / min(C / 8, 256) pixel lanes), the PP lanes in order, the C / groups channels of the group in order."""
+    pp = 256 // min(C // 8, 256)
+    return -(-min(hw, GN_PIX) // pp) + pp + C // groups
+
+
+def gn_stats_ref_and_bound(x, groups, eps):
+    """``vface_groupnorm_stats`` from the pixels in fp64 and its per-element bound.  ``x [nimg, hw, C]`` 16-bit or fp32.  Returns
+    ``(stats [nimg, groups, 2] = (mean, rstd), bound)``.  The kernel sums x and x^2 in fp32 per thread, per pixel lane and per
+    group (D = gn_sum_depth additions on the way of any term: D U32 sum |x|, (D + 1) U32 sum x^2 with the squares' own
+    rounding), folds the 128-pixel chunks in fp64 and forms var = E[x^2] - mean^2 in fp64.  With m = mean, v = var:
+
+      dmean = (D + 2) U32 mean |x|
+      dvar  = 3 (D + 3) U32 (m^2 + v) + dmean^2 = 3 (D + 3) U32 v * [(m^2 + v) / v] + dmean^2
+              -- dE2 <= (D + 3) U32 (m^2 + v) and 2 |m| dmean <= 2 (D + 2) U32 (m^2 + v) since |m| mean |x| <= E[x^2] = m^2 + v:
+              the CONDITIONING TERM (m^2 + v) / v of the one-pass form is explicit here, it is what the algorithm implies (at
+              mean / spread 16 it is 257), not a property of a particular kernel
+      mean:  dmean + U32 |m|                       (the rounding of the fp64 mean to fp32)
+      rstd:  what dvar moves (v + eps)^-1/2 by, the clamp of the variance at 0 included, + 2 U32 rstd"""
+    nimg, hw, C = x.shape
+    cpg = C // groups
+    x64 = x.double().reshape(nimg, hw, groups, cpg)
+    m = x64.mean((1, 3))
+    v = ((x64 - m[:, None, :, None]) ** 2).mean((1, 3))
+    D = gn_sum_depth(C, groups, hw)
+    dmean = (D + 2) * U32 * x64.abs().mean((1, 3))
+    dvar = 3 * (D + 3) * U32 * (m * m + v) + dmean * dmean
+    rstd, drstd = _rsqrt_interval(v, dvar, eps)
+    return torch.stack([m, rstd], -1), torch.stack([dmean + U32 * m.abs(), drstd + 2 * U32 * rstd], -1)
+
+
+def gn_cols_ref_and_bound(cs, nimg, hw, groups, eps, gamma=None, beta=None):
+    """``vface_groupnorm_finalize_cols`` / ``_coeffs_from_cols`` in fp64 from the very column sums ``cs [nimg hw / 64, C, 2]`` the
+    kernel reads.  The fold is fp64 (n = cpg hw / 64 terms), so what is left is the fold's own error and THE FINAL ROUNDING to fp32:
+      mean: (n + 2) U64 mean |s| + U32 |m|
+      var  = max(E2 - m^2, 0) exactly as the kernel forms and clamps it; dvar = (n + 4) U64 (E2 + m^2) -- a group whose fp32
+             sums give a slightly negative variance is clamped in the reference too, and the clamp is continuous
+      rstd: what dvar moves it by + 4 U64 rstd + U32 rstd
+    With ``gamma, beta``: also ``(ab [nimg, C, 2], bound)`` of a = rstd32 gamma, b = beta - mean32 a in fp32:
+      da = |gamma| drstd + U32 |a|;  db = |m| da + |a| dmean + 2 U32 |m a| + U32 |beta|.
+    Returns ``(stats, stats_bound)`` or ``(stats, stats_bound, ab, ab_bound)``."""
+    C = cs.shape[1]
+    cpg, spi = C // groups, hw // 64
+    c64 = cs.double().reshape(nimg, spi, groups, cpg, 2)
+    n, count = cpg * spi, float(hw * cpg)
+    m = c64[..., 0].sum((1, 3)) / count
+    E2 = c64[..., 1].sum((1, 3)) / count
+    v = torch.clamp(E2 - m * m, min=0.0)
+    dmean = (n + 2) * U64 * c64[..., 0].abs().sum((1, 3)) / count
+    dvar = (n + 4) * U64 * (E2.abs() + m * m)
+    rstd, drstd = _rsqrt_interval(v, dvar, eps)
+    drstd = drstd + (4 * U64 + U32) * rstd
+    dmean = dmean + U32 * m.abs()
+    out = (torch.stack([m, rstd], -1), torch.stack([dmean, drstd], -1))
+    if gamma is None:
+        return out
+    g64, b64 = gamma.double()[None, :], beta.double()[None, :]
+    rep = lambda t: t.repeat_interleave(cpg, 1)
+    a = rep(rstd) * g64
+    b = b64 - rep(m) * a
+    da = g64.abs() * rep(drstd) + U32 * a.abs()
+    db = rep(m).abs() * da + a.abs() * rep(dmean) + 2 * U32 * (rep(m) * a).abs() + U32 * b64.abs()
+    return out + (torch.stack([a, b], -1), torch.stack([da, db], -1))
+
+
+def scale_shift_act(x, a, b, silu):
+    """o = act(x a + b) in fp64 and the fp32 error of it: ``(o, e)`` with e = 2 U32 (|x a| + |b|) |act'| + r |o| -- the product and
+    the sum (or their fused form) through the activation's slope, r = cpu_fp32_rel_error of the SiLU on the case's own arguments."""
+    x64, a64, b64 = x.double(), a.double(), b.double()
+    t = x64 * a64 + b64
+    e = 2 * U32 * ((x64 * a64).abs() + b64.abs())
+    if not silu:
+        return t, e
+    sg = torch.sigmoid(t)
+    o = t * sg
+    r = cpu_fp32_rel_error(F.silu, (x.float() * a.float() + b.float()))
+    return o, e * (sg * (1.0 + t * (1.0 - sg))).abs() + r * o.abs() + 0.4 * e * e
+
+
+def gn_apply_ref_and_bound(x, stats, gamma, beta, groups, silu, dt):
+    """``vface_groupnorm_apply`` in fp64 FROM THE STATISTICS AS READ BACK FROM THE DEVICE (``stats [nimg, groups, 2]`` fp32), so
+    the bound holds no statistics error: a = rstd gamma and b = beta - mean a formed in fp32 (da = U32 |a|, db = |mean| da +
+    2 U32 (|beta| + |mean a|)), the multiply-add x a + b (|x| da + db + ``scale_shift_act``'s 2 U32 (|x a| + |b|)), the SiLU
+    allowance, one rounding.  ``x [nimg, hw, C]``.  Returns ``(y [nimg, hw, C], bound)``."""
+    nimg, hw, C = x.shape
+    cpg = C // groups
+    st = stats.double()
+    mean, rstd = st[..., 0].repeat_interleave(cpg, 1)[:, None, :], st[..., 1].repeat_interleave(cpg, 1)[:, None, :]
+    g64, b64 = gamma.double()[None, None, :], beta.double()[None, None, :]
+    a = rstd * g64
+    b = b64 - mean * a
+    da = U32 * a.abs()
+    db = mean.abs() * da + 2 * U32 * (b64.abs() + (mean * a).abs())
+    o, e = scale_shift_act(x, a.expand(nimg, hw, C), b.expand(nimg, hw, C), silu)
+    slope = 1.1 if silu else 1.0                                      # |SiLU'| <= 1.1
+    e = e + slope * (x.double().abs() * da + db)
+    return o, as_16bit(o, e, dt)
+
+
+def linear_small_ref_and_bound(a, w, dt, bias=None, silu=False, out_f32=False):
+    """``vface_linear_small`` in fp64: ``gemm_ref_and_bound`` with FOUR partial sums (the four waves' quarters of K meet in LDS in
+    a fixed order: ``splits=4``), then the SiLU on the fp32 sum through its slope (|SiLU'| <= 1.1, r = cpu_fp32_rel_error), then
+    one rounding -- to ``dt``, or to fp32."""
+    pre, e = gemm_ref_and_bound(a, w, dt, bias=bias, out_f32=True, splits=4)
+    if silu:
+        sg = torch.sigmoid(pre)
+        r = cpu_fp32_rel_error(F.silu, pre.float())
+        o = pre * sg
+        e = (sg * (1.0 + pre * (1.0 - sg))).abs() * e + 0.4 * e * e + r * o.abs()
+        pre = o
+    return pre, (e + U32 * pre.abs() if out_f32 else as_16bit(pre, e, dt))
+
+
+def st_front_t0_ref_and_bound(x32, ab, hw, w_in, b_in, dt):
+    """Stage 1 of ``vface_st_front``: t0 = round_dt(x a[img] + b[img]) @ W_in^T + b_in in fp64 from x32 and THE DEVICE's ``ab
+    [nimg, C, 2]``.  The GroupNorm'd operand is rounded by ``round_operand`` (exact except within the multiply-add's 2 U32 (|x a| +
+    |b|) of a tie): with u |o| instead the bound would be 100x the fp32 stage's own and a tile that takes another image's (a, b)
+    on images that differ little would pass.  b_in is the accumulator's initial value (``init``).  Returns ``(t0, bound)``, fp32 form."""
+    abd = ab.double()
+    a, b = abd[..., 0].repeat_interleave(hw, 0), abd[..., 1].repeat_interleave(hw, 0)
+    o, e = scale_shift_act(x32, a.float(), b.float(), False)
+    r, d = round_operand(o, e, dt)
+    return gemm_ref_and_bound(r, w_in, dt, out_f32=True, a_err=d @ w_in.double().abs().T, init=b_in.double()[None, :].expand(r.shape[0], -1))
+
+
+def st_front_qkv_ref_and_bound(t0, gamma, beta, eps, w_p, dt, ln=None):
+    """Stages 2 and 3 of ``vface_st_front`` from the device's ``t0`` (fp32): ``(ln_ref, ln_bound, qkv_ref, qkv_bound)``.  ln: the
+    LayerNorm bound on the device's t0.  qkv: with the device's ``ln`` bits, ``gemm_ref_and_bound`` on them (an exact operand);
+    without, the fp64 LayerNorm rounded by ``round_operand`` (exact except within the LayerNorm's fp32 error of a tie), its d
+    pushed through |W_p| -- u |ln| instead would hide unpermuted k columns of W_p behind sum |ln| |w| u wherever gamma is flat."""
+    y, e = layernorm_ref_and_bound(t0, gamma, beta, eps, dt, rounded=False)
+    if ln is not None:
+        q, qb = gemm_ref_and_bound(ln, w_p, dt)
+    else:
+        r, d = round_operand(y, e, dt)
+        q, qb = gemm_ref_and_bound(r, w_p, dt, a_err=d @ w_p.double().abs().T)
+    return y, as_16bit(y, e, dt), q, qb
+
+
+def ffn_ref_and_bound(dt, *, gamma, beta, eps, w1, b1, w2, b2, x32=None, att=None, wo=None, bo=None, rowbias=None, rows_per_sample=1,
+                      resid=None, wpo=None, b_po=None, x_in=None, t3_from=None):
+    """The three forms of csrc/ffn.hip in fp64, stage by stage, none of the intermediates being exposed: ``(out, e)`` -- PLAIN
+    (``x32``) and PRE (``att, wo, bo, resid`` [+ ``rowbias``]) -- or ``(y, e)`` -- POST (+ ``wpo, b_po, x_in``); e is the fp32
+    form (what ``out32`` may differ by; ``as_16bit`` for a 16-bit-only output).  Weights in the MODULE's order (``w1``: value rows,
+    then gate rows; no packing).
+      t1  = x32                                             PLAIN: exact
+          = att Wo^T + bo + rowbias + resid                 PRE: gemm bound, fp32 form, resid the accumulator's initial value (e1)
+      ln  = LayerNorm(t1)                                   layernorm bound with x_err = e1, then ``round_operand``
+      h   = val gelu(gate), [val; gate] = W1 ln + b1        gemm bound with GEGLU, a_err = d_ln |W1|^T, then ``round_operand``
+      out = W2 h + b2 + t1                                  gemm bound, fp32 form, a_err = d_h |W2|^T + e1; PLAIN: t1 an epilogue
+                                                            addend; PRE: t1 INSIDE the accumulator through all 4C additions
+                                                            (``init``, magnitude |resid| + |att| |Wo|^T + |bo + rowbias|)
+      t3  = round(out); y = Wpo t3 + b_po + x_in            POST: ``round_operand``, gemm bound with ``init`` = x_in
+    ``t3_from`` (fp32 [M, C], POST only): ``out32`` of the PRE form launched on the same inputs -- the sibling kernel EXPOSES the
+    intermediate, its accumulator and its (b2 + bo + rowbias) addend are formed by the same operations, so t3 is that value rounded
+    once, exact except within 4 U32 |out| of a tie; y is then one GEMM stage with a bound as tight as a stage's.  Without it the
+    chain's bound on y carries every upstream rounding tie through |W2| and |Wpo| and is 10x to 100x wider.
+    Every 16-bit rounding is ``round_operand`` (exact except within the stage's own fp32 error of a tie): the defects this chain
+    must refuse -- the residual added after the rounding, t1 rounded before the LayerNorm, a workgroup's row bias taken from sample
+    0 where row biases differ little -- are OF THE SIZE u |o|, so a bound that granted u |o| per operand could not see them."""
+    if t3_from is not None:
+        o32 = t3_from.double()
+        t3, d_t3 = round_operand(o32, 4 * U32 * o32.abs(), dt)
+        return gemm_ref_and_bound(t3, wpo, dt, bias=b_po, out_f32=True, a_err=d_t3 @ wpo.double().abs().T, init=x_in.double())
+    if att is None:
+        t1, e1, init = x32.double(), None, {}
+    else:
+        rb = None if rowbias is None else rowbias
+        t1, e1 = gemm_ref_and_bound(att, wo, dt, bias=bo, rowbias=rb, rows_per_sample=rows_per_sample, out_f32=True, init=resid.double())
+        mag = resid.double().abs() + att.double().abs() @ wo.double().abs().T + (t1 - resid.double() - att.double() @ wo.double().T).abs()
+        init = dict(init=t1, init_mag=mag)
+    ln, e_ln = layernorm_ref_and_bound(t1, gamma, beta, eps, dt, x_err=e1, rounded=False)
+    ln_r, d_ln = round_operand(ln, e_ln, dt)
+    h, e_h = gemm_ref_and_bound(ln_r, w1, dt, bias=b1, geglu=True, a_err=d_ln @ w1.double().abs().T, rounded=False)
+    h_r, d_h = round_operand(h, e_h, dt)
+    a_err = d_h @ w2.double().abs().T + (e1 if e1 is not None else 0.0)
+    if att is None:
+        out, e_out = gemm_ref_and_bound(h_r, w2, dt, bias=b2, residual=t1, out_f32=True, a_err=a_err)
+    else:
+        out, e_out = gemm_ref_and_bound(h_r, w2, dt, bias=b2, out_f32=True, a_err=a_err, **init)
+    if wpo is None:
+        return out, e_out
+    t3, d_t3 = round_operand(out, e_out, dt)
+    return gemm_ref_and_bound(t3, wpo, dt, bias=b_po, out_f32=True, a_err=d_t3 @ wpo.double().abs().T, init=x_in.double())

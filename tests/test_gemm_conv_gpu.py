@@ -19,72 +19,19 @@ import math
 import pytest
 import torch
 
-from kernel_bounds import (assert_within, colstats_ref_and_bound, conv_ref_and_bound, gemm_ref_and_bound, rnd, same_bits, sentinel)
+from kernel_bounds import (Framed, assert_within, colstats_ref_and_bound, conv_ref_and_bound, gemm_ref_and_bound, note, rnd, same_bits, strided)
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 DTS = [torch.float16, torch.bfloat16]
 ERR_ARG, ERR_ALIGN, ERR_SHAPE = -1, -2, -3          # include/vface_hip.h
-WORST = {}                                           # family -> worst err / bound seen (printed; a record of headroom, no threshold)
 
 
 def hip():
     from vface_amd import hip as h
     h.load()
     return h
-
-
-def note(family, err, bound):
-    r = float((err / bound.clamp_min(1e-300)).max()) if err.numel() else 0.0
-    WORST[family] = max(WORST.get(family, 0.0), r)
-    print(f"[headroom] {family}: worst err / bound {r:.3f} (so far {WORST[family]:.3f})")
-    return r
-
-
-class Framed:
-    """A ``[rows, cols]`` view inside a sentinel buffer (``lead`` extra trailing dimension for the statistics' pairs)."""
-
-    def __init__(self, rows, cols, dt, pair=False):
-        self.rows, self.cols, self.ld, self.pair = rows, cols, cols + 24, pair
-        k = 2 if pair else 1
-        self.keep = sentinel(rows + 3, self.ld * k, dt)
-        self.dev = self.keep.to(DEV)
-
-    def _v(self, t):
-        if self.pair:
-            return t.view(self.rows + 3, self.ld, 2)[1:1 + self.rows, 8:8 + self.cols]
-        return t[1:1 + self.rows, 8:8 + self.cols]
-
-    @property
-    def view(self):
-        return self._v(self.dev)
-
-    @property
-    def stats_arg(self):
-        """what ``hip.gemm(colstats=...)`` takes: its ``stride(0) // 2`` is the leading dimension"""
-        return self.dev.view(self.rows + 3, self.ld, 2)[1:, 8:]
-
-    def result(self, what, rows=None):
-        """The view's content on the CPU, after the check that nothing outside it (or outside ``rows`` of it) changed."""
-        torch.cuda.synchronize()
-        allv = self.dev.cpu()
-        got = self._v(allv).clone()
-        expect = self.keep.clone()
-        if rows is None:
-            self._v(expect).copy_(got)
-        else:
-            self._v(expect)[rows] = got[rows]
-        assert same_bits(allv, expect), f"{what}: a store outside the output view"
-        self.keep = expect
-        return got
-
-
-def strided(x, off):
-    """``x [rows, cols]`` on the device as a view ``off`` columns into a buffer ``2 off`` wider (the rest NaN)."""
-    buf = torch.full((x.shape[0], x.shape[1] + 2 * off), float("nan"), dtype=x.dtype)
-    buf[:, off:off + x.shape[1]] = x
-    return buf.to(DEV)[:, off:off + x.shape[1]]
 
 
 def plain_slices(M):

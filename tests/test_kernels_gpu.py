@@ -1247,7 +1247,9 @@ def test_st_front_vs_reference_and_vs_four_kernel_path(dt, M, C, hw, rows_full, 
     h = hip()
     from vface_amd.packing import pack_st_front
     nimg = M // hw
-    x = (rnd((M, C), 21, torch.float32, 1.3) + 0.25 * rnd((1, C), 22, torch.float32)).to(DEV)
+    img = torch.arange(M) // hw          # every image its own mean and scale: a tile that took another image's (a, b) would show
+    x = (rnd((M, C), 21, torch.float32, 1.3) * (1.0 + 0.5 * (img % 3))[:, None] + 0.25 * rnd((1, C), 22, torch.float32)
+         + (0.7 * (img % 3) - 0.5)[:, None]).to(DEV)
     w_in = rnd((C, C), 23, dt, 1 / math.sqrt(C))
     b_in = rnd((C,), 24, torch.float32, 0.1)
     w_p = rnd((3 * C, C), 25, dt, 1 / math.sqrt(C))
@@ -1311,7 +1313,8 @@ def test_fused_out_layer_vs_reference_and_vs_separate_launches(dt, cin, cout, H,
     h = hip()
     from vface_amd.packing import pack_conv3x3
     hw = H * W
-    x = (rnd((nimg * hw, cin), 51, torch.float32, 1.4) + 0.2)
+    img = torch.arange(nimg * hw) // hw          # every image its own mean and scale, so its own coefficients
+    x = rnd((nimg * hw, cin), 51, torch.float32, 1.4) * (1.0 + 0.5 * (img % 3))[:, None] + 0.2 + (0.7 * (img % 3))[:, None]
     xin = x.to(DEV) if in32 else x.to(dt).to(DEV)
     xs = xin.float()
     w = rnd((cout, cin, 3, 3), 52, dt, 1 / math.sqrt(9 * cin))
