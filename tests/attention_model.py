@@ -23,17 +23,20 @@ AGGREGATE_MARGIN = 1.25
 
 
 def ones_column(dh):
-    """True where the instantiation of head dim ``dh`` has a spare V column (DVP > DV): its denominator is summed from the ROUNDED P."""
+    """True where the instantiation of head dim ``dh`` (value tile width: sets x dh) has a spare V column (DVP > DV): its denominator
+    is summed from the ROUNDED P."""
     return (-dh) % 16 != 0
 
 
-def attention_model(q, k, v, scale, dt, form="lazy", denom_rounded=None, defect=None):
-    """``q [n, dh]``, ``k, v [nk, dh]`` of type ``dt`` -> ``[n, dh]`` of type ``dt``."""
+def attention_model(q, k, v, scale, dt, form="lazy", denom_rounded=None, defect=None, sets=1):
+    """``q [n, dh]``, ``k, v [nk, dh]`` of type ``dt`` -> ``[n, dh]`` of type ``dt``.  ``sets``: the value sets of the shared-score
+    instantiation (2 or 3); one set's output is modelled at a time, so it only selects the denominator form -- the value tile is
+    ``sets * dh`` wide and has a spare column where THAT is no multiple of 16 (dh 40 and 8 with 3 sets; not with 2)."""
     assert form in ("lazy", "exact", "spec") and (defect is None or defect in DEFECTS)
     n, dh = q.shape
     nk = k.shape[0]
     if denom_rounded is None:
-        denom_rounded = ones_column(dh)
+        denom_rounded = ones_column(sets * dh)
     c = torch.tensor(scale, dtype=torch.float32) * torch.tensor(LOG2E, dtype=torch.float32)
     qf = q.float() if form == "exact" else (q.float() * c).to(dt).float()
     nb = -(-nk // KVB)

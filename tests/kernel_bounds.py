@@ -1,5 +1,5 @@
-"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py, test_gemm_conv_gpu.py,
-test_transformer_kernels_gpu.py): seeded 16-bit inputs, the unit in the last place of a 16-bit type, sentinel-filled buffers and the
+"""Helpers of the per-kernel GPU tests (test_kernels_gpu.py, test_glue_kernels_gpu.py, test_attention_gpu.py,
+test_attention_shared_gpu.py, test_gemm_conv_gpu.py, test_transformer_kernels_gpu.py, test_hook_sampler_kernels_gpu.py): seeded 16-bit inputs, the unit in the last place of a 16-bit type, sentinel-filled buffers and the
 ``Framed`` output view / ``strided`` input view that show a store outside a kernel's slot or a leading dimension mistaken for a
 width, the element-wise bound check that names the worst element, and the fp64 references with their per-element bounds: the
 attention kernel's (``attention_ref_and_bound``), the GEMM family's with its epilogues, split-K and GEGLU (``gemm_ref_and_bound``),
@@ -7,9 +7,10 @@ the convolutions' (``conv_ref_and_bound``), the column statistics' (``colstats_r
 (``layernorm_ref_and_bound``), the GroupNorm family's (``gn_stats_ref_and_bound`` from pixels with the conditioning term of the
 one-pass sums, ``gn_cols_ref_and_bound`` from column sums, ``gn_apply_ref_and_bound`` from the device's statistics),
 ``linear_small_ref_and_bound``, and the fused chains' stage by stage (``st_front_t0_`` / ``st_front_qkv_ref_and_bound``,
-``ffn_ref_and_bound`` for PLAIN / PRE / POST) with ``round_operand`` for a value rounded once as the next operand.  Every bound is
-built from fp64 quantities of the reference alone; test_attention_bound_cpu.py, test_gemm_bound_cpu.py and
-test_transformer_bound_cpu.py show that each admits a model of the kernel's rounding points and refuses one-line defects of it.
+``ffn_ref_and_bound`` for PLAIN / PRE / POST) with ``round_operand`` for a value rounded once as the next operand, and the hook and
+sampler kernels' (``flow_warp_`` / ``flow_to_latent_`` / ``ddim_step_`` / ``timestep_embedding_ref_and_bound``).  Every bound is
+built from fp64 quantities of the reference alone; test_attention_bound_cpu.py, test_gemm_bound_cpu.py,
+test_transformer_bound_cpu.py and test_hook_bound_cpu.py show that each admits a model of the kernel's rounding points and refuses one-line defects of it.
 Plain functions, nothing collected by pytest."""
 import math
 
@@ -621,3 +622,147 @@ def ffn_ref_and_bound(dt, *, gamma, beta, eps, w1, b1, w2, b2, x32=None, att=Non
         return out, e_out
     t3, d_t3 = round_operand(out, e_out, dt)
     return gemm_ref_and_bound(t3, wpo, dt, bias=b_po, out_f32=True, a_err=d_t3 @ wpo.double().abs().T, init=x_in.double())
+
+
+# ------------------------------------------------------------------------------------------------ flow warp, flow resample, DDIM step, timestep embedding
+COORD_ULPS = 8.0          # fp32 roundings between a flow value and its un-normalised coordinate, in units of U32 (size - 1)
+
+
+def flow_coords64(flow, h, w):
+    """temporal_flow.py:43-49 and ATen's un-normalisation in fp64: ``flow [2, h, w]`` fp32 -> clamped ``(ix, iy)`` fp64 ``[h, w]``."""
+    f64 = flow.double()
+    xs = torch.arange(w, dtype=torch.float64).view(1, w).expand(h, w)
+    ys = torch.arange(h, dtype=torch.float64).view(h, 1).expand(h, w)
+    gx = 2.0 * (xs + f64[0]) / float(max(w - 1, 1)) - 1.0
+    gy = 2.0 * (ys + f64[1]) / float(max(h - 1, 1)) - 1.0
+    ix = torch.clamp(((gx + 1.0) / 2.0) * float(w - 1), 0.0, float(w - 1))
+    iy = torch.clamp(((gy + 1.0) / 2.0) * float(h - 1), 0.0, float(h - 1))
+    return ix, iy
+
+
+def flow_warp_ref_and_bound(x, frm, flow, alpha, dt, h, w):
+    """One frame of ``vface_flow_warp`` in fp64 and what a correct kernel may differ by, per element.  ``x [h w, C]``: the frame
+    itself, ``frm [h w, C]``: the frame it is warped from (the previous one, or the halo), both 16-bit; ``flow [2, h, w]`` fp32.
+    Returns ``(ref, bound)`` fp64 ``[h w, C]``, both from fp64 quantities of the reference alone (and from the one fp32 product the
+    reference itself rounds to the storage type):
+
+      (ix, iy) = the reference's coordinate in fp64: grid + flow, normalise, un-normalise, border clamp (``flow_coords64``)
+      warp     = sum over the four taps of w_tap tap, bilinear, x1 = min(x0 + 1, w - 1), y1 alike (weight 0 where clamped)
+      ax       = round_dt(fp32(alpha) * x)         -- python scalar * 16-bit tensor keeps the 16-bit type in the reference: ONE IEEE
+                                                      fp32 product rounded to ``dt``, restated exactly in torch fp32 (no error term)
+      ref      = ax + fp32(1 - alpha) * warp
+      bound    = |oma| 8 U32 S + 2 U32 (|ax| + |oma| S) + |oma| (dcx slope_x + dcy slope_y) + 0.5 ulp(|ref| + all of that)
+
+    * S = sum |w_tap tap|.  8 U32 S: wx1 = ix - floor(ix) is exact, wx0 = 1 - wx1 one rounding, the product of two weights one,
+      the product with the tap one, three additions (or their fused forms): six roundings on the way of any tap, + 2 for second
+      order and the two weights of a product both being rounded.
+    * 2 U32 (...): the product oma * warp and the final fp32 sum.
+    * dcx = COORD_ULPS U32 (w - 1): the kernel's fp32 coordinate passes through x + dx, the division, - 1, + 1 and the product
+      with (w - 1) -- five roundings (six in the reciprocal form) of numbers that, once inside the map, are no larger than w - 1
+      in units of the coordinate; outside the map both coordinates are clamped to the same border.  COORD_ULPS = 8.  A map of
+      width 1 has ix = 0 by arithmetic: dcx = 0.
+    * slope_x: bilinear interpolation is continuous across cell borders and its x-derivative inside a cell is no larger than the
+      larger |tap(x + 1) - tap(x)| of the cell's two rows; the kernel's coordinate may lie across a border from the reference's
+      (an integer flow floors to x0 - 1 with weight ~1), so the maximum runs over the footprint AND the cells next to it: columns
+      x0 - 1 .. x1 + 1, rows y0 - 1 .. y1 + 1.  slope_y alike.
+    * one rounding to ``dt`` at the largest magnitude the bound admits."""
+    C = x.shape[1]
+    img = frm.double().reshape(h, w, C)
+    ix, iy = flow_coords64(flow, h, w)
+    x0, y0 = torch.floor(ix).long(), torch.floor(iy).long()
+    wx1, wy1 = (ix - x0)[..., None], (iy - y0)[..., None]
+    wx0, wy0 = 1.0 - wx1, 1.0 - wy1
+    x1, y1 = torch.clamp(x0 + 1, max=w - 1), torch.clamp(y0 + 1, max=h - 1)
+    a, b, c, d = img[y0, x0], img[y0, x1], img[y1, x0], img[y1, x1]
+    warp = a * (wx0 * wy0) + b * (wx1 * wy0) + c * (wx0 * wy1) + d * (wx1 * wy1)
+    S = a.abs() * (wx0 * wy0) + b.abs() * (wx1 * wy0) + c.abs() * (wx0 * wy1) + d.abs() * (wx1 * wy1)
+    chw = img.permute(2, 0, 1)[None]
+    dxm = F.pad((chw[..., 1:] - chw[..., :-1]).abs(), (0, 1))             # |tap(x + 1) - tap(x)|, 0 in the last column
+    dym = F.pad((chw[..., 1:, :] - chw[..., :-1, :]).abs(), (0, 0, 0, 1))
+    mx = F.max_pool2d(dxm, 3, stride=1, padding=1)[0].permute(1, 2, 0)    # [h, w, C]: the maximum over the 3 x 3 cells around
+    my = F.max_pool2d(dym, 3, stride=1, padding=1)[0].permute(1, 2, 0)
+    slope_x = torch.maximum(mx[y0, x0], mx[y1, x0])
+    slope_y = torch.maximum(my[y0, x0], my[y0, x1])
+    ax = (torch.tensor(alpha, dtype=torch.float32) * x.float()).to(dt).double().reshape(h, w, C)
+    oma = float(torch.tensor(1.0 - alpha, dtype=torch.float32))
+    ref = ax + oma * warp
+    o = abs(oma)
+    e = o * 8 * U32 * S + 2 * U32 * (ax.abs() + o * S) + o * COORD_ULPS * U32 * ((w - 1) * slope_x + (h - 1) * slope_y)
+    return ref.reshape(h * w, C), as_16bit(ref, e, dt).reshape(h * w, C)
+
+
+def flow_to_latent_ref_and_bound(flow_px, f):
+    """``vface_flow_to_latent``: the fp64 mean over each f x f block divided by f, and ``(f f + 2) U32 mean|x| / f``: f f - 1 fp32
+    additions in order, each at most U32 of a partial sum no larger than sum |x|, the reciprocal of f^3 and the product."""
+    x64 = flow_px.double()
+    ref = F.avg_pool2d(x64, f) / f
+    return ref, (f * f + 2) * U32 * F.avg_pool2d(x64.abs(), f) / f
+
+
+def ddim_step_ref_and_bound(eu, ec, er, x, inv, noise, *, scale, a_t, a_prev, sigma_t, sqrt_1m_at, single):
+    """``vface_ddim_step`` in fp64 and its per-element fp32 bound.  ``eu, ec, er, x, inv, noise``: fp32 tensors of one shape (``ec``
+    / ``er`` / ``inv`` / ``noise`` None where the mode has none); the scalars are taken AS ROUNDED TO fp32, which is what the kernel
+    receives.  ddim_w_inv.py:666-667, 686-700; with ``single=1``, a_t = a_cur, a_prev = a_next, scale 0 it is the inversion's
+    update (:449) (x - sqrt(1 - a_cur) e) sqrt(a_next) / sqrt(a_cur) + sqrt(1 - a_next) e.
+
+      e    = eu + s (ec - eu)                 de   = 3 U32 (|eu| + |s| |ec - eu|)      the difference, the product, the sum
+      num  = x - c e, c = sqrt(1 - a_t)       dnum = c de + 2 U32 (|x| + c |e|)        the product and the difference
+      p0   = num / sqrt(a_t)                  dp0  = dnum / sqrt(a_t) + 4 U32 (|x| + c |e|) / sqrt(a_t)
+                                              -- sqrtf and the division, relative to the magnitudes num was made from
+      dir  = sqrt(1 - a_prev - sigma^2)       ddir = 3 U32 / (2 dir) + 2 U32 dir       two fp32 differences of numbers <= 1 and a
+                                              square under the root (d sqrt(a) = da / (2 sqrt(a))), sqrtf itself
+      xp   = sqrt(a_prev) p0 + dir e + sigma noise
+      dxp  = sqrt(a_prev) dp0 + dir de + ddir |e| + 3 U32 (T + dT),  T = sqrt(a_prev) |p0| + dir |e| + |sigma noise|
+                                              -- sqrtf(a_prev) and the three products, the two additions of the three-term sum
+    ``pred_x0`` is p0 with dp0.  The recon twin (mode 0): e_r = er + s (er - eu) and the same chain from ``inv``, without noise.
+    Returns a dict name -> ``(ref, bound)`` for ``x_prev``, ``pred_x0`` and (mode 0 with ``inv``) ``x_prev_recon``."""
+    f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    s, a_t, a_prev, sg, c = f32(scale), f32(a_t), f32(a_prev), f32(sigma_t), f32(sqrt_1m_at)
+    sat, sap = math.sqrt(a_t), math.sqrt(a_prev)
+    dirv = math.sqrt(1.0 - a_prev - sg * sg)
+    ddir = 3 * U32 / (2 * dirv) + 2 * U32 * dirv
+
+    def chain(base, diff, x0, nz):
+        # e = base + s diff: the guidance eu + s (ec - eu), the recon twin er + s (er - eu), or one branch alone (diff None)
+        e = base.double()
+        de = torch.zeros_like(e)
+        if diff is not None:
+            e = base.double() + s * diff
+            de = 3 * U32 * (base.double().abs() + abs(s) * diff.abs())
+        x64 = x0.double()
+        mag = x64.abs() + c * e.abs()
+        p0 = (x64 - c * e) / sat
+        dp0 = (c * de + 2 * U32 * mag) / sat + 4 * U32 * mag / sat
+        t3 = sg * nz.double() if nz is not None else torch.zeros_like(p0)
+        xp = sap * p0 + dirv * e + t3
+        T = sap * p0.abs() + dirv * e.abs() + t3.abs()
+        dT = sap * dp0 + dirv * de + ddir * e.abs()
+        return (xp, dT + 3 * U32 * (T + dT)), (p0, dp0)
+
+    out = {}
+    out["x_prev"], out["pred_x0"] = chain(eu, None if single == 1 else ec.double() - eu.double(), x, noise)
+    if single == 0 and inv is not None:
+        out["x_prev_recon"], _ = chain(er, er.double() - eu.double(), inv, None)
+    return out
+
+
+def timestep_embedding_ref_and_bound(t, dim, dt):
+    """``vface_timestep_embedding``: fp64 cos / sin of the fp32-rounded chain of util.py:151-171 (freqs = exp(-ln(10000) i / half)
+    and args = t * freqs in torch fp32 on the CPU), the zero pad of an odd ``dim``, and
+
+      bound = 8 U32 |arg| + 4 U32 + 0.5 ulp(|ref| + that, dt)
+
+    * 8 U32 |arg|: the kernel's freq and torch's are two fp32 evaluations of the same exp of the same fp32 argument (the product
+      with i and the division by half are single IEEE operations on both sides): expf within 2 ulp = 4 U32 relative on the
+      device, torch's within 1 ulp = 2 U32; then the product t * freq, one rounding on each side: 2 U32.  |cos'|, |sin'| <= 1, so
+      an error of the argument is an error of the result.
+    * 4 U32: cosf / sinf within 2 ulp of a result no larger than 1, at any argument up to 999 (full-range reduction).
+    * one rounding to ``dt``."""
+    half = dim // 2
+    freqs = torch.exp(-math.log(10000) * torch.arange(0, half, dtype=torch.float32) / half)
+    args = (t[:, None].float() * freqs[None]).double()
+    ref = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
+    e = (8 * U32 * args.abs() + 4 * U32).repeat(1, 2)
+    if dim % 2:
+        ref, e = torch.cat([ref, torch.zeros_like(ref[:, :1])], -1), torch.cat([e, torch.zeros_like(e[:, :1])], -1)
+    return ref, as_16bit(ref, e, dt)

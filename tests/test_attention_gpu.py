@@ -42,13 +42,21 @@ def _strided(x, ld, gap_rows, off, nan):
     return buf, off, ld, bs
 
 
-def _launch(h, q, k, v, *, heads, dh, scale, nan=True, **kw):
-    """``q [B, n, d]``, ``k [B, nk, d]``, ``v [Bo, nk, d]`` on the CPU (Bo = B, or the live value sets x B of the shared-score form)
-    -> the kernel's ``[Bo, n, d]`` on the CPU, after the checks on what the call must not touch."""
+def _launch(h, q, k, v, *, heads, dh, scale, nan=True, dead=(), **kw):
+    """``q [B, n, d]``, ``k [B, nk, d]``, ``v [Bo, nk, d]`` on the CPU -> the kernel's ``[Bo, n, d]`` on the CPU, after the checks on what
+    the call must not touch.  Bo = B, or for the shared-score form (``v_sets``, ``set_stride`` [, ``v_sets_live``] in ``kw``)
+    (v_sets - 1) set_stride + B: output sample b + g set_stride takes the probabilities of q, k sample b and v of that sample.
+    ``dead``: samples of v and of the output that the call must neither read nor write -- a gap sample between two sets and, with 2
+    live sets of 3, the third set.  They lie INSIDE both allocations: their v is poison (NaN or +-6e4), their output keeps its
+    sentinel bits; a kernel that touches them shows as a wrong value or a changed sentinel, never as an access out of bounds."""
     B, n, d = q.shape
     nk, Bo = k.shape[1], v.shape[0]
     dt = q.dtype
-    assert d == heads * dh
+    assert d == heads * dh and Bo == (kw.get("v_sets", 1) - 1) * kw.get("set_stride", 0) + B
+    dead = sorted(dead)
+    if dead:
+        v = v.clone()
+        v[dead] = _poisoned(nk * d, dt, nan).reshape(nk, d)
     (qb, qo, ldq, bsq), (kb, ko, ldk, bsk), (vb, vo, ldv, bsv) = (_strided(t, d + p, g, 8, nan) for t, p, g in ((q, 24, 1), (k, 40, 2), (v, 56, 3)))
     ldo, bso, oo = d + 12, (n + 2) * (d + 12), 4
     keep = sentinel(1, oo + Bo * bso + ldo, dt).flatten()
@@ -60,8 +68,9 @@ def _launch(h, q, k, v, *, heads, dh, scale, nan=True, **kw):
     view = lambda t: t[oo:oo + Bo * bso].as_strided((Bo, n, d), (bso, ldo, 1))
     got = view(got_all).clone()
     expect = keep.clone()
-    view(expect).copy_(got)
-    assert same_bits(got_all, expect), "a store outside the output view"
+    written = [s for s in range(Bo) if s not in dead]
+    view(expect)[written] = got[written]
+    assert same_bits(got_all, expect), "a store outside the output view (or into a dead sample of it)"
     assert same_bits(qd.cpu(), qb) and same_bits(kd.cpu(), kb) and same_bits(vd.cpu(), vb), "an input changed"
     return got
 
