@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VFACE_ABI_VERSION 8   /* 8: 7 minus the composite hooked-attn1 call and its workspace query (a hooked attn1 is a sequence of single-kernel calls issued by the caller), nothing else changed; 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
+#define VFACE_ABI_VERSION 8   /* 8 (later additions, nothing changed): + vface_clip_patches, vface_clip_embed, vface_act, vface_cond_mix (the conditioning stage) and vface_attention at dh = 64; 8: 7 minus the composite hooked-attn1 call and its workspace query (a hooked attn1 is a sequence of single-kernel calls issued by the caller), nothing else changed; 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
 
 #define VFACE_OK 0
 #define VFACE_ERR_ARG (-1)
@@ -163,7 +163,7 @@ int vface_upsample2x_conv3x3_phase(const void* X, int64_t ldx, int nimg, int H, 
                                    int64_t ld_colstats, void* stream, const vface_stream32* s32);
 
 /* O = softmax(Q K^T * scale) V per (sample, head), streaming softmax, no [n x n] matrix.
- * Replaces attention.py:206-220 / pnp_utils.py:270-285.  Output sample b uses q,k of sample qk_map[b] and
+ * Replaces attention.py:206-220 / pnp_utils.py:270-285, and at dh = 64 the self-attention of the CLIP image tower.  Output sample b uses q,k of sample qk_map[b] and
  * v of sample v_map[b] (NULL = identity): the zero-copy form of the hook's q/k/v row assignments. */
 int vface_attention(const void* Q, const void* K, const void* V, int64_t ldq, int64_t ldk, int64_t ldv, int64_t bsq,
                     int64_t bsk, int64_t bsv, const int32_t* qk_map, const int32_t* v_map, void* O, int64_t ldo,
@@ -364,6 +364,49 @@ int vface_pooled_linear(const float* a, int64_t lda, int sa, const float* W, con
  *   ncls .. ld - 1 may hold anything); out [nframes][H][W] uint8 = table[first maximal class].  ld % 4 == 0. */
 int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h, int w, int ncls, const uint8_t* table,
                              uint8_t* out, int H, int W, void* stream);
+
+/* ---- conditioning: the CLIP ViT image embedder, its mapper and the feature mix -----------------------------------------------
+ * The reference runs `FrozenCLIPEmbedder` (REFace/ldm/modules/encoders/modules.py:211-264: HF CLIPVisionModel ViT-L/14, pooled output,
+ * visual_projection, `mapper2` of encoders/xf.py, `final_ln2`) on every batch of target frames (scripts/VFace_inference_batch.py:442,
+ * :500 -> ddpm.py:872-1045 `conditioning_with_feat`) in stock PyTorch.  Its projections are vface_gemm (q | k | v as one [3 C][C]
+ * weight, the residual adds through vface_stream32), its attention vface_attention at dh = 64 on the three strided thirds of that
+ * buffer, its LayerNorms vface_layernorm (in_f32); these entry points are the rest.  All: raw device pointers, no allocation, no
+ * synchronisation, capturable; a refusal launches nothing; no atomics (a sample's bits do not depend on the batch).
+ *
+ * vface_clip_patches: the image as the patch matrix of CLIPVisionEmbeddings.patch_embedding (Conv2d 14 x 14, stride 14, no bias):
+ *   out [B * grid * grid][ldo >= 640] 16-bit, row (b, py, px), column c * 196 + ky * 14 + kx -- the flattening of the weight
+ *   [hidden][3][14][14] -- columns 588 .. 639 zero (K padded to a multiple of 64), so the embedding is one vface_gemm with K = 640.
+ *   img fp32 planar [B][3][H][W].  prep == 0: img is already CLIP-normalised at 14 grid x 14 grid and is copied (one rounding).
+ *   prep == 1: img is in [-1, 1] at any size -- ddpm.py:907-912 `un_norm`, `TF.normalize(CLIP mean, std)`, `TF.resize((224, 224))`
+ *   (bilinear, align_corners false, NO antialias: what torchvision 0.14.1 does to a tensor; fp32 in vface_frame_normalise_resize's
+ *   order); mask (optional, fp32 [B][H][W] = inpaint_mask): every pixel is first multiplied by (1 - mask)
+ *   (scripts/VFace_inference_batch.py:493-496, where the normalisation follows the resize: equal up to fp32 rounding, the bilinear
+ *   weights sum to 1).  dbg_x0 / dbg_y0 (optional, prep only, int32 [14 grid] each): the first source column / row of every output
+ *   column / row.  grid <= 64. */
+int vface_clip_patches(const float* img, int H, int W, const float* mask, int prep, void* out, int64_t ldo, int B, int grid,
+                       int32_t* dbg_x0, int32_t* dbg_y0, int dtype, void* stream);
+
+/* vface_clip_embed: CLIPVisionEmbeddings.forward behind the convolution (`cat([class_embedding, patch_embeds]) + position_embedding`)
+ *   and, with gamma / beta, CLIPVisionTransformer's `pre_layrnorm` (the reference's spelling) on the sum:
+ *   x32 [B * (patches + 1)][ldo] fp32: row b (patches + 1) from cls + pos[0], row b (patches + 1) + 1 + p from tok[b patches + p] +
+ *   pos[1 + p]; gamma == beta == NULL: the sums themselves; otherwise their LayerNorm (fp32 two-pass statistics, eps), so the fp32
+ *   residual stream starts unrounded.  tok [B * patches][ldt]: the patch GEMM's output, 16-bit, or fp32 when tok_f32 (the out32
+ *   carrier of vface_stream32); cls, gamma, beta fp32 [C], pos fp32 [patches + 1][C].  C % 8 == 0. */
+int vface_clip_embed(const void* tok, int64_t ldt, int tok_f32, const float* cls, const float* pos, const float* gamma, const float* beta,
+                     float eps, float* x32, int64_t ldo, int B, int patches, int C, int dtype, void* stream);
+
+/* vface_act: an activation on a 16-bit matrix view x [rows][ldx] -> y [rows][ldy] (y may be x), fp32 inside, one rounding.
+ *   kind 0: quick_gelu v * sigmoid(1.702 v) (HF activations.py QuickGELUActivation, the ViT's MLP); kind 1: the erf GELU
+ *   (encoders/xf.py MLP `nn.GELU()` of the mapper).  cols % 8 == 0. */
+int vface_act(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, int kind, int dtype, void* stream);
+
+/* vface_cond_mix: ddpm.py:1038-1039 `(c * clip_weight + c2 * ID_weight + landmarks * Landmarks_weight) / (sum of the weights)`:
+ *   out[b][n] = (a w_a + b w_b + c w_c) / w_sum in fp32, summed left to right; operands fp32, contiguous [rows_x][N] with rows_x = B,
+ *   or 1 for one row shared by every sample (the source's features); a NULL operand is left out (:1018-1019 without landmarks).
+ *   w_sum is passed in (the reference forms it in double and rounds once).  out32 fp32 [B][ldo32] and / or out16 16-bit [B][ldo16].
+ *   N % 4 == 0. */
+int vface_cond_mix(const float* a, int rows_a, float w_a, const float* b, int rows_b, float w_b, const float* c, int rows_c, float w_c,
+                   float w_sum, float* out32, int64_t ldo32, void* out16, int64_t ldo16, int B, int N, int dtype, void* stream);
 
 /* The FeedForward third of BasicTransformerBlock._forward in ONE launch (REFace/ldm/modules/attention.py:243 `x = ff(norm3(x)) + x`,
  * FeedForward / GEGLU :37-64, LayerNorm :233):  out = W2 (a * gelu(g)) + b2 + x,  [a ; g] = W1 LN(x) + b1.

@@ -705,6 +705,7 @@ int dispatch_l(const AttnParams& p, hipStream_t stream) {
             // four-wave form): 2 472 -> 2 388 us at 96 samples, 1 268 -> 1 201 at 48, 679 -> 600 at 24 (profiles/r05_m; in round 3,
             // before the speculative reference, the two forms measured equal); variant bit 3: four waves (A/B)
             return (p.variant & 8) ? launch<TT, 40, 4, 1, LAZY>(p, stream) : launch<TT, 40, 4, 1, LAZY, false, 8>(p, stream);
+        case 64: return launch<TT, 64, 2, 1, LAZY>(p, stream);      // the CLIP ViT-L/14 image tower (16 heads of 64, 257 tokens)
         case 80:
             // (the four-query-tiles-per-wave A/B form of rounds 3-5 spilled 28 B at 256 registers and lost its A/B: not built)
             if (p.variant & 8) return launch<TT, 80, 2, 1, LAZY, false, 8>(p, stream);                 // A/B: eight waves per workgroup

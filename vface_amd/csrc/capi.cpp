@@ -299,6 +299,25 @@ int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h
     return vf_launch_upsample_argmax_u8(logits, ld, nframes, h, w, ncls, table, out, H, W, S(stream));
 }
 
+int vface_clip_patches(const float* img, int H, int W, const float* mask, int prep, void* out, int64_t ldo, int B, int grid,
+                       int32_t* dbg_x0, int32_t* dbg_y0, int dtype, void* stream) {
+    return vf_launch_clip_patches(img, H, W, mask, prep, out, ldo, B, grid, dbg_x0, dbg_y0, dtype, S(stream));
+}
+
+int vface_clip_embed(const void* tok, int64_t ldt, int tok_f32, const float* cls, const float* pos, const float* gamma, const float* beta,
+                     float eps, float* x32, int64_t ldo, int B, int patches, int C, int dtype, void* stream) {
+    return vf_launch_clip_embed(tok, ldt, tok_f32, cls, pos, gamma, beta, eps, x32, ldo, B, patches, C, dtype, S(stream));
+}
+
+int vface_act(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, int kind, int dtype, void* stream) {
+    return vf_launch_act(x, ldx, y, ldy, rows, cols, kind, dtype, S(stream));
+}
+
+int vface_cond_mix(const float* a, int rows_a, float w_a, const float* b, int rows_b, float w_b, const float* c, int rows_c, float w_c,
+                   float w_sum, float* out32, int64_t ldo32, void* out16, int64_t ldo16, int B, int N, int dtype, void* stream) {
+    return vf_launch_cond_mix(a, rows_a, w_a, b, rows_b, w_b, c, rows_c, w_c, w_sum, out32, ldo32, out16, ldo16, B, N, dtype, S(stream));
+}
+
 int vface_ffn_fused_supported(int64_t M, int C) { return vf_ffn_fused_supported((long)M, C) ? 1 : 0; }
 
 int vface_ffn_fused(const float* x32, int64_t ldx, const float* gamma, const float* beta, float eps, const void* W1, const float* b1,

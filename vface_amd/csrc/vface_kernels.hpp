@@ -239,6 +239,14 @@ int vf_launch_pooled_linear(const float* a, long lda, int sa, const float* W, co
                             int K, int act, hipStream_t stream);
 int vf_launch_upsample_argmax_u8(const float* logits, long ld, int nframes, int h, int w, int ncls, const unsigned char* table,
                                  unsigned char* out, int H, int W, hipStream_t stream);
+// clip.hip: glue of the CLIP image embedder and the conditioning mix (ldm/modules/encoders/modules.py:211-264, ddpm.py:872-1045)
+int vf_launch_clip_patches(const float* img, int H, int W, const float* mask, int prep, void* out, long ldo, int B, int G, int* dbg_x0,
+                           int* dbg_y0, int dtype, hipStream_t stream);
+int vf_launch_clip_embed(const void* tok, long ldt, int tok_f32, const float* cls, const float* pos, const float* gamma,
+                         const float* beta, float eps, float* x32, long ldo, int B, int P, int C, int dtype, hipStream_t stream);
+int vf_launch_act(const void* x, long ldx, void* y, long ldy, long rows, int cols, int kind, int dtype, hipStream_t stream);
+int vf_launch_cond_mix(const float* a, int rows_a, float wa, const float* b, int rows_b, float wb, const float* c, int rows_c, float wc,
+                       float wsum, float* out32, long ldo32, void* out16, long ldo16, int B, int N, int dtype, hipStream_t stream);
 int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, int dtype, hipStream_t stream);
 int vf_launch_silu(const void* x, void* y, long count, int in_f32, int dtype, hipStream_t stream);
 int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, int N, float scale, int dtype, hipStream_t stream);

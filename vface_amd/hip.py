@@ -89,6 +89,10 @@ SIGNATURES = {
     "vface_channel_gate": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "vface_pooled_linear": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "vface_upsample_argmax_u8": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp]),
+    "vface_clip_patches": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "vface_clip_embed": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "vface_act": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "vface_cond_mix": (C.c_int, [_vp, _i32, _f32, _vp, _i32, _f32, _vp, _i32, _f32, _f32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
     "vface_ffn_fused_supported": (C.c_int, [_i64, _i32]),
     "vface_ffn_fused": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
     "vface_attn_out_ffn_fused": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp,
@@ -853,3 +857,61 @@ def conv3x3_plus_1x1(x: torch.Tensor, x2: torch.Tensor, wt: torch.Tensor, out: t
                                     colstats.stride(0) // 2 if colstats is not None else 0, _p(ws), ws_bytes, _stream(),
                                     _s32(None, out32, gn_ab, gn_silu))
     _check(rc, "vface_conv3x3_plus_1x1")
+
+
+# ---------------------------------------------------------------------------------------------- conditioning (csrc/clip.hip)
+CLIP_PATCH, CLIP_PATCH_K, CLIP_PATCH_KP = 14, 588, 640      # the patch convolution's window, its K = 3 * 14 * 14 and K padded to 64
+ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1
+
+
+def clip_patches(img: torch.Tensor, out: torch.Tensor, *, B: int, grid: int, H: int, W: int, ldo: int, prep: bool, mask=None,
+                 dbg_x0=None, dbg_y0=None):
+    """``img`` fp32 planar [B, 3, H, W] -> the patch matrix ``out`` [B grid grid, >= 640] (16-bit), column c 196 + ky 14 + kx, zero
+    from 588 on.  ``prep``: un_norm + CLIP normalise + bilinear resize to 14 grid (``mask`` fp32 [B, H, W]: times (1 - mask) first);
+    otherwise a copy of an already normalised 14 grid x 14 grid image."""
+    for t in (img, mask):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise VFaceHipError("clip_patches: img / mask must be contiguous fp32")
+    for t in (dbg_x0, dbg_y0):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < CLIP_PATCH * grid):
+            raise VFaceHipError("clip_patches: dbg_x0 / dbg_y0 must be int32 [14 grid]")
+    rc = load().vface_clip_patches(_p(img), H, W, _p(mask), int(prep), _p(out), ldo, B, grid, _p(dbg_x0), _p(dbg_y0),
+                                   dtype_code(out.dtype), _stream())
+    _check(rc, "vface_clip_patches")
+
+
+def clip_embed(tok: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, x32: torch.Tensor, *, B: int, patches: int, C_: int, ldt: int,
+               ldo: int, gamma=None, beta=None, eps: float = 1e-5):
+    """x32 [B (patches + 1), C] fp32 = the class row and the patch rows ``tok`` (16-bit or fp32) plus the position table; with
+    ``gamma`` / ``beta`` (fp32 [C]) the LayerNorm of those rows (``pre_layrnorm``)."""
+    f32 = tok.dtype == torch.float32
+    for t in (cls, pos, x32, gamma, beta):
+        if t is not None and t.dtype != torch.float32:
+            raise VFaceHipError("clip_embed: cls, pos, gamma, beta and x32 must be fp32")
+    if not pos.is_contiguous():
+        raise VFaceHipError("clip_embed: pos must be contiguous [patches + 1, C]")
+    rc = load().vface_clip_embed(_p(tok), ldt, int(f32), _p(cls), _p(pos), _p(gamma), _p(beta), eps, _p(x32), ldo, B, patches, C_,
+                                 F16 if f32 else dtype_code(tok.dtype), _stream())
+    _check(rc, "vface_clip_embed")
+
+
+def act(x: torch.Tensor, y: torch.Tensor, *, rows: int, cols: int, ldx: int, ldy: int, kind: int):
+    """y = quick_gelu(x) (``ACT_QUICK_GELU``) or erf-GELU(x) (``ACT_GELU_ERF``) on 16-bit [rows, cols] views; ``y`` may be ``x``."""
+    rc = load().vface_act(_p(x), ldx, _p(y), ldy, rows, cols, kind, dtype_code(x.dtype), _stream())
+    _check(rc, "vface_act")
+
+
+def cond_mix(operands, *, B: int, N: int, out32=None, out16=None, ldo32: int = 0, ldo16: int = 0, w_sum: Optional[float] = None):
+    """``operands``: three ``(tensor | None, weight)`` pairs, each tensor contiguous fp32 [B, N] or [1, N] (one row for every sample):
+    out = (a w_a + b w_b + c w_c) / w_sum, ``w_sum`` defaulting to the sum of the weights of the operands present."""
+    assert len(operands) == 3
+    args = []
+    for t, w in operands:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() % N):
+            raise VFaceHipError("cond_mix: operands must be contiguous fp32 [B | 1, N]")
+        args += [_p(t), t.numel() // N if t is not None else 0, float(w)]
+    if w_sum is None:
+        w_sum = sum(float(w) for t, w in operands if t is not None)
+    rc = load().vface_cond_mix(*args, float(w_sum), _p(out32), ldo32, _p(out16), ldo16, B, N,
+                               dtype_code(out16.dtype) if out16 is not None else F16, _stream())
+    _check(rc, "vface_cond_mix")

@@ -3,7 +3,10 @@
 ``conditioning_key: crossattn``, plus the schedule buffers of ``DDPM.register_schedule`` the sampler reads.
 The first-stage VAE is optional: ``first_stage_config`` builds ``AutoencoderKL`` under ``first_stage_model``
 and ``encode_first_stage`` / ``get_first_stage_encoding`` / ``decode_first_stage`` (:1402, :850-857, :1277-1284) work as in
-the reference.  Conditioning encoders, losses and training (the other ~2200 lines) are out of scope.
+the reference.  The conditioning stage is optional too: ``cond_stage_config`` builds ``FrozenCLIPEmbedder`` under
+``cond_stage_model`` with the projections of ddpm.py:695-733, and ``get_learned_conditioning`` (:859-870) /
+``conditioning_with_feat`` (:872-1045, the shipped configuration) run on the GPU; the ArcFace features and the dlib landmarks stay
+inputs.  Losses and training (the other ~2000 lines) are out of scope.
 
 State-dict keys of the UNet are ``model.diffusion_model.*`` as in ``last.ckpt`` so
 ``load_state_dict(ckpt["state_dict"], strict=False)`` (VFace_inference_batch.py:118-135) fills it unchanged.
@@ -33,12 +36,15 @@ class DiffusionWrapper(nn.Module):
 
 class LatentDiffusion(nn.Module):
     def __init__(self, unet_config: dict, timesteps=1000, linear_start=0.00085, linear_end=0.012,
-                 beta_schedule="linear", scale_factor=0.18215, parameterization="eps", first_stage_config=None):
+                 beta_schedule="linear", scale_factor=0.18215, parameterization="eps", first_stage_config=None,
+                 cond_stage_config=None):
         super().__init__()
         self.model = DiffusionWrapper(UNetModel(**unet_config))
         if first_stage_config is not None:
             from ..autoencoder import AutoencoderKL
             self.first_stage_model = AutoencoderKL(**first_stage_config)
+        if cond_stage_config is not None:
+            self._init_cond_stage(dict(cond_stage_config))
         self.parameterization = parameterization
         self.scale_factor = scale_factor
         self.num_timesteps = int(timesteps)
@@ -74,6 +80,108 @@ class LatentDiffusion(nn.Module):
             raise NotImplementedError("predict_cids belongs to VQ first stages; the VFace configuration uses AutoencoderKL")
         return self.first_stage_model.decode(1. / self.scale_factor * z)
 
+    # ---- conditioning stage (ddpm.py:598-733, 859-870, 872-1045; project_ffhq.yaml:79-99) ----
+    def _init_cond_stage(self, cfg: dict):
+        from ...modules.encoders.modules import FrozenCLIPEmbedder
+        target = cfg.get("target", "ldm.modules.encoders.modules.FrozenCLIPEmbedder")
+        if not target.endswith("encoders.modules.FrozenCLIPEmbedder"):
+            raise NotImplementedError(f"cond_stage_config.target {target!r}: the shipped configuration uses FrozenCLIPEmbedder")
+        op = {**FFHQ_COND_PARAMS, **cfg.get("other_params", {})}
+        add = {**FFHQ_COND_PARAMS["Additional_config"], **op.get("Additional_config", {})}
+        for flag in ("concat_feat", "land_mark_id_seperate_layers", "multi_scale_ID", "sep_head_att", "stack_feat", "normalize"):
+            if op.get(flag, False):
+                raise NotImplementedError(f"other_params.{flag} is false in the shipped configuration (project_ffhq.yaml:87-90)")
+        if not (add["Source_CLIP_feat"] and add["Target_CLIP_feat"] and op["Landmark_cond"] and op["weight_division"]):
+            raise NotImplementedError("the shipped configuration has Source_CLIP_feat, Target_CLIP_feat, Landmark_cond and weight_division on")
+        if not (op["clip_weight"] > 0 and op["ID_weight"] > 0):
+            raise NotImplementedError("the shipped configuration mixes CLIP and identity features (clip_weight 1.0, ID_weight 10.0)")
+        self.clip_weight, self.ID_weight, self.Landmarks_weight = float(op["clip_weight"]), float(op["ID_weight"]), float(op["Landmarks_weight"])
+        self.Landmark_cond, self.weight_division, self.normalize = True, True, False
+        self.Source_CLIP_feat = self.Target_CLIP_feat = True
+        self.cond_stage_model = FrozenCLIPEmbedder(**cfg.get("params", {}))
+        self.learnable_vector = nn.Parameter(torch.randn((1, 1, 768)), requires_grad=False)
+        self.proj_out_source, self.proj_out_target = nn.Linear(768, 768), nn.Linear(768, 768)
+        self.proj_out = nn.Identity()
+        self.ID_proj_out = nn.Linear(512, 768)
+        self.landmark_proj_out = nn.Linear(136, 768)
+        self._cond_packed = None
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """With a conditioning stage, the checkpoint's ``cond_stage_model.*`` keys that FrozenCLIPEmbedder holds without reading
+        (the text tower, ``mapper``, ``final_ln``, ``projection_back``) are dropped before loading."""
+        if hasattr(self, "cond_stage_model"):
+            from .... import clip
+            pre = "cond_stage_model."
+            state_dict = {k: v for k, v in state_dict.items()
+                          if not (k.startswith(pre) and k[len(pre):].startswith(clip.UNUSED_PREFIXES))}
+            self.cond_stage_model._engine = None
+            self._cond_packed = None
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def _apply(self, fn, *a, **k):
+        self._cond_packed = None
+        return super()._apply(fn, *a, **k)
+
+    def get_learned_conditioning(self, c):
+        return self.cond_stage_model.encode(c)
+
+    def _cond_weights(self):
+        """The four projections in the compute type (landmark_proj_out's K = 136 zero-padded to 192), built on first use."""
+        if self._cond_packed is None:
+            dt = self.cond_stage_model.compute_dtype
+            pk = {}
+            for name in ("proj_out_source", "proj_out_target", "ID_proj_out", "landmark_proj_out"):
+                lin = getattr(self, name)
+                w = lin.weight.detach().float()
+                if w.shape[1] % 64:
+                    w = torch.cat([w, w.new_zeros(w.shape[0], -w.shape[1] % 64)], 1)
+                pk[name] = (w.to(dt).contiguous(), lin.bias.detach().float().contiguous())
+            self._cond_packed = pk
+        return self._cond_packed
+
+    @torch.no_grad()
+    def conditioning_with_feat(self, x, landmarks=None, tar=None, id_feat=None, *, e_src=None, e_tar=None):
+        """ddpm.py:872-1045 in the shipped configuration, ``[B, 1, 768]`` fp32:
+            c  = proj_out_source(E(x)) + proj_out_target(E(prep(tar)))            x [1 | B, 3, 224, 224] CLIP-normalised
+            c2 = ID_proj_out(id_feat)[:, None]                                    id_feat [B, 512]: the ArcFace features, an INPUT here
+            lm = landmark_proj_out(landmarks)[:, None]                            landmarks [B, 136]: dlib's, an input as in the reference
+            (c clip_weight + c2 ID_weight + lm Landmarks_weight) / (clip_weight + ID_weight + Landmarks_weight)
+        ``e_src`` / ``e_tar``: E(x) / E(prep(tar)) where the caller already has them -- a clip's source image is encoded once, and
+        both conditions of a batch (scripts/VFace_inference_batch.py:442, :500) share E(prep(tar))."""
+        from .... import hip
+        if landmarks is None or id_feat is None or (tar is None and e_tar is None) or (x is None and e_src is None):
+            raise NotImplementedError("the shipped configuration mixes CLIP (source and target), identity and landmark features: "
+                                      "x, tar, landmarks and id_feat are all needed (id_feat = face_ID_model.extract_feats(x)[0], not computed here)")
+        enc, pk = self.cond_stage_model, self._cond_weights()
+        dt, dev = enc.compute_dtype, landmarks.device
+        if e_tar is None:
+            e_tar = enc.encode_from_frames(tar)
+        if e_src is None:
+            e_src = self.get_learned_conditioning(x)
+        B, Bs = e_tar.shape[0], e_src.shape[0]
+        if Bs not in (1, B):
+            raise ValueError(f"{Bs} source images for {B} target frames")
+        f32 = lambda: torch.empty(B, 768, dtype=torch.float32, device=dev)
+
+        def linear(a, name, M, out32, **kw):
+            w, b = pk[name]
+            hip.gemm(a, w, None, M=M, N=768, K=w.shape[1], lda=a.stride(0), ldc=768, bias=b, out32=out32, split_k=False, **kw)
+
+        def staged(t, K):       # a [B, k] fp32 input as zero-padded 16-bit rows
+            buf = torch.zeros(B, K, dtype=dt, device=dev)
+            buf[:, :t.shape[-1]] = t.reshape(B, -1).to(device=dev, dtype=dt)
+            return buf
+
+        c_src = torch.empty(Bs, 768, dtype=torch.float32, device=dev)
+        linear(e_src.view(Bs, 768), "proj_out_source", Bs, c_src)
+        c, c2, lm = f32(), f32(), f32()
+        linear(e_tar.view(B, 768), "proj_out_target", B, c, rowbias=c_src, rows_per_sample=B if Bs == 1 else 1)
+        linear(staged(id_feat, 512), "ID_proj_out", B, c2)
+        linear(staged(landmarks, pk["landmark_proj_out"][0].shape[1]), "landmark_proj_out", B, lm)
+        out = f32()
+        hip.cond_mix([(c, self.clip_weight), (c2, self.ID_weight), (lm, self.Landmarks_weight)], B=B, N=768, out32=out, ldo32=768)
+        return out.view(B, 1, 768)
+
     def apply_model(self, x_noisy, t, cond):
         if isinstance(cond, dict):
             return self.model(x_noisy, t, **cond)
@@ -81,6 +189,11 @@ class LatentDiffusion(nn.Module):
             cond = [cond]
         return self.model(x_noisy, t, c_crossattn=cond)
 
+
+# project_ffhq.yaml:81-99 (+ the defaults of ddpm.py:644-647 for what the yaml leaves out)
+FFHQ_COND_PARAMS = dict(clip_weight=1.0, ID_weight=10.0, Landmark_cond=True, Landmarks_weight=0.05, concat_feat=False,
+                        land_mark_id_seperate_layers=False, multi_scale_ID=False, sep_head_att=False, weight_division=True,
+                        Additional_config=dict(Target_CLIP_feat=True, Source_CLIP_feat=True))
 
 # project_ffhq.yaml:33-56
 FFHQ_UNET_CONFIG = dict(image_size=32, in_channels=9, out_channels=4, model_channels=320,

@@ -6,7 +6,9 @@ shipped hook schedule.  Everything around it in the reference -- video decoding,
 CLIP/ArcFace/landmark conditioning, the KL-VAE and paste-back (``:193-528, 596-670``) -- is out of scope of this
 build: it needs checkpoints and third-party models that are not available offline.  ``--synthetic``
 therefore stands in for those stages with seeded synthetic latents / conditioning / flow of the right shapes and
-writes the denoised latents; without it the script stops with a message saying what is missing.
+writes the denoised latents; without it the script stops with a message saying what is missing.  The widening flags
+(``--with_vae``, ``--raft_flow``, ``--intake``, ``--parse``, ``--paste_back``, ``--clip_cond``) replace one stand-in each by the
+stage itself on the GPU (synthetic weights unless ``--ckpt`` covers it).
 
     python -m vface_amd.scripts.VFace_inference_batch --synthetic --n_frames 24 --n_samples 8 --ddim_steps 50
 """
@@ -83,6 +85,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--with_vae", action="store_true",
                    help="synthetic run through the first-stage KL-VAE too: the inpaint latents come from encode_first_stage of "
                         "synthetic images (:456-457) and the samples are decoded to pixels (:596-600)")
+    p.add_argument("--clip_cond", action="store_true",
+                   help="the conditioning tokens come from the conditioning stage on the GPU -- FrozenCLIPEmbedder (ViT-L/14, mapper2) "
+                        "and conditioning_with_feat (:437-442, :491-500; vface_amd/clip.py) on the batch's frames: the intake's image "
+                        "and mask with --intake, seeded images otherwise -- instead of seeded N(0, 1); the ArcFace features, the "
+                        "landmarks and the source image stay seeded inputs")
     p.add_argument("--fusion", type=str, default="flow_fix", help="hook mode on the input-block attn1 modules")
     p.add_argument("--no_inversion", action="store_true", help="use random recon latents instead of DDIM inversion")
     p.add_argument("--flow_pixels", action="store_true",
@@ -181,8 +188,10 @@ class _StubUnpickler:
 def load_checkpoint(model, path: str, with_vae: bool = False, stub_unknown_globals: bool = False) -> str:
     """Load ``last.ckpt`` of the reference (``VFace_inference_batch.py:118-135``: ``torch.load`` -> ``["state_dict"]`` ->
     ``load_state_dict(strict=False)``) into ``model``.  Only the keys of what this build runs are taken:
-    ``model.diffusion_model.*`` always, ``first_stage_model.*`` when the first stage was built (``with_vae``); the CLIP /
-    ArcFace / landmark conditioning weights of a full LDM checkpoint are outside the path and ignored.  Unlike the reference's
+    ``model.diffusion_model.*`` always, ``first_stage_model.*`` when the first stage was built (``with_vae``),
+    ``cond_stage_model.*`` and the projections of ``conditioning_with_feat`` when the conditioning stage was built (the text tower
+    and the other entries FrozenCLIPEmbedder holds without reading are dropped); the ArcFace weights of a full LDM checkpoint
+    (``face_ID_model.*``) are outside the path and ignored.  Unlike the reference's
     non-strict load, a checkpoint that does not cover every parameter of the path raises instead of silently running on
     default-initialised weights.
 
@@ -204,6 +213,8 @@ def load_checkpoint(model, path: str, with_vae: bool = False, stub_unknown_globa
                 "allow-list and every other global becomes an inert placeholder") from e
     sd = ck.get("state_dict", ck) if isinstance(ck, dict) else ck
     prefixes = ("model.diffusion_model.",) + (("first_stage_model.",) if with_vae else ())
+    if hasattr(model, "cond_stage_model"):      # the conditioning stage was built: its encoder and the four projections load too
+        prefixes += ("cond_stage_model.", "proj_out_source.", "proj_out_target.", "ID_proj_out.", "landmark_proj_out.", "learnable_vector")
     taken = {k: v for k, v in sd.items() if k.startswith(prefixes) and torch.is_tensor(v)}
     if not taken:
         raise RuntimeError(f"{path}: no key starts with {prefixes} -- not an LDM checkpoint of this model "
@@ -278,18 +289,27 @@ def run_synthetic(opt) -> dict:
     dt = torch.float16 if opt.compute_dtype == "fp16" else torch.bfloat16
     cfg = load_unet_config(opt.config)
     cfg["compute_dtype"] = dt
+    clip_cond = bool(getattr(opt, "clip_cond", False))
+    stage_kw = dict(cond_stage_config=dict(params=dict(compute_dtype=dt))) if clip_cond else {}
     if opt.with_vae:
         from ..ldm.models.autoencoder import FFHQ_VAE_CONFIG
-        model = LatentDiffusion(cfg, first_stage_config=dict(FFHQ_VAE_CONFIG, compute_dtype=dt))
+        model = LatentDiffusion(cfg, first_stage_config=dict(FFHQ_VAE_CONFIG, compute_dtype=dt), **stage_kw)
     else:
-        model = LatentDiffusion(cfg)
+        model = LatentDiffusion(cfg, **stage_kw)
     if opt.ckpt:
         print(load_checkpoint(model, opt.ckpt, with_vae=opt.with_vae, stub_unknown_globals=opt.ckpt_stub_unknown_globals))
     else:
         synth.fill_module_(model.unet, seed=0)
         if opt.with_vae:
             synth.fill_module_(model.first_stage_model, seed=0, prefix="vae.")
+    if clip_cond and not opt.ckpt:
+        synth.fill_module_(model.cond_stage_model, seed=5)
+        for name in ("proj_out_source", "proj_out_target", "ID_proj_out", "landmark_proj_out"):
+            synth.fill_module_(getattr(model, name), seed=5, prefix=name + ".")
     model = model.to(dev).eval()
+    e_source = None
+    if clip_cond:       # :437: the source image, resized and CLIP-normalised, is encoded once per clip and broadcast
+        e_source = model.get_learned_conditioning(synth.synth_normal("cli.source224", (1, 3, 224, 224)).to(dev))
     sampler = DDIMSampler(model)
     sampler.hook_plan = HookPlan(fusion=opt.fusion, enabled=opt.fusion != "none")
     sampler.flow_gate = opt.flow_gate
@@ -330,7 +350,7 @@ def run_synthetic(opt) -> dict:
         d = lambda t: t.to(dev)
         stages = {}
         c, uc, tc = (d(synth.synth_normal(tag(k), (F_, 1, 768))) for k in ("c", "uc", "tc"))
-        img, frames, inv_tf, labels = None, None, None, None
+        img, frames, inv_tf, labels, inpaint_mask = None, None, None, None, None
         if intake is not None:
             frames, quads, labels = synthetic_intake_inputs(F_, opt.frame_size, opt.H, opt.W, opt.seed + 1000 + batch_id)
             frames, labels = d(frames), d(labels)
@@ -341,10 +361,10 @@ def run_synthetic(opt) -> dict:
                 ts_ = stage(stages, "intake", ts_)
                 labels = parser.labels(crops, convert_to_seg12=opt.seg12)
                 ts_ = stage(stages, "parse", ts_)
-                img, inpaint_image, _, mask = intake.tensors(crops, labels, REMOVE_MASK_TAR_FFHQ)
+                img, inpaint_image, inpaint_mask, mask = intake.tensors(crops, labels, REMOVE_MASK_TAR_FFHQ)
                 inv_tf = inv_transforms(quads, intake.image_size)
             else:
-                img, inpaint_image, _, mask, inv_tf = intake(frames, quads, labels, REMOVE_MASK_TAR_FFHQ)
+                img, inpaint_image, inpaint_mask, mask, inv_tf = intake(frames, quads, labels, REMOVE_MASK_TAR_FFHQ)
             ts_ = stage(stages, "intake", ts_)
             z_inp = model.get_first_stage_encoding(model.encode_first_stage(inpaint_image)).detach()     # :456-457
             stage(stages, "vae_encode", ts_)
@@ -357,6 +377,20 @@ def run_synthetic(opt) -> dict:
             z_inp = d(synth.synth_normal(tag("inp"), (F_, opt.C, h, w)) * 0.18215)
         if intake is None:
             mask = d(synth.synth_mask(F_, h, w))
+        if clip_cond:
+            # :442 c = conditioning_with_feat(source, landmarks, tar = the batch's frames); :491-500 the inversion's condition takes
+            # the masked frames in the source's place.  E(prep(tar)) is needed by both: once per batch
+            tar = img if img is not None else d(torch.stack([synth.synth_normal(tag(f"img{f}"), (3, opt.H, opt.W)).clamp(-1, 1)
+                                                             for f in range(F_)]))
+            keep = inpaint_mask if inpaint_mask is not None else d(synth.synth_mask(F_, opt.H, opt.W))
+            idf, idf_t = (d(synth.synth_normal(tag(k), (F_, 512))) for k in ("id_feat", "id_feat_tar"))
+            lmk = d(synth.synth_normal(tag("landmarks"), (F_, 136)) * 0.1 + 0.5)
+            ts_ = stage(stages, "_", time.time())
+            enc = model.cond_stage_model
+            e_tar = enc.encode_from_frames(tar)
+            c = model.conditioning_with_feat(None, landmarks=lmk, id_feat=idf, e_src=e_source, e_tar=e_tar)
+            tc = model.conditioning_with_feat(None, landmarks=lmk, id_feat=idf_t, e_src=enc.encode_from_frames(tar, keep), e_tar=e_tar)
+            stage(stages, "clip_cond", ts_)
         if opt.raft_flow:     # :550-553 flow = return_flow(target frames), pixel resolution
             from . import temporal_flow as tflow
             if raft is None:
