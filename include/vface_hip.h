@@ -133,10 +133,12 @@ int vface_conv3x3(const void* X, int64_t ldx, int nimg, int H, int W, int Cin, c
 
 /* Which kernel a vface_conv3x3 / vface_conv3x3_plus_1x1 (window = 3) / vface_upsample2x_conv3x3_phase (window = 2) launch of this
  * geometry runs: 1 = the patch-staged kernel (conv.hip: stride 1, H and W multiples of 16, Cin % 64 == 0, Cout % 160 == 0 or
- * % 128 == 0, 16-bit output, and a grid that is deep enough at the nominal 24-sample batch, or VFACE_TUNE_PATCH), 2 = its
- * 8x8 form (3x3 window on 8 x 8 images, Cout % 128 == 0: four images per workgroup, K split over channel chunks, then the
- * split-K reduce; taken when the caller passes the workspace vface_splitk_workspace_bytes asks for), 0 = the im2col-style
- * implicit GEMM (gemm.hip).  For measurement harnesses (bench.py prices the two kernels separately). */
+ * % 128 == 0, 16-bit output, and a grid of at least 160 tiles at the nominal batch of 24 samples -- NOMINAL_BATCH_CLIP of
+ * csrc/dispatch.cpp, where every rule of this family lives --, or VFACE_TUNE_PATCH), 2 = its 8x8 form (3x3 window on 8 x 8 images,
+ * Cout % 128 == 0: four images per workgroup, K split over channel chunks by the grid at NOMINAL_BATCH_STREAM = 48 samples, then
+ * the split-K reduce; taken when the caller passes the workspace vface_splitk_workspace_bytes asks for), 0 = the im2col-style
+ * implicit GEMM (gemm.hip).  The answer depends on the per-sample geometry only, never on a batch.  For measurement harnesses
+ * (bench.py prices the two kernels separately). */
 int vface_conv_uses_patch_kernel(int H, int W, int Cin, int Cout, int window, int stride, int upsample, int flags);
 
 /* Y = conv3x3(X) + X2 W2^T + bias: the second convolution of a ResBlock together with the block's 1x1 shortcut

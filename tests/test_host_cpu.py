@@ -417,7 +417,7 @@ def test_every_built_kernel_keeps_its_values_in_registers():
     """no instantiation that ships in libvface_hip.so carries scratch (a spilled kernel is a kernel whose schedule
     nobody chose) -- read from the code-object notes of csrc/build/*.o (tools/codeobj_audit.py; no GPU needed).  Round 5 still had
     eight: an attention A/B form, the 160-wide fused-GroupNorm convolution and the 160-wide 2 x 2 window with a residual operand;
-    they are no longer built (conv.hip launch_patch / vf_conv_patch_tile hand those launches the 128-wide tile or refuse them)."""
+    they are no longer built (dispatch.cpp conv_patch_tile hands those launches the 128-wide tile or refuses them)."""
     import glob
     import sys
     import tempfile

@@ -82,12 +82,7 @@ int vface_conv3x3(const void* X, int64_t ldx, int nimg, int H, int W, int Cin, c
 }
 
 int vface_conv_uses_patch_kernel(int H, int W, int Cin, int Cout, int window, int stride, int upsample, int flags) {
-    if (H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (window != 2 && window != 3)) return 0;
-    GemmParams p{};
-    p.mode = 1; p.H = H; p.W = W; p.OH = H; p.OW = W; p.Cin = Cin; p.N = Cout; p.stride = stride; p.upsample = upsample ? 1 : 0;
-    p.KH = p.KW = window; p.ntaps = window * window; p.pad = 1; p.pad_x = 1; p.flags = flags;
-    p.K = p.K1 = p.ntaps * Cin; p.rows_per_sample = H * W; p.M = 24 * H * W;
-    return vf_conv_kernel_choice(p, nullptr);     // the launcher's own rule (conv.hip), not a restatement of it
+    return vf_conv_uses_patch_kernel(H, W, Cin, Cout, window, stride, upsample, flags);     // the plan's own rule (dispatch.cpp), not a restatement of it
 }
 
 int vface_conv3x3_plus_1x1(const void* X, int64_t ldx, int nimg, int H, int W, int Cin, const void* X2, int64_t ldx2, int C2,

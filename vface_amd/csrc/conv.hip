@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int TP = 16;                 // output tile: TP x TP pixels of one image
+constexpr int TP = VF_PATCH_TP;        // output tile: TP x TP pixels of one image (16; dispatch.hpp)
 
 // DIAG: diagnostic build (flag 0x4000, tools/stamp_conv.py; never used by the engine): s_memtime stamps around the parts of
 // the kernel and of every K-tile period; the sums go to the colstats pointer as [workgroup][wave][8] floats and feed no output.
@@ -338,7 +338,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
         for (int i = 0; i < PPW; ++i) issue_P(c_begin, i);
         issue_T(c_begin);
     } else if constexpr (TAIL) {
-        // plain GEMM (vf_launch_gemm_patch): no window at all, every K tile is a tile of the halo-free "1x1 source"
+        // plain GEMM (the plan's GEMM_PATCH form, dispatch.cpp step 3): no window at all, every K tile is a tile of the halo-free "1x1 source"
         if (ntail > 0) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) issue_P2(0, i);
@@ -638,183 +638,45 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
 }
 
 template <class TT, int NT, int KH, int KW>
-int launch_patch(const GemmParams& p, hipStream_t stream) {
-    constexpr int BN = 32 * NT, TAPS = KH * KW, NSLOT = (TAPS % 3 == 0) ? 3 : 4;
-    constexpr int NPIECES = ((TP + KW - 1) * (TP + KH - 1) + 7) / 8;
-    const size_t lds = 2 * (size_t)NPIECES * 1024 + NSLOT * (size_t)BN * 128 + (KH == 3 ? 2048 : 0);
-    const int rm = p.res_f32 ? 2 : (p.residual ? 1 : 0);
-    // Every instantiation built here keeps its values in registers (0 B scratch: tools/codeobj_audit.py, tests/test_host_cpu.py).  Three
-    // forms did not at 160 channels per tile and are NOT built: the 2 x 2 window with a residual operand (12 / 16 B) and the fused
-    // GroupNorm (36 B) -- vf_conv_patch_tile hands such launches the 128-wide tile or none (the im2col kernel / an error for gn_ab).
+int launch_patch(const VfGemmPlan& pl, hipStream_t stream) {
+    // Every instantiation built here keeps its values in registers (0 B scratch: tools/codeobj_audit.py, tests/test_host_cpu.py).  Three forms did
+    // not at 160 channels per tile and are NOT built: the 2 x 2 window with a residual operand (12 / 16 B) and the fused GroupNorm (36 B); the plan
+    // hands such launches the 128-wide tile or none.
     auto kern = conv_patch_kernel<TT, NT, KH, KW, false, false, 0>;
+    bool built = pl.form == 0;
     if constexpr (!(KH == 2 && NT == 5)) {
-        if (rm == 2) kern = conv_patch_kernel<TT, NT, KH, KW, false, false, 2>;
-        else if (rm == 1) kern = conv_patch_kernel<TT, NT, KH, KW, false, false, 1>;
-    } else if (rm) return VF_ERR_SHAPE;
-    int which = rm;
+        if (pl.form == 2) { kern = conv_patch_kernel<TT, NT, KH, KW, false, false, 2>; built = true; }
+        else if (pl.form == 1) { kern = conv_patch_kernel<TT, NT, KH, KW, false, false, 1>; built = true; }
+    }
     if constexpr (NT == 5 && KH == 3 && sizeof(typename TT::elem) == 2) {
-        if (p.flags & 0x4000) { kern = conv_patch_kernel<TT, NT, KH, KW, true>; which = 3; }   // diagnostic stamps (tools/stamp_conv.py)
+        if (pl.form == 3) { kern = conv_patch_kernel<TT, NT, KH, KW, true>; built = true; }   // diagnostic stamps (tools/stamp_conv.py)
     }
     if constexpr (KH == 3 && NT == 4) {
-        if (p.gn_ab) { kern = conv_patch_kernel<TT, NT, KH, KW, false, true>; which = 4; }       // fused GroupNorm-apply + SiLU
-    } else if (p.gn_ab) return VF_ERR_SHAPE;
+        if (pl.form == 4) { kern = conv_patch_kernel<TT, NT, KH, KW, false, true>; built = true; }       // fused GroupNorm-apply + SiLU
+    }
+    if (!built) return VF_ERR_SHAPE;      // (a guard, not a rule: unreachable under dispatch.cpp's conv_patch_tile, which plans built forms only)
     static VfOncePerDevice attr_set[5];
-    if (!attr_set[which].set_lds(reinterpret_cast<const void*>(kern), (int)lds)) return VF_ERR_LAUNCH;
-    const int ntm = (p.M / (p.OH * p.OW)) * (p.H / TP) * (p.W / TP), ntn = p.N / BN;
-    // Column-group width of the tile order.  An XCD (own L2) works through tiles_xcd = ntm * ntn / 8 consecutive tiles = a block
-    // of (tiles_xcd / GN) m-tiles x GN n-tiles, and fetches that block's patches and weight panels once: bytes per XCD =
-    // tiles_xcd / GN * A_mt + GN * W_nt, least at GN = sqrt(tiles_xcd * A_mt / W_nt).  On the 16x16 level (weight panels of 3 MB
-    // against 0.65 MB patches) the old fixed GN = 8 made every XCD fetch 80 % of the weights: 256 MB per launch measured.
-    GemmParams q = p;
-    {
-        const double a_mt = (double)(TP + KW - 1) * (TP + KH - 1) * (p.Cin + (p.A2 ? (p.K - p.K1) : 0)) * 2.0;
-        const double w_nt = (double)BN * p.K * 2.0;
-        const double tiles_xcd = (double)ntm * ntn / 8.0;
-        int gn = (int)(__builtin_sqrt(tiles_xcd * a_mt / w_nt) + 0.5);
-        q.tile_group = gn < 1 ? 1 : (gn > ntn ? ntn : gn);
-    }
-    hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(512), lds, stream, q);
+    if (!attr_set[pl.form].set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(512), pl.lds_bytes, stream, pl.p);
     return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
 }
 
 template <class TT>
-int launch_patch_dtype(const GemmParams& p, int bn, hipStream_t stream) {
-    if (p.KH == 3 && p.KW == 3) return bn == 160 ? launch_patch<TT, 5, 3, 3>(p, stream) : launch_patch<TT, 4, 3, 3>(p, stream);
-    if (p.KH == 2 && p.KW == 2) return bn == 160 ? launch_patch<TT, 5, 2, 2>(p, stream) : launch_patch<TT, 4, 2, 2>(p, stream);
-    return VF_ERR_SHAPE;
-}
-
-template <class TT>
-int launch_q8(const GemmParams& p, hipStream_t stream) {
-    constexpr int NT = 4, BN = 128, NPIECES = 50;
-    const size_t lds = 2 * (size_t)NPIECES * 1024 + 3 * (size_t)BN * 128 + 2048;
-    auto kern = conv_patch_kernel<TT, NT, 3, 3, false, false, 0, true>;
-    static VfOncePerDevice attr_set;
-    if (!attr_set.set_lds(reinterpret_cast<const void*>(kern), (int)lds)) return VF_ERR_LAUNCH;
-    const int nimg = p.M / 64, ntm = (nimg + 3) / 4, ntn = p.N / BN;
-    hipLaunchKernelGGL(kern, dim3(ntm * ntn * p.split_k), dim3(512), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+int launch_conv(const VfGemmPlan& pl, hipStream_t stream) {
+    if (pl.kernel == VF_KERNEL_CONV_Q8) {      // the 8x8 form: main pass only, vf_launch_gemm runs the split-K reduce
+        auto kern = conv_patch_kernel<TT, 4, 3, 3, false, false, 0, true>;
+        static VfOncePerDevice attr_set;
+        if (!attr_set.set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
+        hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(512), pl.lds_bytes, stream, pl.p);
+        return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    }
+    if (pl.mode == 3) return pl.bn == 160 ? launch_patch<TT, 5, 3, 3>(pl, stream) : launch_patch<TT, 4, 3, 3>(pl, stream);
+    // (the 2 x 2 window: convolutions only -- the plain-GEMM form runs the 3 x 3 instantiation without window tiles)
+    return pl.bn == 160 ? launch_patch<TT, 5, 2, 2>(pl, stream) : launch_patch<TT, 4, 2, 2>(pl, stream);
 }
 
 }  // namespace
 
-// The 8 x 8 level through the patch-staged kernel (Q8 form): 0 = not such a launch, else the K split (number of fp32 partial
-// tiles per output tile).  Four images per workgroup and N / 128 channel tiles give (nimg / 4) * (N / 128) workgroups -- 120 at
-// the nominal 48-sample batch of the UNet's 1280-channel level -- so K is split over channel chunks until the one-per-CU grid
-// is about one round; the split follows the NOMINAL batch (the fp32 summation order must not depend on the launch's batch).
-// Nominal = 48 samples since round 6, like the tile-width rule below (one launch stream's half of the 32-frame headline, a rank's
-// 16-frame share at N > 1): K in two shares instead of four -- half the prologues, epilogues and fp32 partials.  Same-box A/B
-// (profiles/r06_i): 32 frames 76.22 -> 75.83 ms/step (conv family 31.65 -> 30.96); the 8-frame clip pays for it, 20.0 -> 20.6.
-int vf_conv_q8_split(const GemmParams& p) {
-    if (p.mode != 1 || p.stride != 1 || p.upsample || p.out_phase || (p.Cin & 63) || p.gn_ab) return 0;
-    if (p.H != 8 || p.W != 8 || p.OH != 8 || p.OW != 8 || p.KH != 3 || p.KW != 3 || p.ntaps != 9 || p.pad != 1 || p.pad_x != 1) return 0;
-    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_NO_PATCH | 0x4000 | (0xF << 8))) || (p.N % 128)) return 0;
-    if (p.A2 && ((p.K - p.K1) & 63)) return 0;
-    if (p.rows_per_sample != 64 && p.rowbias) return 0;
-    const int nchunks = p.Cin >> 6;
-    const long tiles24 = 12L * (p.N / 128);      // (the name is history: the nominal batch is 48 samples = 12 image quads)
-    int s = (int)(256 / tiles24);
-    if (s > 8) s = 8;
-    if (s > nchunks / 2) s = nchunks / 2;       // at least two chunks (18 K tiles) per share
-    return s < 1 ? 0 : s;
-}
-
-int vf_launch_conv_q8(const GemmParams& p, int dtype, hipStream_t stream) {
-    if (dtype == VF_DTYPE_F16) return launch_q8<F16>(p, stream);
-    if (dtype == VF_DTYPE_BF16) return launch_q8<BF16>(p, stream);
-    return VF_ERR_DTYPE;
-}
-
-namespace {
-}  // namespace
-
-// THE rule for which kernel a convolution launch runs -- 0: gemm.hip's implicit GEMM, 1: the patch-staged kernel (*arg = channel-tile
-// width), 2: its 8x8 form (*arg = K split; the launcher additionally needs the caller's split-K workspace, which every wrapper
-// passes).  vf_launch_gemm dispatches on it and vface_conv_uses_patch_kernel (what bench.py prices launches by and the engine
-// decides GroupNorm fusion by) reports it: one copy, so the two cannot drift apart.  Geometry and flags only, grid depth at the
-// nominal 24-sample batch: a sample's bits never depend on which other samples share its launch.
-int vf_conv_kernel_choice(const GemmParams& p, int* arg) {
-    if (arg) *arg = 0;
-    if (p.mode != 1 || ((p.flags >> 8) & 0xF) || (p.flags & GEMM_NO_PATCH)) return 0;
-    const int bn = vf_conv_patch_tile(p);
-    if (bn) {
-        const long tiles24 = 24L * (p.H / TP) * (p.W / TP) * (p.N / bn);
-        if (tiles24 >= 160 || (p.flags & GEMM_PATCH)) { if (arg) *arg = bn; return 1; }
-    }
-    if (!(p.flags & GEMM_NO_Q8)) {
-        const int s = vf_conv_q8_split(p);
-        if (s) { if (arg) *arg = s; return 2; }
-    }
-    return 0;
-}
-
-// 0 = this launch is not a patch-kernel shape; else the channel-tile width (160 | 128) the launch would use
-int vf_conv_patch_tile(const GemmParams& p) {
-    if (p.mode != 1 || p.stride != 1 || p.upsample || (p.Cin & 63)) return 0;
-    if (p.OH != p.H || p.OW != p.W || (p.H % TP) || (p.W % TP)) return 0;
-    if (!((p.KH == 3 && p.KW == 3) || (p.KH == 2 && p.KW == 2)) || p.ntaps != p.KH * p.KW) return 0;
-    if (p.pad < 0 || p.pad_x < 0 || p.pad > 1 || p.pad_x > 1) return 0;
-    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE)) || (p.N & 7)) return 0;
-    if ((p.flags & 0x4000) && !(p.KH == 3 && p.N % 160 == 0 && p.colstats)) return 0;   // diagnostic build: one instantiation
-    if (p.A2 && (((p.K - p.K1) & 63) || p.KH != 3)) return 0;
-    if (p.gn_ab && (p.KH != 3 || (p.ld_gn_ab < p.Cin) || ((uintptr_t)p.gn_ab & 15) || (p.flags & 0x4000))) return 0;
-    if (p.colstats && ((p.H * p.W) & 63)) return 0;
-    if (p.residual && !p.res_f32 && (((uintptr_t)p.residual & 15) || (p.ldr & 7))) return 0;
-    if (((uintptr_t)p.C & 15) || (p.C && (p.ldc & 7))) return 0;
-    const bool ok160 = p.N % 160 == 0, ok128 = p.N % 128 == 0;
-    if (p.gn_ab) return ok128 ? 128 : 0;   // the fused-normalisation build exists 128 wide only (the 160-wide one spilled 36 B)
-    if (p.KH == 2 && (p.residual || p.res_f32)) return ok128 ? 128 : 0;      // ... and so does the 2 x 2 window with a residual operand
-    if (ok160 && ok128 && !(p.flags & (GEMM_PATCH_BN160 | 0x4000))) {
-        // Both widths tile N (640, 1280, 1920 channels): one workgroup per CU, so a launch takes ceil(workgroups / CUs) rounds, and
-        // a 128-wide workgroup takes ~0.8 of a 160-wide one (32 instead of 40 MFMAs per wave and K tile, same fixed costs).
-        // Measured (tools/quantisation_probe.py, 24 samples): 32x32 640->640: 160-wide 384 workgroups = 1.5 rounds 181.6 us,
-        // 128-wide 480 = 1.9 rounds 153.6 us; 16x16 1280->1280: 192 = 0.75 rounds 175.3 us vs 240 = 0.94 rounds 151.8 us.
-        // The grid is taken at a NOMINAL batch on 256 CUs -- the width changes the summation order of the column statistics, so it
-        // must not depend on how many samples share the launch (batch invariance).  Nominal = 48 samples since round 5:
-        // one launch stream's half of the 32-frame headline and a rank's 16-frame share at N > 1 (at 24 -- the 8-frame clip --
-        // the 32 x 32 640-channel launches would take the 128-wide tile: 15 % faster THERE, 6 % slower at 48 and 96 samples;
-        // measured on the headline: 79.34 -> 79.10 ms/step, conv family 33.4 -> 32.8, profiles/r05_o).
-        const long t24 = 48L * (p.H / TP) * (p.W / TP);
-        const long r160 = (t24 * (p.N / 160) + 255) / 256, r128 = (t24 * (p.N / 128) + 255) / 256;
-        return (r128 * 4 < r160 * 5) ? 128 : 160;      // r128 * 0.8 < r160
-    }
-    if (ok160) return 160;
-    if (ok128) return 128;
-    return 0;
-}
-
-// Plain GEMM C[M, N] = A[M, K] Wt[N, K]^T through the patch-staged kernel's 256 x BN tile (8 waves, one workgroup per CU): the
-// kernel's "fused 1x1 source" K loop IS a GEMM K loop -- 256 consecutive rows of A per workgroup as a halo-free 16 x 16 "image",
-// no window tiles at all.  Versus gemm.hip's 128-row tile: 28 % fewer L2->LDS bytes per FLOP (measured where it pays: DESIGN 4).
-// 0 = not a shape this form takes; else the channel-tile width.
-int vf_gemm_patch_tile(const GemmParams& p) {
-    if (p.mode != 0 || p.A2 || p.out_phase || p.gn_ab || p.split_k > 1) return 0;
-    if ((p.M % (TP * TP)) || (p.K & 63) || p.K < 128) return 0;
-    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | 0x4000)) || (p.N & 7)) return 0;
-    if (p.rowbias && (p.rows_per_sample <= 0 || (p.rows_per_sample % (TP * TP)))) return 0;
-    if (p.residual && !p.res_f32 && (((uintptr_t)p.residual & 15) || (p.ldr & 7))) return 0;
-    if (((uintptr_t)p.C & 15) || (p.C && (p.ldc & 7))) return 0;
-    if (p.N % 160 == 0) return 160;
-    if (p.N % 128 == 0) return 128;
-    return 0;
-}
-
-int vf_launch_gemm_patch(const GemmParams& p_in, int dtype, hipStream_t stream) {
-    const int bn = vf_gemm_patch_tile(p_in);
-    if (!bn) return VF_ERR_SHAPE;
-    GemmParams p = p_in;
-    // the geometry the kernel derives its tile origin and output rows from: M / 256 images of 16 x 16 pixels, no window
-    p.H = p.W = p.OH = p.OW = TP; p.Cin = 0; p.K1 = 0; p.KH = p.KW = 3; p.ntaps = 9; p.pad = p.pad_x = 0; p.stride = 1; p.upsample = 0;
-    p.A2 = p.A; p.lda2 = p.lda; p.a2_bytes = p.a_bytes; p.a2_row_mod = 0;
-    if (dtype == VF_DTYPE_F16) return bn == 160 ? launch_patch<F16, 5, 3, 3>(p, stream) : launch_patch<F16, 4, 3, 3>(p, stream);
-    if (dtype == VF_DTYPE_BF16) return bn == 160 ? launch_patch<BF16, 5, 3, 3>(p, stream) : launch_patch<BF16, 4, 3, 3>(p, stream);
-    return VF_ERR_DTYPE;
-}
-
-int vf_launch_conv_patch(const GemmParams& p, int dtype, hipStream_t stream) {
-    const int bn = vf_conv_patch_tile(p);
-    if (!bn) return VF_ERR_SHAPE;
-    if (dtype == VF_DTYPE_F16) return launch_patch_dtype<F16>(p, bn, stream);
-    if (dtype == VF_DTYPE_BF16) return launch_patch_dtype<BF16>(p, bn, stream);
-    return VF_ERR_DTYPE;
+int vf_launch_conv_patch(const VfGemmPlan& pl, int dtype, hipStream_t stream) {
+    return dtype == VF_DTYPE_F16 ? launch_conv<F16>(pl, stream) : launch_conv<BF16>(pl, stream);
 }

@@ -31,7 +31,7 @@
 
 namespace {
 
-constexpr int BM = 128, BK = 64;
+constexpr int BM = VF_GEMM_BM, BK = VF_GEMM_BK;      // 128, 64 (dispatch.hpp)
 enum { MODE_PLAIN = 0, MODE_CONV_FAST = 1, MODE_CONV_GENERIC = 2 };
 
 // RM: the residual form of the wide epilogue (0 none, 1 16-bit, 2 the fp32 stream) as an instantiation of its own; -1 = chosen
@@ -884,8 +884,49 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p) {
     }
 }
 
+template <class TT, int MODE, int NT, bool DB>
+int launch_one(const VfGemmPlan& pl, hipStream_t stream) {
+    // residual form of the wide epilogue as a kernel of its own (see gemm_kernel's RM); the persistent form exists without a residual only -- its run-time-residual
+    // instantiation spilled 22-41 registers, the generic window's 35 --, and the single-stage and generic-window schedules carry the residual at run time
+    void (*kern)(GemmParams) = nullptr;
+    int which = 0;
+    if constexpr (DB && MODE != MODE_CONV_GENERIC) {
+        if (pl.persistent) { which = 1; kern = gemm_kernel<TT, MODE, NT, DB, DB, 0>; }
+        else { which = 3 + pl.form; kern = pl.form == 2 ? gemm_kernel<TT, MODE, NT, DB, false, 2> : pl.form == 1 ? gemm_kernel<TT, MODE, NT, DB, false, 1> : gemm_kernel<TT, MODE, NT, DB, false, 0>; }
+    } else kern = gemm_kernel<TT, MODE, NT, DB, false>;
+    static VfOncePerDevice attr_set[6];
+    if (pl.lds_bytes > 64 * 1024 && !attr_set[which].set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(256), pl.lds_bytes, stream, pl.p);
+    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+}
+
+template <class TT, int MODE>
+int launch_mode(const VfGemmPlan& pl, hipStream_t stream) {
+    if (pl.stages == 2) return pl.bn == 128 ? launch_one<TT, MODE, 4, true>(pl, stream) : launch_one<TT, MODE, 5, true>(pl, stream);   // 128x128x64 | 128x160x64
+    return pl.bn == 128 ? launch_one<TT, MODE, 4, false>(pl, stream) : launch_one<TT, MODE, 5, false>(pl, stream);
+}
+
+template <class TT>
+int launch_gemm(const VfGemmPlan& pl, hipStream_t stream) {
+    if (pl.mode == MODE_PLAIN) return launch_mode<TT, MODE_PLAIN>(pl, stream);
+    if (pl.mode == MODE_CONV_FAST) return launch_mode<TT, MODE_CONV_FAST>(pl, stream);
+    return launch_mode<TT, MODE_CONV_GENERIC>(pl, stream);
+}
+
+}  // namespace
+
+// The file is compiled as two translation units so that the two element types build in parallel (half the wall time of
+// `make -j`): VF_GEMM_TU == 1 holds the bf16 instantiations behind vf_launch_gemm_bf16, the default unit everything else.
+int vf_launch_gemm_bf16(const VfGemmPlan& pl, hipStream_t stream);
+#if defined(VF_GEMM_TU) && VF_GEMM_TU == 1
+int vf_launch_gemm_bf16(const VfGemmPlan& pl, hipStream_t stream) { return launch_gemm<BF16>(pl, stream); }
+#else
+// (rounds 1-3 kept four experimental schedules -- 3-stage / single-stage / BK = 32 pipelines, a 256-row ping-pong kernel -- behind `make VARIANTS=1`; all
+// measured slower than this kernel on every shape of the UNet (HISTORY.md) and were removed in round 4.  The entry point stays in the ABI and answers 0.)
+bool vf_gemm_variants_built() { return false; }
+
 // workgroups a persistent launch keeps resident: 2 per CU (LDS 64-74 KB and <= 256 VGPRs each)
-int persistent_grid() {
+static int persistent_grid() {
     static std::atomic<int> g{0};
     int v = g.load(std::memory_order_relaxed);
     if (!v) {
@@ -899,229 +940,21 @@ int persistent_grid() {
     return v;
 }
 
-template <class TT, int MODE, int NT, bool DB>
-int launch_one(const GemmParams& p, hipStream_t stream) {
-    constexpr int BN = 32 * NT;
-    const int ntiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    const size_t lds = (size_t)(DB ? 2 : 1) * (BM + BN) * BK * sizeof(typename TT::elem);
-    // persistent form: only where a workgroup would get more than one tile and the wide epilogue applies
-    // (measured on the UNet's shapes: +1..3 % for the implicit convolutions, +-2 % noise for plain GEMMs, which keep the
-    // one-tile-per-workgroup launch unless GEMM_PERSIST asks otherwise)
-    // (never for the generic-window form -- Cin % 64 != 0: the UNet's 9 -> 320 input convolution --: its persistent instantiation
-    //  carries all three residual forms of the epilogue and spilled 35 registers; the one-tile-per-workgroup form does not)
-    const bool persist_shape = DB && MODE != MODE_CONV_GENERIC && p.split_k == 1 &&
-                         !(p.flags & (GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_NO_PERSIST | 0x4000)) &&
-                         !(p.N & 7) && ntiles > persistent_grid() && (MODE != MODE_PLAIN || (p.flags & GEMM_PERSIST));
-    // residual form of the wide epilogue as a kernel of its own for the forms the UNet launches (see gemm_kernel's RM)
-    const int rm = p.res_f32 ? 2 : (p.residual ? 1 : 0);
-    const bool persist = persist_shape && rm == 0;
-    void (*kern)(GemmParams) = nullptr;
-    int which = 0;
-    if constexpr (DB && MODE != MODE_CONV_GENERIC) {
-        // (the persistent form exists without a residual only -- what the UNet launches it with; its run-time-residual instantiation
-        //  spilled 22-41 registers and is gone: a persistent launch with a residual runs one tile per workgroup)
-        if (persist) { which = 1; kern = gemm_kernel<TT, MODE, NT, DB, DB, 0>; }
-        else { which = 3 + rm; kern = rm == 2 ? gemm_kernel<TT, MODE, NT, DB, false, 2> : rm == 1 ? gemm_kernel<TT, MODE, NT, DB, false, 1> : gemm_kernel<TT, MODE, NT, DB, false, 0>; }
-    } else {
-        which = 0;
-        kern = gemm_kernel<TT, MODE, NT, DB, false>;
+int vf_launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
+    VfGemmPlan pl;
+    int rc = vf_plan_gemm(p, persistent_grid(), &pl);      // (dispatch.cpp: validation, extents and every choice)
+    if (rc != VF_OK) return rc;
+    if (dtype != VF_DTYPE_F16 && dtype != VF_DTYPE_BF16) return VF_ERR_DTYPE;
+    switch (pl.kernel) {
+        case VF_KERNEL_CONV_IN16: rc = vf_launch_conv_in16(pl, dtype, stream); break;
+        case VF_KERNEL_GEMM_BIG: rc = vf_launch_gemm_big(pl, dtype, stream); break;
+        case VF_KERNEL_GEMM: rc = dtype == VF_DTYPE_F16 ? launch_gemm<F16>(pl, stream) : vf_launch_gemm_bf16(pl, stream); break;
+        default: rc = vf_launch_conv_patch(pl, dtype, stream); break;
     }
-    static VfOncePerDevice attr_set[6];
-    if (lds > 64 * 1024 && !attr_set[which].set_lds(reinterpret_cast<const void*>(kern), (int)lds)) return VF_ERR_LAUNCH;
-    dim3 grid(persist ? persistent_grid() : ntiles * p.split_k);
-    GemmParams q = p;
-    if (MODE == MODE_PLAIN && p.split_k == 1 && !p.tile_group) {
-        // column-group width of the XCD-aware tile order (see conv.hip launch_patch): an XCD's share of the grid is a block of
-        // (tiles_xcd / GN) m-tiles x GN n-tiles; bytes through its L2 are least at GN = sqrt(tiles_xcd * A_mt / W_nt), as long as
-        // the GN weight panels (re-used over many rounds here) stay resident: at most half of the 4 MiB L2
-        const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM;
-        const double a_mt = (double)BM * p.K * 2.0, w_nt = (double)BN * p.K * 2.0;
-        int gn = (int)(__builtin_sqrt((double)ntm * ntn / 8.0 * a_mt / w_nt) + 0.5);
-        const int cap = (int)(2097152.0 / w_nt);
-        if (gn > cap) gn = cap;
-        q.tile_group = gn < 1 ? 1 : (gn > ntn ? ntn : gn);
-        if (p.flags & GEMM_GN8) q.tile_group = 8;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, q);
-    if (p.split_k > 1)
-        hipLaunchKernelGGL(splitk_reduce_kernel<TT>, dim3((p.M + 63) / 64, (p.N + 255) / 256), dim3(256), 0, stream, p);
+    if (rc != VF_OK || !pl.reduce) return rc;      // (else: the second pass of every split launch, the 128-row kernel's and the 8x8 form's)
+    const dim3 grid((pl.p.M + 63) / 64, (pl.p.N + 255) / 256);
+    if (dtype == VF_DTYPE_F16) hipLaunchKernelGGL(splitk_reduce_kernel<F16>, grid, dim3(256), 0, stream, pl.p);
+    else hipLaunchKernelGGL(splitk_reduce_kernel<BF16>, grid, dim3(256), 0, stream, pl.p);
     return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
-}
-
-template <class TT, int MODE>
-int launch_mode(const GemmParams& p, int variant, hipStream_t stream) {
-    switch (variant) {
-        case 5: return launch_one<TT, MODE, 4, true>(p, stream);   // 128x128x64, two stages
-        case 6: return launch_one<TT, MODE, 5, true>(p, stream);   // 128x160x64, two stages
-        case 7: return launch_one<TT, MODE, 4, false>(p, stream);  // 128x128x64, one stage
-        default: return launch_one<TT, MODE, 5, false>(p, stream); // 128x160x64, one stage
-    }
-}
-
-template <class TT>
-int launch_gemm(const GemmParams& p, int variant, hipStream_t stream) {
-    if (p.mode == 0) return launch_mode<TT, MODE_PLAIN>(p, variant, stream);
-    if (p.Cin % 64 == 0) return launch_mode<TT, MODE_CONV_FAST>(p, variant, stream);
-    return launch_mode<TT, MODE_CONV_GENERIC>(p, variant, stream);
-}
-
-// Schedule choice.  `flags` bits 8..11 force a variant (A/B benchmarking); 0 = automatic.
-int pick_variant(const GemmParams& p) {
-    const int forced = (p.flags >> 8) & 0xF;
-    if (forced) return forced;
-    const bool geglu = p.flags & GEMM_GEGLU;
-    // BN = 160 moves 10 % fewer L2->LDS bytes per FLOP.  Where N is a multiple of 128 as well (640, 1280, 1920) it only
-    // pays once the grid is several rounds deep (measured: +5..10 % at >= 1536 tiles, -3..5 % below: 160-wide tiles
-    // quantise a 1-2 round grid worse)
-    // (grid depth taken at the nominal 24-sample batch when the per-sample geometry is known, like split_for: the column
-    // statistics are folded in a tile-shape-dependent order, so the choice must not depend on the batch)
-    const long mref = p.rows_per_sample > 1 ? 24L * p.rows_per_sample : p.M;
-    const long tiles160 = ((mref + BM - 1) / BM) * (p.N / 160);
-    const bool n160 = !geglu && (p.N % 160 == 0) && ((p.N % 128 != 0) || tiles160 >= 1536);
-    return n160 ? 6 : 5;
-}
-
-// Split-K factor for a launch whose tile grid would leave most of the 256 CUs (2 workgroups each) idle while every
-// workgroup walks a long K loop (the 8x8-level convolutions: 120 tiles x 180..360 K tiles).  Depends on the shape only.
-// The factor is a function of the PER-SAMPLE geometry when the caller states it (rows_per_sample = OH*OW of a conv, h*w
-// of a token matrix): the tile count is taken at a nominal batch of 24 samples, so a frame's bits do not depend on how
-// many other frames share its launch (the fp32 summation order changes with the split) -- what frame sharding relies on.
-int split_for(int M, int N, int K, int flags, int rows_per_sample) {
-    if (flags & (GEMM_GEGLU | GEMM_OUT_F32)) return 1;
-    if ((N & 7) || ((flags >> 8) & 0xF) == 0xF) return 1;
-    const bool n160 = (N % 160 == 0) && (N % 128 != 0);
-    const int bn = n160 ? 160 : 128;
-    const long mref = rows_per_sample > 1 ? 24L * rows_per_sample : M;
-    const int tiles = (int)((mref + BM - 1) / BM) * ((N + bn - 1) / bn);
-    const int nt = (K + BK - 1) / BK;
-    if (tiles > 192 || nt < 16) return 1;
-    int s = 512 / tiles;
-    if (s > 8) s = 8;
-    if (s > nt / 8) s = nt / 8;
-    return s < 2 ? 1 : s;
-}
-
-}  // namespace
-
-// The file is compiled as two translation units so that the two element types build in parallel (half the wall time of
-// `make -j`): VF_GEMM_TU == 1 holds the bf16 instantiations behind vf_launch_gemm_bf16, the default unit everything else.
-int vf_launch_gemm_bf16(const GemmParams& p, int variant, hipStream_t stream);
-#if defined(VF_GEMM_TU) && VF_GEMM_TU == 1
-int vf_launch_gemm_bf16(const GemmParams& p, int variant, hipStream_t stream) { return launch_gemm<BF16>(p, variant, stream); }
-#else
-// (rounds 1-3 kept four experimental schedules -- 3-stage / single-stage / BK = 32 pipelines, a 256-row ping-pong kernel -- behind
-// `make VARIANTS=1`; all measured slower than this kernel on every shape of the UNet (HISTORY.md) and were removed in round 4.
-// The entry point stays in the ABI and answers 0.)
-bool vf_gemm_variants_built() { return false; }
-
-long vf_splitk_workspace_bytes(int M, int N, int K, int flags, int rows_per_sample) {
-    int s = split_for(M, N, K, flags, rows_per_sample);
-    if (s < 2) s = 0;
-    if (rows_per_sample == 64 && (N % 128) == 0 && !(flags & (GEMM_GEGLU | GEMM_OUT_F32))) {
-        // a 3x3 convolution on 8x8 images may take the Q8 form (conv.hip: vf_conv_q8_split), which always ends in fp32 partials:
-        // room for the largest split that rule can choose for this N
-        int s8 = (int)(256 / (12L * (N / 128)));      // (vf_conv_q8_split's nominal 48-sample grid)
-        if (s8 > 8) s8 = 8;
-        if (s8 < 1) s8 = 1;
-        if (s8 > s) s = s8;
-    }
-    return (long)s * M * N * 4;
-}
-
-int vf_launch_gemm(const GemmParams& p_in, int dtype, hipStream_t stream) {
-    GemmParams p = p_in;
-    p.split_k = 1; p.kt_per_split = 0;
-    if (!p.A || !p.Wt || (!p.C && !p.C32) || !p.zeros) return VF_ERR_ARG;
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0) return VF_ERR_ARG;
-    if (p.res_f32 && !p.residual) p.res_f32 = 0;
-    if (p.res_f32 || p.C32) {
-        // the fp32 residual stream lives in the wide epilogue (and the split-K reduce) only
-        if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | 0x4000)) || (p.N & 7)) return VF_ERR_SHAPE;
-        if (p.C32 && (((uintptr_t)p.C32 & 15) || (p.ldc32 & 3))) return VF_ERR_ALIGN;
-        if (p.res_f32 && (((uintptr_t)p.residual & 15) || (p.ldr & 3))) return VF_ERR_ALIGN;
-        if (p.out_phase && p.res_f32) return VF_ERR_SHAPE;
-    }
-    if ((p.K & 7) || (p.Kw & 7) || (p.lda & 7) || (p.ldw & 7) || (p.N & 3) || (p.ldc & 3)) return VF_ERR_ALIGN;
-    if (((uintptr_t)p.A | (uintptr_t)p.Wt | (uintptr_t)p.zeros) & 15) return VF_ERR_ALIGN;
-    if ((uintptr_t)p.C & 7) return VF_ERR_ALIGN;
-    if (p.C32 && (((uintptr_t)p.C & 15) || (p.ldc & 7))) return VF_ERR_ALIGN;
-    if (p.residual && (((uintptr_t)p.residual & 7) || (p.ldr & 3))) return VF_ERR_ALIGN;
-    if (p.rowbias && (p.rows_per_sample <= 0 || (p.ld_rowbias & 3))) return VF_ERR_ARG;
-    if ((p.flags & GEMM_GEGLU) && ((p.N & 31) || (p.flags & GEMM_OUT_F32) || p.residual || p.rowbias)) return VF_ERR_SHAPE;
-    if (p.colstats && ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32)) || (p.ld_colstats & 1) || ((uintptr_t)p.colstats & 15))) return VF_ERR_ARG;
-    if (p.A2 && (p.K1 <= 0 || (p.K1 % BK) || (p.lda2 & 7) || ((uintptr_t)p.A2 & 15))) return VF_ERR_ALIGN;
-    if (p.A2 && p.mode == 1 && ((p.Cin % 64) || ((p.K - p.K1) % BK) || p.upsample || p.a2_row_mod)) return VF_ERR_SHAPE;
-    if (p.mode == 1) {
-        if (p.ntaps == 0) { p.KH = p.KW = 3; p.ntaps = 9; p.pad_x = p.pad; }   // the plain 3x3 window
-        if (p.Cin <= 0 || (p.Cin & 7) || p.ntaps != p.KH * p.KW || p.ntaps > 9) return VF_ERR_SHAPE;
-        if (p.A2 ? (p.K1 != p.ntaps * p.Cin || p.K <= p.K1) : (p.K != p.ntaps * p.Cin)) return VF_ERR_SHAPE;
-        if (p.out_phase && (p.residual || (p.flags & GEMM_OUT_F32) || (p.N & 7))) return VF_ERR_SHAPE;
-        if (p.out_phase && p.colstats && ((p.OH * p.OW) & 63)) return VF_ERR_SHAPE;
-        if (p.stride != 1 && p.stride != 2) return VF_ERR_SHAPE;
-    }
-    // extents of the operand views for the buffer descriptors (bytes; must stay below 4 GiB - 16)
-    {
-        const unsigned long es = 2, lim = 0xFFFFFFF0ul;
-        const unsigned long rows = p.mode == 1 ? (unsigned long)(p.M / (p.OH * p.OW)) * p.H * p.W : (unsigned long)p.M;
-        const unsigned long ab = ((rows - 1) * (unsigned long)p.lda + (p.mode == 1 ? p.Cin : (p.A2 ? p.K1 : p.K))) * es;
-        const unsigned long wb = ((unsigned long)(p.N - 1) * p.ldw + p.Kw) * es;
-        unsigned long a2b = 0;
-        if (p.A2) a2b = ((unsigned long)((p.a2_row_mod > 0 ? p.a2_row_mod : p.M) - 1) * p.lda2 + (p.K - p.K1)) * es;
-        if (ab >= lim || wb >= lim || a2b >= lim) return VF_ERR_SHAPE;
-        p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb; p.a2_bytes = (unsigned)a2b;
-    }
-    // stride-1 convolutions over images that tile into 16 x 16 pixel patches run the patch-staged kernel (conv.hip): every
-    // input pixel goes through LDS once per channel chunk instead of once per tap.  The choice looks at the PER-SAMPLE
-    // geometry only (grid depth taken at the nominal 24-sample batch): the two kernels produce the same output bits but
-    // slice the column statistics differently, so a sample's bits must not depend on which other samples share its launch.
-    if (p.gn_ab) {
-        if (p.mode != 1 || p.M <= 0) return VF_ERR_SHAPE;
-        const unsigned long nimg = (unsigned long)(p.M / (p.OH * p.OW));
-        const unsigned long gb = ((nimg - 1) * (unsigned long)p.ld_gn_ab + p.Cin) * 8ul;
-        if (gb >= 0xFFFFFFF0ul) return VF_ERR_SHAPE;
-        p.gn_ab_bytes = (unsigned)gb;
-    }
-    // the UNet's 9 (16 stored) -> 320 input convolution: K = 144 in one MFMA pass, bound by its stores (inconv.hip)
-    if (vf_conv_in16_ok(p)) return vf_launch_conv_in16(p, dtype, stream);
-    int karg = 0;
-    const int kchoice = vf_conv_kernel_choice(p, &karg);      // (conv.hip: the one statement of the rule)
-    if (kchoice == 1) return vf_launch_conv_patch(p, dtype, stream);
-    if (kchoice == 2 && p.workspace) {
-        // the 8x8 level: four images per workgroup through the patch-staged kernel, K split over channel chunks, then the
-        // ordinary split-K reduce (which runs the whole epilogue)
-        const int s = karg;
-        if (s && p.workspace_bytes >= (long)s * p.M * p.N * 4 && !((uintptr_t)p.workspace & 15) && (p.M % 64) == 0 &&
-            !(p.residual && (((uintptr_t)p.residual & 15) || (p.ldr & 7))) && !(p.ldc & 7) && !((uintptr_t)p.C & 15)) {
-            p.split_k = s;
-            const int rc = vf_launch_conv_q8(p, dtype, stream);
-            if (rc != VF_OK) return rc;
-            if (dtype == VF_DTYPE_F16) hipLaunchKernelGGL(splitk_reduce_kernel<F16>, dim3((p.M + 63) / 64, (p.N + 255) / 256), dim3(256), 0, stream, p);
-            else hipLaunchKernelGGL(splitk_reduce_kernel<BF16>, dim3((p.M + 63) / 64, (p.N + 255) / 256), dim3(256), 0, stream, p);
-            return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
-        }
-    }
-    if (p.mode == 0 && (p.flags & GEMM_PATCH) && !((p.flags >> 8) & 0xF) && vf_gemm_patch_tile(p)) return vf_launch_gemm_patch(p, dtype, stream);
-    // long token matrices: gemm_big.hip's 256 x 320 tile (the one statement of the rule: vf_gemm_big_choice)
-    if (p.mode == 0 && vf_gemm_big_choice(p)) return vf_launch_gemm_big(p, dtype, stream);
-    if (p.gn_ab) return VF_ERR_SHAPE;   // the fused input normalisation exists in the patch-staged kernel only
-    const int variant = pick_variant(p);
-    if ((p.res_f32 || p.C32) && variant != 5 && variant != 6) return VF_ERR_SHAPE;
-    if (p.mode == 1 && (p.ntaps != 9 || p.out_phase || p.A2) && variant != 5 && variant != 6) return VF_ERR_SHAPE;
-    if (p.workspace && !p.out_phase && (variant == 5 || variant == 6) && !((p.flags >> 8) & 0xF) && !(p.flags & 0x4000)) {
-        const int s = split_for(p.M, p.N, p.K, p.flags, p.rows_per_sample);
-        if (s > 1 && p.workspace_bytes >= (long)s * p.M * p.N * 4 && !((uintptr_t)p.workspace & 15) &&
-            !(p.residual && (((uintptr_t)p.residual & 15) || (p.ldr & 7))) && !(p.ldc & 7) && !((uintptr_t)p.C & 15)) {
-            const int nt = (p.K + BK - 1) / BK;
-            p.split_k = s;
-            p.kt_per_split = (nt + s - 1) / s;
-            if ((long)(s - 1) * p.kt_per_split >= nt) p.split_k = (nt + p.kt_per_split - 1) / p.kt_per_split;  // no empty split
-        }
-    }
-    if ((p.flags & GEMM_GEGLU) && (variant == 2 || variant == 4 || variant == 6 || variant == 8 || variant == 10)) return VF_ERR_SHAPE;
-    if (p.colstats && (variant < 5 || variant > 8)) return VF_ERR_SHAPE;
-    if ((variant >= 1 && variant <= 4) || variant == 9 || variant == 10) return VF_ERR_SHAPE;      // (removed experimental schedules)
-    if (dtype == VF_DTYPE_F16) return launch_gemm<F16>(p, variant, stream);
-    if (dtype == VF_DTYPE_BF16) return vf_launch_gemm_bf16(p, variant, stream);
-    return VF_ERR_DTYPE;
 }
 #endif  // VF_GEMM_TU

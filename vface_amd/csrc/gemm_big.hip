@@ -17,8 +17,8 @@
 //   k-chunk c of row r at c ^ ((r >> 1) & 7)); everything arrives by `buffer_load_dwordx4 ... lds` (rows past M are
 //   out-of-range offsets: the hardware writes zeros).  One barrier per K tile; the nine pieces of tile t+1 go out one per
 //   MFMA group at the head of tile t's compute phase.
-// * K-tile compute as 20 steps (2 k32 halves x 10 channel tiles): per step one weight fragment is read two steps ahead and four
-//   MFMAs (the wave's four row tiles) issue; the activation fragments of a half stay in registers for its ten steps.
+// * K-tile compute as NS = 2 NJ steps (2 k32 halves x NJ channel tiles: 20 at the 320-wide tile, 16 at the 256-wide one): per step one weight fragment
+//   is read two steps ahead and four MFMAs (the wave's four row tiles) issue; the activation fragments of a half stay in registers for its NJ steps.
 // * Operand roles, fragment layout and the per-accumulator MFMA order (K tile by K tile, half 0 then half 1) are gemm.hip's:
 //   the results are BIT-IDENTICAL to that kernel's, so which of the two a launch takes may depend on the batch (tests).
 // * Epilogues (template EPI): 0: + bias, round, transposed through LDS as 16-bit rows, 16-byte stores; 1: GEGLU (weight rows
@@ -33,7 +33,7 @@
 
 namespace {
 
-constexpr int BM2 = 256, BN2 = 320;
+constexpr int BM2 = VF_BIG_BM, BN2 = VF_BIG_BN;      // 256, 320 (dispatch.hpp)
 constexpr int A_BYTES = BM2 * 128, B_BYTES = BN2 * 128, STAGE_BYTES = A_BYTES + B_BYTES;   // 32 KB + 40 KB
 
 // NJ: 16-channel tiles per wave -- 10 = the 256 x 320 tile; 8 = a 256 x 256 tile (round 6): the same kernel with eight weight pieces and
@@ -131,17 +131,16 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
     const unsigned aadr = (unsigned)(arow * 128 + ((fq ^ ((arow >> 1) & 7)) << 4));
     const unsigned wadr = (unsigned)(A_BYTES + wrow * 128 + ((fq ^ ((wrow >> 1) & 7)) << 4));
 
-    // ---- the K loop.  A K tile is 20 steps (k32 half kk = s / 10, channel tile j = s % 10); step s issues the four MFMAs of
-    // (kk, j) on the wave's four row tiles.  Weight fragments are read TWO steps ahead into a ring of four; the activation
-    // fragments of half 1 are read at step 4, those of the NEXT tile's half 0 at step 18.  The one barrier per tile sits at step 18:
-    // by then every LDS read of tile kt has been issued (the read for step 19 went out at step 17), so behind the wave's own
-    // `lgkmcnt(0)` + `vmcnt(0)` and the barrier (i) tile kt+1 is complete in the other stage and its first fragments are requested
-    // while the MFMAs of steps 18 and 19 -- operands already in registers -- run, and (ii) tile kt's stage is free: the nine pieces
-    // of tile kt+2 go out at steps 18, 19 of tile kt and 0..6 of tile kt+1, a full tile ahead of their use.
+    // ---- the K loop.  A K tile is NS = 2 NJ steps (k32 half kk = s / NJ, channel tile j = s % NJ: 20 steps at the 320-wide tile, 16 at the 256-wide
+    // one); step s issues the four MFMAs of (kk, j) on the wave's four row tiles.  Weight fragments are read TWO steps ahead into a ring of four; the
+    // activation fragments of half 1 are read at step 4, those of the NEXT tile's half 0 at step NS-2.  The one barrier per tile sits at step NS-2: by
+    // then every LDS read of tile kt has been issued (the read for step NS-1 went out at step NS-3), so behind the wave's own `lgkmcnt(0)` + `vmcnt(0)`
+    // and the barrier (i) tile kt+1 is complete in the other stage and its first fragments are requested while the MFMAs of steps NS-2 and NS-1 run,
+    // and (ii) tile kt's stage is free: the NPC pieces of tile kt+2 go out at steps NS-2, NS-1 of tile kt and 0..NPC-3 of tile kt+1, a tile ahead.
     const int nt = p.K >> 6;
 #pragma unroll
     for (int s = 0; s < NPC; ++s) issue_piece(s, 0, 0);
-    if (nt > 1) { issue_piece(0, 1, 1); issue_piece(1, 1, 1); }      // (what steps 18, 19 of a tile "-1" would have issued)
+    if (nt > 1) { issue_piece(0, 1, 1); issue_piece(1, 1, 1); }      // (what steps NS-2, NS-1 of a tile "-1" would have issued)
     V8 af[2][4], wf[4];
     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");          // tile 0 has landed (the two pieces of tile 1 may still fly)
     __builtin_amdgcn_s_barrier();
@@ -181,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) af[0][i] = *reinterpret_cast<const V8*>(sn + aadr + i * 2048);
             }
-            // pieces of the tile after next: 0, 1 at steps 18, 19 (into the stage this tile just left), 2..8 at steps 0..6 of the next
+            // pieces of the tile after next: 0, 1 at steps NS-2, NS-1 (into the stage this tile just left), 2..NPC-1 at steps 0..NPC-3 of the next
             if (s >= NS - 2) { if (more2) issue_piece(s - (NS - 2), kt + 2, cur); }
             else if (s < NPC - 2) { if (more) issue_piece(s + 2, kt + 1, cur ^ 1); }
             __builtin_amdgcn_sched_barrier(0);
@@ -437,112 +436,31 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmParams p) {
 }
 
 template <class TT, int EPI, int NJ>
-int launch_big(const GemmParams& p, hipStream_t stream) {
+int launch_big(const VfGemmPlan& pl, hipStream_t stream) {
     auto kern = gemm256_kernel<TT, EPI, NJ>;
     static VfOncePerDevice attr_set;
-    constexpr int BN = 32 * NJ;
-    constexpr int lds = 2 * (A_BYTES + BN * 128);
-    if (!attr_set.set_lds(reinterpret_cast<const void*>(kern), lds)) return VF_ERR_LAUNCH;
-    const int ntn = p.N / BN, ntm = (p.M + BM2 - 1) / BM2;
-    GemmParams q = p;
-    {
-        // column-group width of the XCD-aware tile order: gemm.hip's rule (bytes through an XCD's L2 are least at
-        // GN = sqrt(tiles_xcd * A_mt / W_nt); the GN weight panels stay within half of the 4 MiB L2)
-        const double a_mt = (double)BM2 * p.K * 2.0, w_nt = (double)BN * p.K * 2.0;
-        int gn = (int)(__builtin_sqrt((double)ntm * ntn / 8.0 * a_mt / w_nt) + 0.5);
-        const int cap = (int)(2097152.0 / w_nt);
-        if (gn > cap) gn = cap;
-        q.tile_group = gn < 1 ? 1 : (gn > ntn ? ntn : gn);
-    }
-    hipLaunchKernelGGL(kern, dim3(ntn * ntm), dim3(512), lds, stream, q);
+    if (!attr_set.set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(512), pl.lds_bytes, stream, pl.p);
     return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
 }
 
-// Tile width of a launch: 320 channels, or 256 where N allows both, K is short and the one-workgroup-per-CU grid then takes fewer
-// tile-times (rounds of 256 workgroups).  MEASURED (tools/bench_gemm_widths.py, profiles/r06_h): a 256-wide tile is NOT 0.8 of a 320-wide
-// one when K is deep -- ff2 at K = 5120: 240 tiles in one round take as long as 192 (175 vs 180 us at 48 samples; 361 vs 349 at 96),
-// the K loop waits for its activation pieces, which five n-tiles per m-tile request instead of four -- it pays where the prologue and
-// epilogue weigh: the 1280 x 1280 projections (55 -> 45 us at 48 samples, 90 -> 80 at 96) and the dual-source projection under one
-// round (80 -> 70).  Hence: K <= 1280 only, and only where the rounds say so at 0.85 of a tile-time.  The two widths give the same bits,
-// so the choice may follow the batch.  GEMM_BIG_W256 / _W320 (tuning bits of vface_gemm: tests and A/B runs) force one.
 template <class TT, int EPI>
-int launch_big_width(const GemmParams& p, hipStream_t stream) {
-    if constexpr (EPI != 3) {
-        bool w256 = false;
-        if (p.N % 256 == 0 && !(p.flags & GEMM_BIG_W320)) {
-            const long ntm = (p.M + BM2 - 1) / BM2;
-            const long r320 = (ntm * (p.N / 320) + 255) / 256, r256 = (ntm * (p.N / 256) + 255) / 256;
-            w256 = (p.flags & GEMM_BIG_W256) || (p.K <= 1280 && (double)r256 * 0.85 < (double)r320);
-        }
-        if (w256) return launch_big<TT, EPI, 8>(p, stream);
+int launch_big_width(const VfGemmPlan& pl, hipStream_t stream) {
+    if constexpr (EPI != 3) {      // (the fp32 residual-stream form is built 320 wide only)
+        if (pl.bn == 256) return launch_big<TT, EPI, 8>(pl, stream);
     }
-    return launch_big<TT, EPI, 10>(p, stream);
+    return launch_big<TT, EPI, 10>(pl, stream);
 }
 
 template <class TT>
-int launch_big_dtype(const GemmParams& p, hipStream_t stream) {
-    if (p.C32) return launch_big_width<TT, 3>(p, stream);
-    if (p.flags & GEMM_GEGLU) return launch_big_width<TT, 1>(p, stream);
-    if (p.residual) return launch_big_width<TT, 2>(p, stream);
-    return launch_big_width<TT, 0>(p, stream);
+int launch_big_dtype(const VfGemmPlan& pl, hipStream_t stream) {
+    if (pl.form == 3) return launch_big_width<TT, 3>(pl, stream);
+    if (pl.form == 1) return launch_big_width<TT, 1>(pl, stream);
+    return pl.form == 2 ? launch_big_width<TT, 2>(pl, stream) : launch_big_width<TT, 0>(pl, stream);
 }
 
 }  // namespace
 
-// Is this plain-GEMM launch one the 256 x 320 tile takes?  Shape, operands and epilogue form only (vf_launch_gemm has already
-// validated alignments and filled the operand extents).  Since the two kernels' outputs are bit-identical, the caller is free to
-// look at the batch (tile count) when it chooses between them.
-bool vf_gemm_big_ok(const GemmParams& p) {
-    if (p.mode != 0 || p.out_phase || p.gn_ab || p.split_k > 1 || p.a2_row_mod) return false;
-    if ((p.N % BN2) || (p.K & 63) || p.K < 128 || (p.Kw < p.K)) return false;
-    if (p.A2 && ((p.K1 & 63) || p.K1 <= 0 || p.K1 >= p.K)) return false;
-    if (p.flags & (GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_F32_TRANSPOSE | 0x4000 | (0xF << 8))) return false;
-    if (p.C32) {
-        // the fp32 residual-stream form (EPI 3): carrier required; the per-sample row bias needs every 256-row tile inside one sample
-        if (p.flags & GEMM_GEGLU) return false;
-        if (((uintptr_t)p.C32 & 15) || (p.ldc32 & 3)) return false;
-        if (p.rowbias && (p.rows_per_sample <= 0 || (p.rows_per_sample % BM2) || (p.ld_rowbias & 3) || ((uintptr_t)p.rowbias & 15))) return false;
-        if (p.colstats && ((p.M & 63) || (p.ld_colstats & 1) || ((uintptr_t)p.colstats & 7))) return false;
-    } else if (p.colstats || p.rowbias || !p.C) {
-        return false;
-    }
-    if (p.C && (((uintptr_t)p.C & 15) || (p.ldc & 7))) return false;
-    if ((p.lda & 7) || (p.ldw & 7)) return false;
-    if (p.residual && ((p.flags & GEMM_GEGLU) || ((uintptr_t)p.residual & 15) || (p.ldr & (p.res_f32 ? 3 : 7)))) return false;
-    if (p.residual && !p.res_f32 && p.C32) return false;      // (16-bit residual rows: the 16-bit-output form only)
-    if (p.bias && ((uintptr_t)p.bias & 15)) return false;
-    return true;
-}
-
-// THE rule for which plain-GEMM kernel a launch runs (vf_launch_gemm dispatches on it).  Outputs and the fp32 carrier are
-// bit-identical between the two kernels (the per-64-row column statistics of the residual-stream form are not: another fold
-// order -- one more reason that form is never chosen automatically: a sample's bits must not depend on which other samples
-// share its launch, what frame sharding and the two launch streams rely on); 16-bit-output launches take the 256 x 320 tile
-// from 192 tiles on -- about a round of the one-workgroup-per-CU grid (measured: profiles/r05_c, r05_d).
-bool vf_gemm_big_choice(const GemmParams& p) {
-    if ((p.flags & GEMM_NO_BIG) || !vf_gemm_big_ok(p)) return false;
-    if (p.flags & GEMM_BIG) return true;
-    // the fp32 residual-stream form (EPI 3: proj_in / to_out / proj_out) is built, bit-identical and MEASURED SLOWER than the 128-row
-    // kernel on 14 of 18 of the UNet's launches (profiles/r05_e: 0.78-1.29x): these launches are bound by their epilogue's HBM
-    // traffic (4 + 4 B per output element around a K = 640 loop), which two 128-row workgroups per CU overlap with each other's
-    // K loops and one 256-row workgroup per CU cannot.  It stays selectable (VFACE_TUNE_BIG_TILE) and is never chosen here.
-    if (p.C32) return false;
-    return (long)((p.M + BM2 - 1) / BM2) * (p.N / BN2) >= 192;
-}
-
-int vf_launch_gemm_big(const GemmParams& p_in, int dtype, hipStream_t stream) {
-    if (!vf_gemm_big_ok(p_in)) return VF_ERR_SHAPE;
-    GemmParams p = p_in;
-    {
-        // extents of the residual and output views for the epilogue's buffer descriptors (bytes; below 4 GiB - 16)
-        const unsigned long nout = (p.flags & GEMM_GEGLU) ? (unsigned long)p.N / 2 : (unsigned long)p.N;
-        const unsigned long cb = p.C ? ((unsigned long)(p.M - 1) * p.ldc + nout) * 2ul : 0ul;
-        const unsigned long rb = p.residual ? ((unsigned long)(p.M - 1) * p.ldr + p.N) * (p.res_f32 ? 4ul : 2ul) : 0ul;
-        const unsigned long c32b = p.C32 ? ((unsigned long)(p.M - 1) * p.ldc32 + p.N) * 4ul : 0ul;
-        if (cb >= 0xFFFFFFF0ul || rb >= 0xFFFFFFF0ul || c32b >= 0xFFFFFFF0ul) return VF_ERR_SHAPE;
-        p.c_bytes = (unsigned)cb; p.res_bytes = (unsigned)rb; p.c32_bytes = (unsigned)c32b;
-    }
-    if (dtype == VF_DTYPE_F16) return launch_big_dtype<F16>(p, stream);
-    if (dtype == VF_DTYPE_BF16) return launch_big_dtype<BF16>(p, stream);
-    return VF_ERR_DTYPE;
+int vf_launch_gemm_big(const VfGemmPlan& pl, int dtype, hipStream_t stream) {
+    return dtype == VF_DTYPE_F16 ? launch_big_dtype<F16>(pl, stream) : launch_big_dtype<BF16>(pl, stream);
 }

@@ -24,8 +24,8 @@
 
 namespace {
 
-constexpr int IC_CH = 80;           // output channels per wave (five 16-channel tiles)
-constexpr int IC_K = 144;           // 9 taps x 16 stored channels
+constexpr int IC_CH = VF_IN16_CH;   // 80 output channels per wave (five 16-channel tiles)
+constexpr int IC_K = VF_IN16_K;     // 144 = 9 taps x 16 stored channels
 constexpr int IC_SP = 84;           // scratch row pitch (floats): 80 + 4, the accumulator tiles' float4 writes spread over the banks
 
 template <class TT>
@@ -155,36 +155,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(GemmParams p, int s
 
 }  // namespace
 
-// Is this convolution launch the 16-stored-channel input form this kernel takes?  (vf_launch_gemm has validated alignments and filled
-// the operand extents.)  Per-sample geometry and epilogue form only: a sample's bits do not depend on its batch.
-bool vf_conv_in16_ok(const GemmParams& p) {
-    if (p.mode != 1 || p.Cin != 16 || p.ntaps != 9 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.upsample || p.pad != 1 || p.pad_x != 1) return false;
-    if (p.A2 || p.residual || p.rowbias || p.gn_ab || p.out_phase || p.res_f32) return false;
-    if (p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NO_PATCH | 0x4000 | (0xF << 8))) return false;      // (GEMM_NO_PATCH: A/B, the generic kernel)
-    if ((p.N % IC_CH) || p.K != IC_K || p.Kw < IC_K || (p.ldw & 7)) return false;
-    if (p.OH != p.H || p.OW != p.W || ((p.H * p.W) & 63) || (p.W & 15) || p.M != (p.M / (p.H * p.W)) * p.H * p.W) return false;
-    if (!p.C && !p.C32) return false;
-    if (p.C && (((uintptr_t)p.C & 15) || (p.ldc & 7))) return false;
-    if (p.C32 && (((uintptr_t)p.C32 & 15) || (p.ldc32 & 3))) return false;
-    if (p.colstats && (((uintptr_t)p.colstats & 15) || (p.ld_colstats & 1))) return false;
-    if (p.bias && ((uintptr_t)p.bias & 15)) return false;
-    const unsigned long cb = p.C ? ((unsigned long)(p.M - 1) * p.ldc + p.N) * 2ul : 0ul, c32b = p.C32 ? ((unsigned long)(p.M - 1) * p.ldc32 + p.N) * 4ul : 0ul;
-    return cb < 0xFFFF0000ul && c32b < 0xFFFF0000ul && p.a_bytes < 0xFFFF0000u;
-}
-
-int vf_launch_conv_in16(const GemmParams& p_in, int dtype, hipStream_t stream) {
-    if (!vf_conv_in16_ok(p_in)) return VF_ERR_SHAPE;
-    GemmParams p = p_in;
-    p.c_bytes = p.C ? (unsigned)(((unsigned long)(p.M - 1) * p.ldc + p.N) * 2ul) : 0u;
-    p.c32_bytes = p.C32 ? (unsigned)(((unsigned long)(p.M - 1) * p.ldc32 + p.N) * 4ul) : 0u;
-    const int nslices = p.M / 64;
-    // a workgroup = the (up to) four 80-channel slices of a run of pixel slices; about two workgroups per CU in flight, each wave
-    // keeping its weight fragments over its whole run (at least 4 slices where the launch has them: the fragments are 26 KB)
-    int spw = (nslices + 511) / 512;
-    if (spw < 4) spw = nslices < 4 ? nslices : 4;
-    const dim3 grid((nslices + spw - 1) / spw, (p.N / IC_CH + 3) / 4);
-    if (dtype == VF_DTYPE_F16) hipLaunchKernelGGL(conv3x3_c16_kernel<F16>, grid, dim3(256), 0, stream, p, spw, nslices);
-    else if (dtype == VF_DTYPE_BF16) hipLaunchKernelGGL(conv3x3_c16_kernel<BF16>, grid, dim3(256), 0, stream, p, spw, nslices);
-    else return VF_ERR_DTYPE;
+int vf_launch_conv_in16(const VfGemmPlan& pl, int dtype, hipStream_t stream) {
+    const dim3 grid(pl.grid_x, pl.grid_y);
+    const int nslices = pl.p.M / 64;
+    if (dtype == VF_DTYPE_F16) hipLaunchKernelGGL(conv3x3_c16_kernel<F16>, grid, dim3(256), 0, stream, pl.p, pl.slices_per_wg, nslices);
+    else hipLaunchKernelGGL(conv3x3_c16_kernel<BF16>, grid, dim3(256), 0, stream, pl.p, pl.slices_per_wg, nslices);
     return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
 }

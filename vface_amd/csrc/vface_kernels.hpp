@@ -21,76 +21,12 @@ struct VfOncePerDevice {
     }
 };
 
-enum { GEMM_GEGLU = 1, GEMM_OUT_F32 = 2, GEMM_NO_XCD_REMAP = 0x1000, GEMM_NO_SETPRIO = 0x2000, GEMM_NARROW_EPILOGUE = 0x8000, GEMM_NO_PERSIST = 0x10000, GEMM_PERSIST = 0x20000,
-       GEMM_NO_PATCH = 0x80000, GEMM_PATCH = 0x100000, GEMM_GN8 = 0x8000000 /* A/B: fixed column groups of 8 n-tiles in the plain GEMM's tile order */, GEMM_NO_Q8 = 0x4000000 /* A/B: the 8x8 level stays on the im2col kernel */, GEMM_PATCH_BN160 = 0x2000000 /* A/B: the patch kernel's 160-wide tile wherever it divides N */, GEMM_F32_TRANSPOSE = 0x1000000 /* A/B: epilogue transposes in fp32 even where 16 bits would do */,
-       GEMM_BIG = 0x10000000 /* take gemm_big.hip's 256 x 320 tile whenever the launch qualifies */, GEMM_NO_BIG = 0x20000000 /* A/B: never */,
-       GEMM_BIG_W256 = 0x200000 /* gemm_big.hip: the 256-channel tile width wherever N allows it */, GEMM_BIG_W320 = 0x400000 /* ... never */ };  // (0x40000 = VFACE_CONV_PAD_TRAILING)  // bits 8..11 of flags: forced schedule variant (0 = automatic)
-
-struct GemmParams {
-    int mode;  // 0: plain A[M][K]; 1: implicit 3x3 conv over NHWC
-    const void* A;
-    long lda;  // plain: row stride; conv: pixel stride (>= Cin) in elements
-    const void* A2;  // optional second source for k >= K1 (plain mode), row = m % a2_row_mod
-    long lda2;
-    int K1, a2_row_mod;
-    const void* Wt;  // [N][ldw]
-    long ldw;
-    int Kw;  // valid k columns of Wt (multiple of 8)
-    int M, N, K;
-    // conv geometry (stored input H x W, output OH x OW)
-    int H, W, Cin, OH, OW, stride, upsample;
-    int pad;  // leading (top) zero padding: 1, or 0 for the VAE encoder's (0,1,0,1) stride-2 convolution
-    int pad_x;           // leading (left) zero padding; KH x KW window (ntaps = KH*KW <= 9; 0 = the launcher fills 3x3)
-    int KH, KW, ntaps;
-    int out_phase;       // 0, or 4 | (py << 1) | px: output rows are the (py, px) parity phase of a 2OH x 2OW image
-    const float* bias;     // [N] or null
-    const float* rowbias;  // [M / rows_per_sample][ld_rowbias] or null
-    int rows_per_sample;
-    int ld_rowbias;
-    const void* residual;  // [M][ldr] or null
-    long ldr;
-    void* C;  // [M][ldc] 16-bit (or fp32 with GEMM_OUT_F32); may be null when C32 is given
-    long ldc;
-    // fp32 residual stream: `residual` is fp32 [M][ldr] when res_f32; C32 (optional) receives the fp32 sum
-    // bias + rowbias + residual + acc BEFORE the rounding to 16 bits -- the carrier the next residual add / norm reads
-    int res_f32;
-    float* C32;
-    long ldc32;
-    // fused input normalisation (patch-staged convolution only): the operand the matrix cores see is
-    // act(x * a[img][ci] + b[img][ci]) with (a, b) fp32 pairs at gn_ab[(img * ld_gn_ab + ci) * 2]; act = SiLU if gn_silu
-    const float* gn_ab;
-    long ld_gn_ab;
-    int gn_silu;
-    unsigned gn_ab_bytes;   // filled by the launcher
-    const void* zeros;  // >= 16 zero bytes, 16-B aligned
-    int flags;
-    unsigned a_bytes, a2_bytes, w_bytes;  // filled by the launcher: extents of the operand views
-    float* colstats;     // optional [ceil(M/64)][ld_colstats][2] per-64-row-slice column (sum, sumsq) of the stored values
-    long ld_colstats;
-    // split-K (launcher-chosen when a workspace is supplied and the tile grid underfills the chip): fp32 partial tiles
-    // [split_k][M][N] in `workspace`, summed in split order by a second kernel that also runs the epilogue
-    float* workspace;
-    long workspace_bytes;
-    int split_k, kt_per_split;  // filled by the launcher
-    int tile_group;             // patch-staged kernel: n-tiles per column group of its XCD-aware tile order (launcher; 0 = 8)
-    unsigned res_bytes, c_bytes, c32_bytes;  // gemm_big.hip (filled by its launcher): extents of the fp32 residual view, of the 16-bit output view and of the fp32 carrier view
-};
-long vf_splitk_workspace_bytes(int M, int N, int K, int flags, int rows_per_sample);
+#include "dispatch.hpp"      // GemmParams, the GEMM_* flag bits and the launch plan
 bool vf_gemm_variants_built();
 int vf_launch_gemm(const GemmParams& p, int dtype, hipStream_t stream);
-// conv.hip: the patch-staged stride-1 convolution; vf_conv_patch_tile = 0 (not a patch shape) | 160 | 128
-int vf_conv_patch_tile(const GemmParams& p);
-int vf_conv_kernel_choice(const GemmParams& p, int* arg);                        // 0 im2col | 1 patch (*arg = tile width) | 2 8x8 form (*arg = K split)
-int vf_launch_conv_patch(const GemmParams& p, int dtype, hipStream_t stream);
-int vf_gemm_patch_tile(const GemmParams& p);                                   // plain GEMM through the patch kernel's 256-row tile: 0 | 160 | 128
-int vf_launch_gemm_patch(const GemmParams& p, int dtype, hipStream_t stream);
-bool vf_gemm_big_ok(const GemmParams& p);
-bool vf_gemm_big_choice(const GemmParams& p);                                  // ... and the rule says it should                                      // gemm_big.hip: the 256 x 320 tile takes this plain-GEMM launch
-int vf_launch_gemm_big(const GemmParams& p, int dtype, hipStream_t stream);
-bool vf_conv_in16_ok(const GemmParams& p);                                       // inconv.hip: the 16-stored-channel input convolution (K = 144 in one MFMA pass)
-int vf_launch_conv_in16(const GemmParams& p, int dtype, hipStream_t stream);
-int vf_conv_q8_split(const GemmParams& p);                                      // the 8x8 level through the patch kernel: 0 | K split
-int vf_launch_conv_q8(const GemmParams& p, int dtype, hipStream_t stream);     // (main pass only: the caller runs the split-K reduce)
+int vf_launch_conv_patch(const VfGemmPlan& plan, int dtype, hipStream_t stream);   // conv.hip: the patch-staged kernel, its 8x8 form (main pass) and its plain-GEMM form
+int vf_launch_gemm_big(const VfGemmPlan& plan, int dtype, hipStream_t stream);     // gemm_big.hip: the 256 x 320 | 256 tile
+int vf_launch_conv_in16(const VfGemmPlan& plan, int dtype, hipStream_t stream);    // inconv.hip: the 16-stored-channel input convolution (K = 144 in one MFMA pass)
 bool vf_attention_shared_scores_supported(int dh, int v_sets);
 
 // ffn.hip: fused LayerNorm -> ff.net[0] (GEGLU) -> ff.net[2] -> + x over token matrices with C in {64, 128, 320}, M % 128 == 0
