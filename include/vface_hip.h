@@ -410,6 +410,45 @@ int vface_act(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, in
 int vface_cond_mix(const float* a, int rows_a, float w_a, const float* b, int rows_b, float w_b, const float* c, int rows_c, float w_c,
                    float w_sum, float* out32, int64_t ldo32, void* out16, int64_t ldo16, int B, int N, int dtype, void* stream);
 
+/* ---- identity features (ArcFace IR-SE50) --------------------------------------------------------------------------------------------
+ * The reference computes `id_feat` with `IDLoss.extract_feats` (REFace/ldm/models/diffusion/ddpm.py:91-124, :1010): a pooling and
+ * crop chain in front of `Backbone(112, 50, 'ir_se')` (REFace/src/Face_models/encoders/{model_irse,helpers}.py), once for the source
+ * and once per target frame (scripts/VFace_inference_batch.py:437, :442, :500).  Its convolutions are vface_conv3x3 / vface_im2col +
+ * vface_gemm with the foldable BatchNorms folded on the host, its squeeze-excite pools vface_channel_stats + vface_pooled_linear, its
+ * output layer one vface_gemm (vface_amd/arcface.py); these entry points are the rest.  All: raw device pointers, no allocation,
+ * no synchronisation, capturable; a refusal launches nothing; no atomics (a sample's bits do not depend on the batch); fp32
+ * arithmetic and one rounding per stored value.
+ *
+ * vface_id_prep: `extract_feats` up to the network (ddpm.py:114-119) in one pass.  img fp32 planar [B][3][H][W] ->
+ *   out [B * 112 * 112][ldo >= 8] 16-bit, 8 channels written per pixel (3 values, 5 zeros).  clip_img != 0: `un_norm_clip`
+ *   (x * std + mean per channel) then (x - 0.5) / 0.5; 0: the input as it is.  Then AdaptiveAvgPool2d(256) unless H == 256 (the
+ *   reference's own condition; W >= 220 then), the crop [35:223, 32:220], AdaptiveAvgPool2d(112); bins floor(i In / Out) ..
+ *   ceil((i + 1) In / Out), the two means nested as the reference nests them.  prep == 1 (clip_img must be set): img is a [-1, 1]
+ *   frame at any size with an optional fp32 mask [B][H][W]; it is first brought to the CLIP-normalised 224 x 224 image by
+ *   vface_clip_patches' prep == 1 expressions, in its order. */
+int vface_id_prep(const float* img, int H, int W, const float* mask, int prep, int clip_img, void* out, int64_t ldo, int B, int dtype,
+                  void* stream);
+
+/* vface_prelu: y[m][c] = x > 0 ? x : slope[c] * x on 16-bit views x [M][ldx] -> y [M][ldy] (y may be x); slope fp32 [C].
+ *   z (optional, 16-bit [M][ldz], distinct from x and y): z[m][c] = za[c] * y32 + zb[c] from the unrounded y (the first unit's
+ *   leading BatchNorm2d, helpers.py:108).  C % 8 == 0. */
+int vface_prelu(const void* x, int64_t ldx, const float* slope, void* y, int64_t ldy, const float* za, const float* zb, void* z,
+                int64_t ldz, int64_t M, int C, int dtype, void* stream);
+
+/* vface_se_gate_add: the end of a `bottleneck_IR_SE` unit (helpers.py:65-72, 116-119):
+ *   y[m][c] = res[m][c] * g[m / (OH * OW)][c] + sc, g fp32 [nimg][ldg], one fp32 fma.  sc_stride == 0: sc is row m of a tensor of
+ *   the output's size, H x W that size (the 1 x 1 convolution shortcut).  sc_stride 1 | 2: sc is pixel (n, oy * s, ox * s) of the
+ *   unit's input [nimg * H * W][lds] -- MaxPool2d(1, s) -- and the output is OH x OW, OH = (H - 1) / s + 1, OW likewise.
+ *   z (optional): z[m][c] = za[c] * y32 + zb[c], the NEXT unit's leading BatchNorm2d: it precedes a zero-padded convolution, so the
+ *   padding must follow it and it cannot be folded.  y and z are each rounded once from the fp32 sum.  y may be res.  C % 8 == 0. */
+int vface_se_gate_add(const void* res, int64_t ldr, const float* g, int64_t ldg, const void* sc, int64_t lds, int sc_stride, int nimg,
+                      int H, int W, int C, void* y, int64_t ldy, const float* za, const float* zb, void* z, int64_t ldz, int dtype,
+                      void* stream);
+
+/* vface_l2norm_rows: `l2_norm` (helpers.py:15-18): out[b][:] = x[b][:] / ||x[b]||_2 on fp32 rows [B][ldx] -> [B][ldo]; the squares
+ *   are summed relative to the row's largest magnitude, in a fixed order that does not depend on B.  N % 4 == 0. */
+int vface_l2norm_rows(const float* x, int64_t ldx, float* out, int64_t ldo, int B, int N, void* stream);
+
 /* The FeedForward third of BasicTransformerBlock._forward in ONE launch (REFace/ldm/modules/attention.py:243 `x = ff(norm3(x)) + x`,
  * FeedForward / GEGLU :37-64, LayerNorm :233):  out = W2 (a * gelu(g)) + b2 + x,  [a ; g] = W1 LN(x) + b1.
  * x32: the block's running sum, fp32 [M][ldx] (LayerNorm input and residual).  W1: ff.net[0].proj.weight [8C][C] 16-bit with rows

@@ -313,6 +313,26 @@ int vface_cond_mix(const float* a, int rows_a, float w_a, const float* b, int ro
     return vf_launch_cond_mix(a, rows_a, w_a, b, rows_b, w_b, c, rows_c, w_c, w_sum, out32, ldo32, out16, ldo16, B, N, dtype, S(stream));
 }
 
+int vface_id_prep(const float* img, int H, int W, const float* mask, int prep, int clip_img, void* out, int64_t ldo, int B, int dtype,
+                  void* stream) {
+    return vf_launch_id_prep(img, H, W, mask, prep, clip_img, out, ldo, B, dtype, S(stream));
+}
+
+int vface_prelu(const void* x, int64_t ldx, const float* slope, void* y, int64_t ldy, const float* za, const float* zb, void* z,
+                int64_t ldz, int64_t M, int C, int dtype, void* stream) {
+    return vf_launch_prelu(x, ldx, slope, y, ldy, za, zb, z, ldz, M, C, dtype, S(stream));
+}
+
+int vface_se_gate_add(const void* res, int64_t ldr, const float* g, int64_t ldg, const void* sc, int64_t lds, int sc_stride, int nimg,
+                      int H, int W, int C, void* y, int64_t ldy, const float* za, const float* zb, void* z, int64_t ldz, int dtype,
+                      void* stream) {
+    return vf_launch_se_gate_add(res, ldr, g, ldg, sc, lds, sc_stride, nimg, H, W, C, y, ldy, za, zb, z, ldz, dtype, S(stream));
+}
+
+int vface_l2norm_rows(const float* x, int64_t ldx, float* out, int64_t ldo, int B, int N, void* stream) {
+    return vf_launch_l2norm_rows(x, ldx, out, ldo, B, N, S(stream));
+}
+
 int vface_ffn_fused_supported(int64_t M, int C) { return vf_ffn_fused_supported((long)M, C) ? 1 : 0; }
 
 int vface_ffn_fused(const float* x32, int64_t ldx, const float* gamma, const float* beta, float eps, const void* W1, const float* b1,

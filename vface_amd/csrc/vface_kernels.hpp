@@ -183,6 +183,15 @@ int vf_launch_clip_embed(const void* tok, long ldt, int tok_f32, const float* cl
 int vf_launch_act(const void* x, long ldx, void* y, long ldy, long rows, int cols, int kind, int dtype, hipStream_t stream);
 int vf_launch_cond_mix(const float* a, int rows_a, float wa, const float* b, int rows_b, float wb, const float* c, int rows_c, float wc,
                        float wsum, float* out32, long ldo32, void* out16, long ldo16, int B, int N, int dtype, hipStream_t stream);
+// arcface.hip: glue of the identity network (ddpm.py:91-124, src/Face_models/encoders/{model_irse,helpers}.py)
+int vf_launch_id_prep(const float* img, int H, int W, const float* mask, int prep, int clip_img, void* out, long ldo, int B, int dtype,
+                      hipStream_t stream);
+int vf_launch_prelu(const void* x, long ldx, const float* slope, void* y, long ldy, const float* za, const float* zb, void* z, long ldz,
+                    long M, int C, int dtype, hipStream_t stream);
+int vf_launch_se_gate_add(const void* res, long ldr, const float* g, long ldg, const void* sc, long lds, int sc_stride, int nimg, int H,
+                          int W, int C, void* y, long ldy, const float* za, const float* zb, void* z, long ldz, int dtype,
+                          hipStream_t stream);
+int vf_launch_l2norm_rows(const float* x, long ldx, float* out, long ldo, int B, int N, hipStream_t stream);
 int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, int dtype, hipStream_t stream);
 int vf_launch_silu(const void* x, void* y, long count, int in_f32, int dtype, hipStream_t stream);
 int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, int N, float scale, int dtype, hipStream_t stream);

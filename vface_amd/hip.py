@@ -93,6 +93,11 @@ SIGNATURES = {
     "vface_clip_embed": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "vface_act": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "vface_cond_mix": (C.c_int, [_vp, _i32, _f32, _vp, _i32, _f32, _vp, _i32, _f32, _f32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "vface_id_prep": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
+    "vface_prelu": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp]),
+    "vface_se_gate_add": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _i32,
+                                    _vp]),
+    "vface_l2norm_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp]),
     "vface_ffn_fused_supported": (C.c_int, [_i64, _i32]),
     "vface_ffn_fused": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
     "vface_attn_out_ffn_fused": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _i64, _vp,
@@ -915,3 +920,67 @@ def cond_mix(operands, *, B: int, N: int, out32=None, out16=None, ldo32: int = 0
     rc = load().vface_cond_mix(*args, float(w_sum), _p(out32), ldo32, _p(out16), ldo16, B, N,
                                dtype_code(out16.dtype) if out16 is not None else F16, _stream())
     _check(rc, "vface_cond_mix")
+
+
+# ---- glue of the identity network (csrc/arcface.hip; include/vface_hip.h "identity features") ----
+ID_SIZE = 112                 # the network's input, after the pooling and crop chain of ``extract_feats``
+
+
+def id_prep(img: torch.Tensor, out: torch.Tensor, *, clip_img: bool = True, prep: bool = False, mask=None):
+    """``img`` fp32 planar [B, 3, H, W] -> ``out`` 16-bit [B 112 112, >= 8] (3 values, 5 zeros): ``IDLoss.extract_feats`` up to the
+    network.  ``prep``: ``img`` is a [-1, 1] frame (``mask`` fp32 [B, H, W]: times (1 - mask) first), brought to the CLIP image as
+    ``clip_patches(prep=True)`` does."""
+    for t in (img, mask):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise VFaceHipError("id_prep: img / mask must be contiguous fp32")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise VFaceHipError(f"id_prep: img must be [B, 3, H, W]; got {tuple(img.shape)}")
+    B, _, H, W = img.shape
+    if mask is not None and mask.numel() != B * H * W:
+        raise VFaceHipError("id_prep: mask must be [B, H, W]")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[1] < 8 or out.shape[0] != B * ID_SIZE * ID_SIZE:
+        raise VFaceHipError(f"id_prep: out must be a 16-bit [B*112*112, >= 8] view; got {tuple(out.shape)}")
+    rc = load().vface_id_prep(_p(img), H, W, _p(mask), int(prep), int(clip_img), _p(out), out.stride(0), B, dtype_code(out.dtype),
+                              _stream())
+    _check(rc, "vface_id_prep")
+
+
+def _zargs(z, za, zb, C_: int, what: str):
+    if z is None:
+        return None, None, None, 0
+    for t in (za, zb):
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C_:
+            raise VFaceHipError(f"{what}: with z, za and zb are contiguous fp32 [C]")
+    return _p(za), _p(zb), _p(z), z.stride(0)
+
+
+def prelu(x: torch.Tensor, slope: torch.Tensor, y: torch.Tensor, *, M: int, C_: int, z=None, za=None, zb=None,
+          ldx: Optional[int] = None, ldy: Optional[int] = None):
+    """``y = x > 0 ? x : slope[c] x`` on 16-bit views (``y`` may be ``x``); ``z = za[c] y32 + zb[c]`` if given."""
+    if slope.dtype != torch.float32 or not slope.is_contiguous() or slope.numel() != C_:
+        raise VFaceHipError("prelu: slope must be contiguous fp32 [C]")
+    pa, pb, pz, ldz = _zargs(z, za, zb, C_, "prelu")
+    rc = load().vface_prelu(_p(x), ldx if ldx is not None else x.stride(0), _p(slope), _p(y), ldy if ldy is not None else y.stride(0),
+                            pa, pb, pz, ldz, M, C_, dtype_code(x.dtype), _stream())
+    _check(rc, "vface_prelu")
+
+
+def se_gate_add(res: torch.Tensor, g: torch.Tensor, sc: torch.Tensor, y: torch.Tensor, *, nimg: int, H: int, W: int, C_: int,
+                sc_stride: int = 0, z=None, za=None, zb=None):
+    """``y = res * g[image] + shortcut``: ``sc_stride == 0`` reads row m of ``sc`` (the output's size, H x W); 1 | 2 reads pixel
+    (oy s, ox s) of the unit's H x W input ``sc``.  ``z = za[c] y32 + zb[c]`` if given."""
+    if g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1 or g.shape[0] < nimg:
+        raise VFaceHipError("se_gate_add: g is a 2-D fp32 view [nimg, C] with unit column stride")
+    pa, pb, pz, ldz = _zargs(z, za, zb, C_, "se_gate_add")
+    rc = load().vface_se_gate_add(_p(res), res.stride(0), _p(g), g.stride(0), _p(sc), sc.stride(0), sc_stride, nimg, H, W, C_, _p(y),
+                                  y.stride(0), pa, pb, pz, ldz, dtype_code(res.dtype), _stream())
+    _check(rc, "vface_se_gate_add")
+
+
+def l2norm_rows(x: torch.Tensor, out: torch.Tensor, *, B: int, N: int):
+    """``out[b] = x[b] / ||x[b]||_2`` on fp32 2-D views with unit column stride."""
+    for t in (x, out):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] < B or t.shape[1] < N:
+            raise VFaceHipError("l2norm_rows: x and out are fp32 [>= B, >= N] views with unit column stride")
+    rc = load().vface_l2norm_rows(_p(x), x.stride(0), _p(out), out.stride(0), B, N, _stream())
+    _check(rc, "vface_l2norm_rows")

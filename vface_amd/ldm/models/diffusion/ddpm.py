@@ -5,8 +5,10 @@ The first-stage VAE is optional: ``first_stage_config`` builds ``A
 and ``encode_first_stage`` / ``get_first_stage_encoding`` / ``decode_first_stage`` (:1402, :850-857, :1277-1284) work as in
 the reference.  The conditioning stage is optional too: ``cond_stage_config`` builds ``FrozenCLIPEmbedder`` under
 ``cond_stage_model`` with the projections of ddpm.py:695-733, and ``get_learned_conditioning`` (:859-870) /
-``conditioning_with_feat`` (:872-1045, the shipped configuration) run on the GPU; the ArcFace features and the dlib landmarks stay
-inputs.  Losses and training (the other ~2000 lines) are out of scope.
+``conditioning_with_feat`` (:872-1045, the shipped configuration) run on the GPU.  ``other_params.arcface`` adds ``IDLoss``
+(:91-124) under ``face_ID_model`` -- ArcFace IR-SE50 behind the pooling and crop chain of ``extract_feats``, on the HIP kernels
+(``vface_amd.arcface``) -- and ``conditioning_with_feat`` then computes ``id_feat`` itself; without it the features stay an input,
+as the dlib landmarks always do.  Losses and training (the other ~2000 lines) are out of scope.
 
 State-dict keys of the UNet are ``model.diffusion_model.*`` as in ``last.ckpt`` so
 ``load_state_dict(ckpt["state_dict"], strict=False)`` (VFace_inference_batch.py:118-135) fills it unchanged.
@@ -32,6 +34,39 @@ class DiffusionWrapper(nn.Module):
     def forward(self, x, t, c_concat=None, c_crossattn=None):
         cc = c_crossattn[0] if len(c_crossattn) == 1 else torch.cat(c_crossattn, 1)
         return self.diffusion_model(x, t, context=cc)
+
+
+class IDLoss(nn.Module):
+    """``IDLoss`` of ddpm.py:91-124 as far as inference uses it: ``facenet`` (``Backbone(112, 50, 'ir_se', drop_ratio=0.6)``, :98)
+    and ``extract_feats``.  ``arcface_path``: a state-dict file for ``facenet`` (:101), read with ``weights_only=True``; None leaves
+    the parameters to the caller (a checkpoint's ``face_ID_model.facenet.*`` keys, or a fill)."""
+
+    def __init__(self, arcface_path=None, multiscale: bool = False, compute_dtype: torch.dtype = torch.float16):
+        super().__init__()
+        from ....arcface import check_config
+        from ....src.Face_models.encoders.model_irse import Backbone
+        check_config(multi_scale=multiscale)
+        self.multiscale = False
+        self.facenet = Backbone(input_size=112, num_layers=50, drop_ratio=0.6, mode="ir_se", compute_dtype=compute_dtype)
+        if arcface_path is not None:
+            self.facenet.load_state_dict(torch.load(arcface_path, map_location="cpu", weights_only=True))
+        self.eval()
+        for p in self.parameters():
+            p.requires_grad = False
+
+    @torch.no_grad()
+    def extract_feats(self, x, clip_img: bool = True):
+        """:112-124: ``x [B, 3, H, W]`` on the device (CLIP-normalised with ``clip_img``) -> ``[features]``, fp32 [B, 512]."""
+        return [self.facenet.engine.extract_feats(x, clip_img=clip_img)]
+
+    @torch.no_grad()
+    def extract_feats_from_frames(self, frames, mask=None):
+        """``extract_feats(prep(frames * (1 - mask)))`` in one pass: ``frames [B, 3, H, W]`` in [-1, 1] at any size, ``prep`` the
+        resize and CLIP normalisation ``FrozenCLIPEmbedder.encode_from_frames`` applies (the two see the same image)."""
+        return [self.facenet.engine.extract_feats_from_frames(frames, mask)]
+
+    def forward(self, *a, **k):
+        raise NotImplementedError("IDLoss.forward is the training loss (ddpm.py:128-170); inference uses extract_feats only")
 
 
 class LatentDiffusion(nn.Module):
@@ -105,6 +140,10 @@ class LatentDiffusion(nn.Module):
         self.ID_proj_out = nn.Linear(512, 768)
         self.landmark_proj_out = nn.Linear(136, 768)
         self._cond_packed = None
+        arcface = op.get("arcface", False)
+        if arcface:      # True: parameters come from the checkpoint (face_ID_model.facenet.*) or a fill; a str: other_params.arcface_path
+            self.face_ID_model = IDLoss(arcface if isinstance(arcface, str) else None,
+                                        compute_dtype=cfg.get("params", {}).get("compute_dtype", torch.float16))
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """With a conditioning stage, the checkpoint's ``cond_stage_model.*`` keys that FrozenCLIPEmbedder holds without reading
@@ -116,6 +155,8 @@ class LatentDiffusion(nn.Module):
                           if not (k.startswith(pre) and k[len(pre):].startswith(clip.UNUSED_PREFIXES))}
             self.cond_stage_model._engine = None
             self._cond_packed = None
+            if hasattr(self, "face_ID_model"):
+                self.face_ID_model.facenet._engine = None
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
     def _apply(self, fn, *a, **k):
@@ -143,12 +184,16 @@ class LatentDiffusion(nn.Module):
     def conditioning_with_feat(self, x, landmarks=None, tar=None, id_feat=None, *, e_src=None, e_tar=None):
         """ddpm.py:872-1045 in the shipped configuration, ``[B, 1, 768]`` fp32:
             c  = proj_out_source(E(x)) + proj_out_target(E(prep(tar)))            x [1 | B, 3, 224, 224] CLIP-normalised
-            c2 = ID_proj_out(id_feat)[:, None]                                    id_feat [B, 512]: the ArcFace features, an INPUT here
+            c2 = ID_proj_out(id_feat)[:, None]                                    id_feat [1 | B, 512]: the ArcFace features; None:
+                                                                                  face_ID_model.extract_feats(x)[0] (:1010), which
+                                                                                  needs the stage built with other_params.arcface
             lm = landmark_proj_out(landmarks)[:, None]                            landmarks [B, 136]: dlib's, an input as in the reference
             (c clip_weight + c2 ID_weight + lm Landmarks_weight) / (clip_weight + ID_weight + Landmarks_weight)
         ``e_src`` / ``e_tar``: E(x) / E(prep(tar)) where the caller already has them -- a clip's source image is encoded once, and
         both conditions of a batch (scripts/VFace_inference_batch.py:442, :500) share E(prep(tar))."""
         from .... import hip
+        if id_feat is None and x is not None and hasattr(self, "face_ID_model"):
+            id_feat = self.face_ID_model.extract_feats(x)[0]
         if landmarks is None or id_feat is None or (tar is None and e_tar is None) or (x is None and e_src is None):
             raise NotImplementedError("the shipped configuration mixes CLIP (source and target), identity and landmark features: "
                                       "x, tar, landmarks and id_feat are all needed (id_feat = face_ID_model.extract_feats(x)[0], not computed here)")
@@ -161,6 +206,9 @@ class LatentDiffusion(nn.Module):
         B, Bs = e_tar.shape[0], e_src.shape[0]
         if Bs not in (1, B):
             raise ValueError(f"{Bs} source images for {B} target frames")
+        if id_feat.shape[0] not in (1, B):
+            raise ValueError(f"{id_feat.shape[0]} identity features for {B} target frames")
+        id_feat = id_feat.reshape(id_feat.shape[0], 512).expand(B, 512)      # one source for the batch: c2 is broadcast (:1038)
         f32 = lambda: torch.empty(B, 768, dtype=torch.float32, device=dev)
 
         def linear(a, name, M, out32, **kw):

@@ -90,6 +90,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "and conditioning_with_feat (:437-442, :491-500; vface_amd/clip.py) on the batch's frames: the intake's image "
                         "and mask with --intake, seeded images otherwise -- instead of seeded N(0, 1); the ArcFace features, the "
                         "landmarks and the source image stay seeded inputs")
+    p.add_argument("--arcface", action="store_true",
+                   help="with --clip_cond: the identity features of the mix come from ArcFace IR-SE50 on the GPU (IDLoss.extract_feats, "
+                        "ddpm.py:91-124, :1010; vface_amd/arcface.py) -- once for the source image, once per batch for the masked "
+                        "frames -- instead of seeded N(0, 1)")
     p.add_argument("--fusion", type=str, default="flow_fix", help="hook mode on the input-block attn1 modules")
     p.add_argument("--no_inversion", action="store_true", help="use random recon latents instead of DDIM inversion")
     p.add_argument("--flow_pixels", action="store_true",
@@ -191,7 +195,7 @@ def load_checkpoint(model, path: str, with_vae: bool = False, stub_unknown_globa
     ``model.diffusion_model.*`` always, ``first_stage_model.*`` when the first stage was built (``with_vae``),
     ``cond_stage_model.*`` and the projections of ``conditioning_with_feat`` when the conditioning stage was built (the text tower
     and the other entries FrozenCLIPEmbedder holds without reading are dropped); the ArcFace weights of a full LDM checkpoint
-    (``face_ID_model.*``) are outside the path and ignored.  Unlike the reference's
+    (``face_ID_model.facenet.*``) when the identity network was built (``--arcface``), otherwise they are outside the path and ignored.  Unlike the reference's
     non-strict load, a checkpoint that does not cover every parameter of the path raises instead of silently running on
     default-initialised weights.
 
@@ -215,6 +219,8 @@ def load_checkpoint(model, path: str, with_vae: bool = False, stub_unknown_globa
     prefixes = ("model.diffusion_model.",) + (("first_stage_model.",) if with_vae else ())
     if hasattr(model, "cond_stage_model"):      # the conditioning stage was built: its encoder and the four projections load too
         prefixes += ("cond_stage_model.", "proj_out_source.", "proj_out_target.", "ID_proj_out.", "landmark_proj_out.", "learnable_vector")
+    if hasattr(model, "face_ID_model"):
+        prefixes += ("face_ID_model.facenet.",)
     taken = {k: v for k, v in sd.items() if k.startswith(prefixes) and torch.is_tensor(v)}
     if not taken:
         raise RuntimeError(f"{path}: no key starts with {prefixes} -- not an LDM checkpoint of this model "
@@ -290,7 +296,11 @@ def run_synthetic(opt) -> dict:
     cfg = load_unet_config(opt.config)
     cfg["compute_dtype"] = dt
     clip_cond = bool(getattr(opt, "clip_cond", False))
-    stage_kw = dict(cond_stage_config=dict(params=dict(compute_dtype=dt))) if clip_cond else {}
+    arcface = bool(getattr(opt, "arcface", False))
+    if arcface and not clip_cond:
+        raise SystemExit("--arcface computes the identity features of the conditioning mix: it needs --clip_cond")
+    stage_kw = dict(cond_stage_config=dict(params=dict(compute_dtype=dt), **(dict(other_params=dict(arcface=True)) if arcface else {}))) \
+        if clip_cond else {}
     if opt.with_vae:
         from ..ldm.models.autoencoder import FFHQ_VAE_CONFIG
         model = LatentDiffusion(cfg, first_stage_config=dict(FFHQ_VAE_CONFIG, compute_dtype=dt), **stage_kw)
@@ -306,10 +316,15 @@ def run_synthetic(opt) -> dict:
         synth.fill_module_(model.cond_stage_model, seed=5)
         for name in ("proj_out_source", "proj_out_target", "ID_proj_out", "landmark_proj_out"):
             synth.fill_module_(getattr(model, name), seed=5, prefix=name + ".")
+        if arcface:
+            synth.fill_arcface_(model.face_ID_model.facenet, seed=5, prefix="face_ID_model.facenet.")
     model = model.to(dev).eval()
-    e_source = None
+    e_source, id_source = None, None
     if clip_cond:       # :437: the source image, resized and CLIP-normalised, is encoded once per clip and broadcast
-        e_source = model.get_learned_conditioning(synth.synth_normal("cli.source224", (1, 3, 224, 224)).to(dev))
+        source224 = synth.synth_normal("cli.source224", (1, 3, 224, 224)).to(dev)
+        e_source = model.get_learned_conditioning(source224)
+        if arcface:     # :437 -> ddpm.py:1010: the source's identity, once per clip
+            id_source = model.face_ID_model.extract_feats(source224)[0]
     sampler = DDIMSampler(model)
     sampler.hook_plan = HookPlan(fusion=opt.fusion, enabled=opt.fusion != "none")
     sampler.flow_gate = opt.flow_gate
@@ -388,6 +403,8 @@ def run_synthetic(opt) -> dict:
             ts_ = stage(stages, "_", time.time())
             enc = model.cond_stage_model
             e_tar = enc.encode_from_frames(tar)
+            if arcface:     # :442 the source's features; :500 those of the batch's masked frames, the network once per frame
+                idf, idf_t = id_source, model.face_ID_model.extract_feats_from_frames(tar, keep)[0]
             c = model.conditioning_with_feat(None, landmarks=lmk, id_feat=idf, e_src=e_source, e_tar=e_tar)
             tc = model.conditioning_with_feat(None, landmarks=lmk, id_feat=idf_t, e_src=enc.encode_from_frames(tar, keep), e_tar=e_tar)
             stage(stages, "clip_cond", ts_)

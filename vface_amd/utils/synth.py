@@ -99,3 +99,21 @@ def fill_parser_(module: torch.nn.Module, seed: int = 0, prefix: str = "") -> to
         if k.endswith("running_mean"):
             v.sub_(1.0)
     return module
+
+
+@torch.no_grad()
+def fill_arcface_(module: torch.nn.Module, seed: int = 0, prefix: str = "") -> torch.nn.Module:
+    """``fill_module_`` for the identity network (or one of its units): every ``*.running_mean`` shifted by -1 as ``fill_parser_``
+    does, and every PReLU slope moved from 1 +- 0.1 to 0.25 +- 0.1.
+
+    A PReLU's ``weight`` is a vector, so the plain fill makes every slope about 1: the activation is then the identity and a kernel
+    that lost its negative branch would compute the same network.  A PReLU is recognised by its module type, or in a bare state dict
+    by a 1-D ``weight`` with no ``running_mean`` beside it."""
+    fill_module_(module, seed, prefix)
+    sd = module.state_dict()
+    for k, v in sd.items():
+        if k.endswith("running_mean"):
+            v.sub_(1.0)
+        elif k.endswith(".weight") and v.dim() == 1 and k[:-len("weight")] + "running_mean" not in sd:
+            v.sub_(0.75)
+    return module
