@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 DTS = [torch.float16, torch.bfloat16]
 ERR_ARG, ERR_SHAPE = -1, -3
-CAP_ITEMS = 16384 * 256            # grid1's cap times the block: beyond it a thread takes more than one item
+CAP_ITEMS = 16384 * 256            # the launchers' vf_grid cap times the block: beyond it a thread takes more than one item
 
 
 def hip():

@@ -16,14 +16,17 @@ HEADER = os.path.join(ROOT, "include", "vface_hip.h")
 LIB = os.path.join(ROOT, "vface_amd", "lib", "libvface_hip.so")
 
 
-def _declared():
+def _declarations():
+    """(return type, name, [argument declaration, ...]) of every function the header declares."""
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(?:int64_t|int|size_t|const char\*)\s+(vface_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
-        args = m.group(2).strip()
-        decls[m.group(1)] = 0 if args in ("", "void") else len(args.split(","))
-    return decls
+    for m in re.finditer(r"\b(int64_t|int|size_t|const char\*)\s+(vface_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
+        args = m.group(3).strip()
+        yield m.group(1), m.group(2), [] if args in ("", "void") else [a.strip() for a in args.split(",")]
+
+
+def _declared():
+    return {name: len(args) for _, name, args in _declarations()}
 
 
 def test_library_exports_every_declared_symbol():
@@ -45,6 +48,38 @@ def test_ctypes_table_matches_header():
     assert set(decls) == set(hip.SIGNATURES)
     for name, n in decls.items():
         assert len(hip.SIGNATURES[name][1]) == n, name
+
+
+def _ctypes_kind(t):
+    from vface_amd import hip
+    if t is ctypes.c_void_p or t is ctypes.c_char_p or t is hip._s32p:
+        return "pointer"
+    return {ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t", ctypes.c_float: "float", ctypes.c_int: "int"}[t]
+
+
+def _c_kind(decl):
+    if "*" in decl:
+        return "pointer"
+    words = decl.split()[:-1]          # the last word is the parameter's name
+    for kind in ("int64_t", "size_t", "float"):
+        if kind in words:
+            return kind
+    return "int"
+
+
+def test_ctypes_table_matches_header_type_for_type():
+    """A pointer bound as a 32-bit integer, or an int64_t as an int, still has the right argument COUNT: it would reach a kernel as
+    a truncated address or stride.  So every return type and every argument's kind is compared, for the whole header."""
+    from vface_amd import hip
+    returns = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+    assert len({ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_void_p}) == 5    # distinct ctypes classes
+    checked = 0
+    for ret, name, args in _declarations():
+        restype, argtypes = hip.SIGNATURES[name]
+        assert restype is returns[ret], (name, ret, restype)
+        assert [_ctypes_kind(t) for t in argtypes] == [_c_kind(a) for a in args], name
+        checked += 1
+    assert checked >= 74
 
 
 def test_no_gpu_means_loud_failure():

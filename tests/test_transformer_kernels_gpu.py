@@ -12,7 +12,7 @@ carry an offset per 64-row slice where column statistics are checked.  Fused cha
 kernel exposes the intermediate (st_front: t0 from x32 and the device's ab, ln from the device's t0, qkv from the device's ln bits;
 POST: y from the PRE form's fp32 output of the same inputs) and through the whole chain's bound otherwise.
 
-``gn_apply_kernel`` has two instantiations and no query: the launcher (csrc/pointwise.hip, vf_launch_gn_apply) starts at ppb = 128
+``gn_apply_kernel`` has two instantiations and no query: the launcher (csrc/pointwise.hip, vface_groupnorm_apply) starts at ppb = 128
 pixels per workgroup and halves it ``while (ppb > 4 && nimg * ceil(hw / ppb) < 1024)``; the one-pixel-per-trip form runs ``if (ppb >
 32)``, i.e. iff nimg * ceil(hw / 64) >= 1024: nimg = 8, hw = 8200 gives 8 * 129 = 1032 (and 8 * 65 = 520 < 1024 at ppb = 128, so
 ppb = 64).  The persistent walks of st_front need more token tiles than CUs: 2 * CUs + 3, the CU count from the device properties."""

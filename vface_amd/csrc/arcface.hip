@@ -16,20 +16,11 @@
 //
 // HBM-bound byte movers: 16-byte accesses along the channel axis, one thread per 8 channels (the prep: per output pixel; the norm:
 // one wave per row).  No atomics, every sum in a fixed order: a sample's bits do not depend on the batch it is in.
-#include <algorithm>
-
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
-
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
-inline unsigned grid1(long total) { return (unsigned)std::min<long>((total + 255) / 256, 16384); }
-
-#define DISPATCH_DTYPE(dtype, CALL)                                \
-    if ((dtype) == VF_DTYPE_F16) { using TT = F16; CALL; }         \
-    else if ((dtype) == VF_DTYPE_BF16) { using TT = BF16; CALL; }  \
-    else return VF_ERR_DTYPE;
 
 constexpr int ID_POOL = 256, ID_Y0 = 35, ID_X0 = 32, ID_CROP = 188, ID_OUT = 112, CLIP_SIZE = 224;
 
@@ -224,8 +215,9 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
 
 }  // namespace
 
-int vf_launch_id_prep(const float* img, int H, int W, const float* mask, int prep, int clip_img, void* out, long ldo, int B, int dtype,
-                      hipStream_t stream) {
+extern "C" int vface_id_prep(const float* img, int H, int W, const float* mask, int prep, int clip_img, void* out, int64_t ldo, int B,
+                             int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!img || !out || B <= 0 || H <= 0 || W <= 0) return VF_ERR_ARG;
     if (!prep && mask) return VF_ERR_ARG;
     if (prep && !clip_img) return VF_ERR_ARG;                    // the frame becomes a CLIP-normalised image: the chain un-normalises it
@@ -237,17 +229,18 @@ int vf_launch_id_prep(const float* img, int H, int W, const float* mask, int pre
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         if (prep)
-            hipLaunchKernelGGL((id_prep_kernel<TT, true>), dim3(grid1(total)), dim3(256), 0, stream, img, H, W, mask, clip_img, (E*)out, ldo,
+            hipLaunchKernelGGL((id_prep_kernel<TT, true>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, img, H, W, mask, clip_img, (E*)out, ldo,
                                total);
         else
-            hipLaunchKernelGGL((id_prep_kernel<TT, false>), dim3(grid1(total)), dim3(256), 0, stream, img, H, W, mask, clip_img, (E*)out, ldo,
+            hipLaunchKernelGGL((id_prep_kernel<TT, false>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, img, H, W, mask, clip_img, (E*)out, ldo,
                                total);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_prelu(const void* x, long ldx, const float* slope, void* y, long ldy, const float* za, const float* zb, void* z, long ldz,
-                    long M, int C, int dtype, hipStream_t stream) {
+extern "C" int vface_prelu(const void* x, int64_t ldx, const float* slope, void* y, int64_t ldy, const float* za, const float* zb, void* z,
+                           int64_t ldz, int64_t M, int C, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !slope || !y || M <= 0 || C <= 0) return VF_ERR_ARG;
     if (z && (!za || !zb || z == x || z == y)) return VF_ERR_ARG;
     if (ldx < C || ldy < C || (z && ldz < C)) return VF_ERR_SHAPE;
@@ -256,15 +249,16 @@ int vf_launch_prelu(const void* x, long ldx, const float* slope, void* y, long l
         return VF_ERR_ALIGN;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((prelu_kernel<TT>), dim3(grid1(M * (C / 8))), dim3(256), 0, stream, (const E*)x, ldx, slope, (E*)y, ldy, za, zb,
+        hipLaunchKernelGGL((prelu_kernel<TT>), dim3(vf_grid(M * (C / 8), 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, slope, (E*)y, ldy, za, zb,
                            (E*)z, ldz, M, C);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_se_gate_add(const void* res, long ldr, const float* g, long ldg, const void* sc, long lds, int sc_stride, int nimg, int H,
-                          int W, int C, void* y, long ldy, const float* za, const float* zb, void* z, long ldz, int dtype,
-                          hipStream_t stream) {
+extern "C" int vface_se_gate_add(const void* res, int64_t ldr, const float* g, int64_t ldg, const void* sc, int64_t lds, int sc_stride,
+                                 int nimg, int H, int W, int C, void* y, int64_t ldy, const float* za, const float* zb, void* z,
+                                 int64_t ldz, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!res || !g || !sc || !y || nimg <= 0 || H <= 0 || W <= 0 || C <= 0) return VF_ERR_ARG;
     if (z && (!za || !zb || z == res || z == y || z == sc)) return VF_ERR_ARG;
     if (sc_stride < 0 || sc_stride > 2) return VF_ERR_SHAPE;
@@ -279,16 +273,17 @@ int vf_launch_se_gate_add(const void* res, long ldr, const float* g, long ldg, c
     const long M = (long)nimg * OH * OW;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((se_gate_add_kernel<TT>), dim3(grid1(M * (C / 8))), dim3(256), 0, stream, (const E*)res, ldr, g, ldg,
+        hipLaunchKernelGGL((se_gate_add_kernel<TT>), dim3(vf_grid(M * (C / 8), 256, 16384)), dim3(256), 0, stream, (const E*)res, ldr, g, ldg,
                            (const E*)sc, lds, sc_stride, H, W, OH, OW, (E*)y, ldy, za, zb, (E*)z, ldz, M, C);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_l2norm_rows(const float* x, long ldx, float* out, long ldo, int B, int N, hipStream_t stream) {
+extern "C" int vface_l2norm_rows(const float* x, int64_t ldx, float* out, int64_t ldo, int B, int N, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !out || B <= 0 || N <= 0) return VF_ERR_ARG;
     if (ldx < N || ldo < N) return VF_ERR_SHAPE;
     if ((N & 3) || (ldx & 3) || (ldo & 3) || (((uintptr_t)x | (uintptr_t)out) & 15)) return VF_ERR_ALIGN;
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3((unsigned)(((long)B + 3) / 4)), dim3(256), 0, stream, x, ldx, out, ldo, B, N);
-    return ok();
+    return vf_launched();
 }

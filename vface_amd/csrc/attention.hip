@@ -16,6 +16,7 @@
 //   how the hook's "replace" / chunks==2 injection (pnp_utils.py:136-142,259-262) and fft_vfixed's
 //   V broadcast (:255-256) run without copying anything.
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -653,7 +654,7 @@ int launch(const AttnParams& p, hipStream_t stream) {
     if (lds > 64 * 1024 && !attr_set.set_lds(reinterpret_cast<const void*>(kern), (int)lds)) return VF_ERR_LAUNCH;
     dim3 grid(((p.n + 16 * NWV * QT - 1) / (16 * NWV * QT)) * p.heads * p.B);
     hipLaunchKernelGGL(kern, grid, dim3(64 * NWV), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 template <class TT, bool LAZY>

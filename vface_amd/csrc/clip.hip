@@ -18,20 +18,11 @@
 //
 // HBM-bound byte movers, one thread per 8 (16-bit) or 4 (fp32) columns (the embedding: one wave per row).  No atomics, every sum
 // in a fixed order: a sample's bits do not depend on the batch it is in.  Contraction is OFF where the reference rounds every product (ATen's interpolation and the mix).
-#include <algorithm>
-
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
-
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
-inline unsigned grid1(long total) { return (unsigned)std::min<long>((total + 255) / 256, 16384); }
-
-#define DISPATCH_DTYPE(dtype, CALL)                                \
-    if ((dtype) == VF_DTYPE_F16) { using TT = F16; CALL; }         \
-    else if ((dtype) == VF_DTYPE_BF16) { using TT = BF16; CALL; }  \
-    else return VF_ERR_DTYPE;
 
 constexpr int PATCH = 14, PATCH_K = 3 * PATCH * PATCH, PATCH_KP = 640;      // 588 columns, padded to a multiple of 64
 
@@ -201,8 +192,9 @@ __global__ __launch_bounds__(256) void cond_mix_kernel(MixOperand a, MixOperand 
 
 }  // namespace
 
-int vf_launch_clip_patches(const float* img, int H, int W, const float* mask, int prep, void* out, long ldo, int B, int G, int* dbg_x0,
-                           int* dbg_y0, int dtype, hipStream_t stream) {
+extern "C" int vface_clip_patches(const float* img, int H, int W, const float* mask, int prep, void* out, int64_t ldo, int B, int G,
+                                  int32_t* dbg_x0, int32_t* dbg_y0, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!img || !out || B <= 0 || G <= 0 || H <= 0 || W <= 0) return VF_ERR_ARG;
     if (!prep && (mask || dbg_x0 || dbg_y0)) return VF_ERR_ARG;
     if (G > 64 || ldo < PATCH_KP || (!prep && (H != PATCH * G || W != PATCH * G))) return VF_ERR_SHAPE;
@@ -212,17 +204,18 @@ int vf_launch_clip_patches(const float* img, int H, int W, const float* mask, in
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         if (prep)
-            hipLaunchKernelGGL((clip_patches_kernel<TT, true>), dim3(grid1(total)), dim3(256), 0, stream, img, H, W, mask, (E*)out, ldo, G,
+            hipLaunchKernelGGL((clip_patches_kernel<TT, true>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, img, H, W, mask, (E*)out, ldo, G,
                                total, dbg_x0, dbg_y0);
         else
-            hipLaunchKernelGGL((clip_patches_kernel<TT, false>), dim3(grid1(total)), dim3(256), 0, stream, img, H, W, mask, (E*)out, ldo, G,
+            hipLaunchKernelGGL((clip_patches_kernel<TT, false>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, img, H, W, mask, (E*)out, ldo, G,
                                total, dbg_x0, dbg_y0);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_clip_embed(const void* tok, long ldt, int tok_f32, const float* cls, const float* pos, const float* gamma,
-                         const float* beta, float eps, float* x32, long ldo, int B, int P, int C, int dtype, hipStream_t stream) {
+extern "C" int vface_clip_embed(const void* tok, int64_t ldt, int tok_f32, const float* cls, const float* pos, const float* gamma,
+                                const float* beta, float eps, float* x32, int64_t ldo, int B, int P, int C, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!tok || !cls || !pos || !x32 || B <= 0 || P <= 0 || C <= 0 || ((gamma != nullptr) != (beta != nullptr))) return VF_ERR_ARG;
     if (ldt < C || ldo < C) return VF_ERR_SHAPE;
     if ((C & 7) || (ldt & 7) || (ldo & 3)) return VF_ERR_ALIGN;
@@ -232,17 +225,18 @@ int vf_launch_clip_embed(const void* tok, long ldt, int tok_f32, const float* cl
     if (tok_f32) {
         hipLaunchKernelGGL((clip_embed_kernel<float>), grid, dim3(256), 0, stream, (const float*)tok, ldt, cls, pos, gamma, beta, eps, x32, ldo,
                            P, C, rows);
-        return ok();
+        return vf_launched();
     }
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         hipLaunchKernelGGL((clip_embed_kernel<E>), grid, dim3(256), 0, stream, (const E*)tok, ldt, cls, pos, gamma, beta, eps, x32, ldo, P, C,
                            rows);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_act(const void* x, long ldx, void* y, long ldy, long rows, int cols, int kind, int dtype, hipStream_t stream) {
+extern "C" int vface_act(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, int kind, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !y || rows <= 0 || cols <= 0) return VF_ERR_ARG;
     if (kind != 0 && kind != 1) return VF_ERR_ARG;
     if (ldx < cols || ldy < cols) return VF_ERR_SHAPE;
@@ -250,14 +244,16 @@ int vf_launch_act(const void* x, long ldx, void* y, long ldy, long rows, int col
     const long total = rows * (cols / 8);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        if (kind == 0) hipLaunchKernelGGL((act_kernel<TT, 0>), dim3(grid1(total)), dim3(256), 0, stream, (const E*)x, ldx, (E*)y, ldy, rows, cols);
-        else hipLaunchKernelGGL((act_kernel<TT, 1>), dim3(grid1(total)), dim3(256), 0, stream, (const E*)x, ldx, (E*)y, ldy, rows, cols);
+        if (kind == 0) hipLaunchKernelGGL((act_kernel<TT, 0>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, (E*)y, ldy, rows, cols);
+        else hipLaunchKernelGGL((act_kernel<TT, 1>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, (E*)y, ldy, rows, cols);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_cond_mix(const float* a, int rows_a, float wa, const float* b, int rows_b, float wb, const float* c, int rows_c, float wc,
-                       float wsum, float* out32, long ldo32, void* out16, long ldo16, int B, int N, int dtype, hipStream_t stream) {
+extern "C" int vface_cond_mix(const float* a, int rows_a, float wa, const float* b, int rows_b, float wb, const float* c, int rows_c,
+                              float wc, float wsum, float* out32, int64_t ldo32, void* out16, int64_t ldo16, int B, int N, int dtype,
+                              void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (B <= 0 || N <= 0 || (!out32 && !out16) || (!a && !b && !c)) return VF_ERR_ARG;
     if (!(wsum != 0.0f)) return VF_ERR_ARG;
     if ((a && rows_a != 1 && rows_a != B) || (b && rows_b != 1 && rows_b != B) || (c && rows_c != 1 && rows_c != B)) return VF_ERR_SHAPE;
@@ -270,8 +266,8 @@ int vf_launch_cond_mix(const float* a, int rows_a, float wa, const float* b, int
     const long total = (long)B * (N / 4);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((cond_mix_kernel<TT>), dim3(grid1(total)), dim3(256), 0, stream, oa, ob, oc, wsum, out32, ldo32, (E*)out16, ldo16, N,
+        hipLaunchKernelGGL((cond_mix_kernel<TT>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, oa, ob, oc, wsum, out32, ldo32, (E*)out16, ldo16, N,
                            total);
     });
-    return ok();
+    return vf_launched();
 }

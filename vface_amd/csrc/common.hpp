@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vface_hip.h"
+
 typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 b8_t __attribute__((ext_vector_type(8)));
@@ -162,15 +164,15 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// error codes of the C ABI
+// error codes and dtype numbers of the C ABI, under the names the kernels use
 enum {
-    VF_OK = 0,
-    VF_ERR_ARG = -1,      // null pointer / non-positive size
-    VF_ERR_ALIGN = -2,    // pointer or leading dimension not aligned as the kernel requires
-    VF_ERR_SHAPE = -3,    // unsupported shape (head dim, channel multiple, ...)
-    VF_ERR_DTYPE = -4,
-    VF_ERR_LAUNCH = -5,   // hipGetLastError() after launch
+    VF_OK = VFACE_OK,
+    VF_ERR_ARG = VFACE_ERR_ARG,        // null pointer / non-positive size
+    VF_ERR_ALIGN = VFACE_ERR_ALIGN,    // pointer or leading dimension not aligned as the kernel requires
+    VF_ERR_SHAPE = VFACE_ERR_SHAPE,    // unsupported shape (head dim, channel multiple, ...)
+    VF_ERR_DTYPE = VFACE_ERR_DTYPE,
+    VF_ERR_LAUNCH = VFACE_ERR_LAUNCH,  // hipGetLastError() after launch
 };
 
-#define VF_DTYPE_F16 0
-#define VF_DTYPE_BF16 1
+#define VF_DTYPE_F16 VFACE_F16
+#define VF_DTYPE_BF16 VFACE_BF16

@@ -29,6 +29,7 @@
 //   (16-bit or the fp32 stream) summed in fp32, single rounding, optional fp32 carrier, per-64-pixel column statistics.
 #include <type_traits>
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -658,7 +659,7 @@ int launch_patch(const VfGemmPlan& pl, hipStream_t stream) {
     static VfOncePerDevice attr_set[5];
     if (!attr_set[pl.form].set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(512), pl.lds_bytes, stream, pl.p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 template <class TT>
@@ -668,7 +669,7 @@ int launch_conv(const VfGemmPlan& pl, hipStream_t stream) {
         static VfOncePerDevice attr_set;
         if (!attr_set.set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
         hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(512), pl.lds_bytes, stream, pl.p);
-        return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+        return vf_launched();
     }
     if (pl.mode == 3) return pl.bn == 160 ? launch_patch<TT, 5, 3, 3>(pl, stream) : launch_patch<TT, 4, 3, 3>(pl, stream);
     // (the 2 x 2 window: convolutions only -- the plain-GEMM form runs the 3 x 3 instantiation without window tiles)

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -685,7 +686,7 @@ int launch_c(const FfnParams& p, hipStream_t stream) {
     static VfOncePerDevice attr_set;
     if (lds > 64 * 1024 && !attr_set.set_lds(reinterpret_cast<const void*>(kern), (int)lds)) return VF_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(p.M / 128), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 template <class TT>

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -897,7 +898,7 @@ int launch_one(const VfGemmPlan& pl, hipStream_t stream) {
     static VfOncePerDevice attr_set[6];
     if (pl.lds_bytes > 64 * 1024 && !attr_set[which].set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(256), pl.lds_bytes, stream, pl.p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 template <class TT, int MODE>
@@ -955,6 +956,6 @@ int vf_launch_gemm(const GemmParams& p, int dtype, hipStream_t stream) {
     const dim3 grid((pl.p.M + 63) / 64, (pl.p.N + 255) / 256);
     if (dtype == VF_DTYPE_F16) hipLaunchKernelGGL(splitk_reduce_kernel<F16>, grid, dim3(256), 0, stream, pl.p);
     else hipLaunchKernelGGL(splitk_reduce_kernel<BF16>, grid, dim3(256), 0, stream, pl.p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 #endif  // VF_GEMM_TU

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -441,7 +442,7 @@ int launch_big(const VfGemmPlan& pl, hipStream_t stream) {
     static VfOncePerDevice attr_set;
     if (!attr_set.set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(512), pl.lds_bytes, stream, pl.p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 template <class TT, int EPI>

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -160,5 +161,5 @@ int vf_launch_conv_in16(const VfGemmPlan& pl, int dtype, hipStream_t stream) {
     const int nslices = pl.p.M / 64;
     if (dtype == VF_DTYPE_F16) hipLaunchKernelGGL(conv3x3_c16_kernel<F16>, grid, dim3(256), 0, stream, pl.p, pl.slices_per_wg, nslices);
     else hipLaunchKernelGGL(conv3x3_c16_kernel<BF16>, grid, dim3(256), 0, stream, pl.p, pl.slices_per_wg, nslices);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }

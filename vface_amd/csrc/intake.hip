@@ -20,12 +20,10 @@
 // with other tap tables (vface_amd/scripts/intake.py).  HBM-bound byte work, no LDS, one thread per output pixel, coalesced along x.
 // Contraction is OFF: Pillow (C, no FMA on generic x86-64) and ATen round every product.
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
-
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
-inline unsigned grid1(long total) { return (unsigned)std::min<long>((total + 255) / 256, 8192); }
 
 // frames [F][Hs][Ws][3]; quads [F][8] = Pillow's QUAD coefficients in WINDOW coordinates; windows [F][4] = (x0, y0, x1, y1) in the
 // frame (0 <= x0 < x1 <= Ws, 0 <= y0 < y1 <= Hs: checked by the caller, re-clamped here so that no tap can leave the frame);
@@ -127,23 +125,25 @@ __global__ __launch_bounds__(256) void mask_latent_kernel(const unsigned char* _
 
 }  // namespace
 
-int vf_launch_quad_crop(const unsigned char* frames, int Ws, int Hs, unsigned char* out, int S, int nframes, const double* quads,
-                        const int* windows, hipStream_t stream) {
+extern "C" int vface_quad_crop(const uint8_t* frames, int Ws, int Hs, uint8_t* out, int S, int nframes, const double* quads,
+                               const int32_t* windows, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!frames || !out || !quads || !windows || nframes <= 0 || Ws <= 0 || Hs <= 0 || S <= 0) return VF_ERR_ARG;
     if ((long)Ws * Hs > 0x7fffffffL / 3 || (long)S * S > 0x7fffffffL / 3) return VF_ERR_SHAPE;
-    hipLaunchKernelGGL(quad_crop_kernel, dim3(grid1((long)S * S), nframes), dim3(256), 0, stream, frames, Ws, Hs, out, S, quads, windows);
-    return ok();
+    hipLaunchKernelGGL(quad_crop_kernel, dim3(vf_grid((long)S * S, 256, 8192), nframes), dim3(256), 0, stream, frames, Ws, Hs, out, S, quads, windows);
+    return vf_launched();
 }
 
-int vf_launch_dataset_tensors(const unsigned char* crop, const unsigned char* label, const unsigned char* member, int W, int H,
-                              float* image, float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH,
-                              int nframes, hipStream_t stream) {
+extern "C" int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, const uint8_t* member, int W, int H, float* image,
+                                     float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH, int nframes,
+                                     void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!crop || !label || !member || !image || !inpaint_image || !inpaint_mask || !mask_latent) return VF_ERR_ARG;
     if (nframes <= 0 || W <= 0 || H <= 0 || OW <= 0 || OH <= 0) return VF_ERR_ARG;
     if ((long)W * H > 0x7fffffffL / 3) return VF_ERR_SHAPE;
-    hipLaunchKernelGGL(dataset_tensors_kernel, dim3(grid1((long)W * H), nframes), dim3(256), 0, stream, crop, label, member, image,
+    hipLaunchKernelGGL(dataset_tensors_kernel, dim3(vf_grid((long)W * H, 256, 8192), nframes), dim3(256), 0, stream, crop, label, member, image,
                        inpaint_image, inpaint_mask, (long)W * H);
-    hipLaunchKernelGGL(mask_latent_kernel, dim3(grid1((long)OW * OH), nframes), dim3(256), 0, stream, label, member, W, H, mask_latent,
+    hipLaunchKernelGGL(mask_latent_kernel, dim3(vf_grid((long)OW * OH, 256, 8192), nframes), dim3(256), 0, stream, label, member, W, H, mask_latent,
                        OW, OH);
-    return ok();
+    return vf_launched();
 }

@@ -13,6 +13,7 @@
 // (Computing the sinusoidal embedding inside the first layer's launch was tried: 40 sinf / cosf per lane, repeated by all 160 waves,
 // took 34 us against 7.9 + 6 for the embedding kernel and a plain launch -- the embedding stays its own launch.)
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -94,7 +95,7 @@ int launch_t(const LinearSmallParams& p, hipStream_t stream) {
         case 20: hipLaunchKernelGGL((linear_small_kernel<TT, 20>), grid, dim3(256), 0, stream, p); break;
         default: return VF_ERR_SHAPE;
     }
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 }  // namespace

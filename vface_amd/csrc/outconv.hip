@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -160,7 +161,7 @@ int launch_t(const OutConvParams& p, hipStream_t stream) {
     else if (p.Cout == 3) { if (p.in_f32) OC_LAUNCH(true, 3); else OC_LAUNCH(false, 3); }
     else return VF_ERR_SHAPE;
 #undef OC_LAUNCH
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 }  // namespace

@@ -21,17 +21,10 @@
 // every sum has a fixed order, so a frame's bits do not depend on the batch it is in.  Contraction is OFF where the reference
 // rounds every product (ATen's interpolation; tests/parse_model.py restates the order).
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
-
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
-inline unsigned grid1(long total, int per = 256) { return (unsigned)std::min<long>((total + per - 1) / per, 16384); }
-
-#define DISPATCH_DTYPE(dtype, CALL)                                \
-    if ((dtype) == VF_DTYPE_F16) { using TT = F16; CALL; }         \
-    else if ((dtype) == VF_DTYPE_BF16) { using TT = BF16; CALL; }  \
-    else return VF_ERR_DTYPE;
 
 struct Taps8 { float k[8]; };
 
@@ -209,8 +202,9 @@ __global__ __launch_bounds__(256) void upsample_argmax_u8_kernel(const float* __
 
 }  // namespace
 
-int vf_launch_parse_prefilter(const unsigned char* crops, int W2, int H2, int factor, void* out, long ldo, int nframes, int dtype,
-                              hipStream_t stream) {
+extern "C" int vface_parse_prefilter(const uint8_t* crops, int W2, int H2, int factor, void* out, int64_t ldo, int nframes, int dtype,
+                                     void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!crops || !out || nframes <= 0 || W2 <= 0 || H2 <= 0) return VF_ERR_ARG;
     if (factor != 2 || (W2 & 1) || (H2 & 1) || W2 < 8 || H2 < 8 || ldo < 8) return VF_ERR_SHAPE;     // reflection needs 3 < size
     if ((long)W2 * H2 > 0x7fffffffL / 3) return VF_ERR_SHAPE;
@@ -229,12 +223,14 @@ int vf_launch_parse_prefilter(const unsigned char* crops, int W2, int H2, int fa
     const long total = (long)nframes * (H2 / 2) * (W2 / 2);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((parse_prefilter_kernel<TT>), dim3(grid1(total)), dim3(256), 0, stream, crops, W2, H2, taps, (E*)out, ldo, total);
+        hipLaunchKernelGGL((parse_prefilter_kernel<TT>), dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, crops, W2, H2, taps, (E*)out, ldo, total);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_maxpool3x3s2(const void* x, long ldx, int nimg, int H, int W, int C, void* y, long ldy, int dtype, hipStream_t stream) {
+extern "C" int vface_maxpool3x3s2(const void* x, int64_t ldx, int nimg, int H, int W, int C, void* y, int64_t ldy, int dtype,
+                                  void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !y || nimg <= 0 || H <= 0 || W <= 0 || C <= 0) return VF_ERR_ARG;
     if (ldx < C || ldy < C) return VF_ERR_SHAPE;
     if ((C & 7) || (ldx & 7) || (ldy & 7) || (((uintptr_t)x | (uintptr_t)y) & 15)) return VF_ERR_ALIGN;
@@ -242,14 +238,16 @@ int vf_launch_maxpool3x3s2(const void* x, long ldx, int nimg, int H, int W, int 
     const long M = (long)nimg * OH * OW;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((maxpool3x3s2_kernel<TT>), dim3(grid1(M * (C / 8))), dim3(256), 0, stream, (const E*)x, ldx, H, W, C, OH, OW, (E*)y,
+        hipLaunchKernelGGL((maxpool3x3s2_kernel<TT>), dim3(vf_grid(M * (C / 8), 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, H, W, C, OH, OW, (E*)y,
                            ldy, M);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_channel_gate(const void* x, long ldx, const float* g, long ldg, const float* rvec, long ldrv, const void* rten, long ldr,
-                           int add_x, void* y, long ldy, long M, int hw, int C, int dtype, hipStream_t stream) {
+extern "C" int vface_channel_gate(const void* x, int64_t ldx, const float* g, int64_t ldg, const float* rvec, int64_t ldrv,
+                                  const void* rten, int64_t ldr, int add_x, void* y, int64_t ldy, int64_t M, int hw, int C, int dtype,
+                                  void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !g || !y || M <= 0 || hw <= 0 || C <= 0) return VF_ERR_ARG;
     if ((rvec != nullptr) + (rten != nullptr) + (add_x != 0) > 1) return VF_ERR_ARG;
     if (M % hw || ldx < C || ldy < C || ldg < C || (rvec && ldrv < C) || (rten && ldr < C)) return VF_ERR_SHAPE;
@@ -257,28 +255,30 @@ int vf_launch_channel_gate(const void* x, long ldx, const float* g, long ldg, co
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)rten | (uintptr_t)g | (uintptr_t)rvec) & 15) return VF_ERR_ALIGN;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((channel_gate_kernel<TT>), dim3(grid1(M * (C / 8))), dim3(256), 0, stream, (const E*)x, ldx, g, ldg, rvec, ldrv,
+        hipLaunchKernelGGL((channel_gate_kernel<TT>), dim3(vf_grid(M * (C / 8), 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, g, ldg, rvec, ldrv,
                            (const E*)rten, ldr, add_x, (E*)y, ldy, M, hw, C);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_pooled_linear(const float* a, long lda, int sa, const float* W, const float* bias, float* out, long ldo, int nimg, int N,
-                            int K, int act, hipStream_t stream) {
+extern "C" int vface_pooled_linear(const float* a, int64_t lda, int sa, const float* W, const float* bias, float* out, int64_t ldo,
+                                   int nimg, int N, int K, int act, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!a || !W || !out || nimg <= 0 || N <= 0 || K <= 0 || sa <= 0) return VF_ERR_ARG;
     if (act != 0 && act != 1 && act != 3) return VF_ERR_ARG;
     if (ldo < N || lda < (long)(K - 1) * sa + 1) return VF_ERR_SHAPE;
     hipLaunchKernelGGL(pooled_linear_kernel, dim3((unsigned)(((long)nimg * N + 3) / 4)), dim3(256), 0, stream, a, lda, sa, W, bias, out, ldo,
                        nimg, N, K, act);
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_upsample_argmax_u8(const float* logits, long ld, int nframes, int h, int w, int ncls, const unsigned char* table,
-                                 unsigned char* out, int H, int W, hipStream_t stream) {
+extern "C" int vface_upsample_argmax_u8(const float* logits, int64_t ld, int nframes, int h, int w, int ncls, const uint8_t* table,
+                                        uint8_t* out, int H, int W, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!logits || !table || !out || nframes <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return VF_ERR_ARG;
     if (ncls <= 0 || ncls > 32 || ld < ncls) return VF_ERR_SHAPE;
     if ((ld & 3) || ((uintptr_t)logits & 15)) return VF_ERR_ALIGN;
     const long total = (long)nframes * H * W;
-    hipLaunchKernelGGL(upsample_argmax_u8_kernel, dim3(grid1(total)), dim3(256), 0, stream, logits, ld, h, w, ncls, table, out, H, W, total);
-    return ok();
+    hipLaunchKernelGGL(upsample_argmax_u8_kernel, dim3(vf_grid(total, 256, 16384)), dim3(256), 0, stream, logits, ld, h, w, ncls, table, out, H, W, total);
+    return vf_launched();
 }

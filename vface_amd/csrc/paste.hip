@@ -19,11 +19,10 @@
 // All HBM-bound byte work (a 1080p frame is 6 MB); no LDS, one thread per output pixel or sample, coalesced along x.
 // Contraction is OFF for the double / float blends: Pillow (C, no FMA on generic x86-64) and ATen round every product.
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
-
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
 
 template <class T>
 __device__ inline float ld_f32(const T* p, long i) { return to_f32(p[i]); }
@@ -154,49 +153,50 @@ __global__ __launch_bounds__(256) void frame_normalise_resize_kernel(const unsig
     }
 }
 
-inline unsigned grid1(long total) { return (unsigned)std::min<long>((total + 255) / 256, 8192); }
-
 }  // namespace
 
-int vf_launch_frame_to_u8(const void* x, unsigned char* out, int frames, int H, int W, int in_kind, hipStream_t stream) {
+extern "C" int vface_frame_to_u8(const void* x, uint8_t* out, int frames, int H, int W, int in_kind, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !out || frames <= 0 || H <= 0 || W <= 0) return VF_ERR_ARG;
     if ((long)H * W > 0x7fffffffL / 3) return VF_ERR_SHAPE;
-    const dim3 grid(grid1((long)H * W), frames);
+    const dim3 grid(vf_grid((long)H * W, 256, 8192), frames);
     if (in_kind == 2) hipLaunchKernelGGL(frame_to_u8_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, out, H * W);
     else if (in_kind == 0) hipLaunchKernelGGL((frame_to_u8_kernel<F16::elem>), grid, dim3(256), 0, stream, (const F16::elem*)x, out, H * W);
     else if (in_kind == 1) hipLaunchKernelGGL((frame_to_u8_kernel<BF16::elem>), grid, dim3(256), 0, stream, (const BF16::elem*)x, out, H * W);
     else if (in_kind == 3) hipLaunchKernelGGL((frame_to_u8_kernel<F16::elem, true>), grid, dim3(256), 0, stream, (const F16::elem*)x, out, H * W);
     else return VF_ERR_ARG;
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_resample_u8(const unsigned char* src, unsigned char* dst, int frames, int in_n, int out_n, int lines, int axis,
-                          const int* bounds, const int* kk, int ksize, hipStream_t stream) {
+extern "C" int vface_resample_u8(const uint8_t* src, uint8_t* dst, int frames, int in_n, int out_n, int lines, int axis,
+                                 const int32_t* bounds, const int32_t* kk, int ksize, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!src || !dst || !bounds || !kk || frames <= 0 || in_n <= 0 || out_n <= 0 || lines <= 0 || ksize <= 0) return VF_ERR_ARG;
     if (axis != 0 && axis != 1) return VF_ERR_ARG;
     const long fin = (long)in_n * lines * 3, fout = (long)out_n * lines * 3;
-    const dim3 grid(grid1(fout), frames);
+    const dim3 grid(vf_grid(fout, 256, 8192), frames);
     if (axis == 0) hipLaunchKernelGGL(resample_u8_kernel<0>, grid, dim3(256), 0, stream, src, dst, in_n, out_n, lines, bounds, kk, ksize, fin, fout);
     else hipLaunchKernelGGL(resample_u8_kernel<1>, grid, dim3(256), 0, stream, src, dst, in_n, out_n, lines, bounds, kk, ksize, fin, fout);
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_perspective_paste(const unsigned char* crop, int sw, int sh, unsigned char* frame, int W, int H, int frames,
-                                const double* coeffs_dev, const double* coeffs_host, hipStream_t stream) {
+extern "C" int vface_perspective_paste(const uint8_t* crop, int sw, int sh, uint8_t* frame, int W, int H, int frames,
+                                       const double* coeffs_dev, const double* coeffs_host, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!crop || !frame || frames <= 0 || sw <= 0 || sh <= 0 || W <= 0 || H <= 0) return VF_ERR_ARG;
     if (!coeffs_dev == !coeffs_host) return VF_ERR_ARG;          // exactly one source of the eight coefficients
     if (coeffs_host && frames != 1) return VF_ERR_ARG;           // host coefficients ride in the kernel arguments: one frame
     Persp cf{};
     if (coeffs_host) for (int j = 0; j < 8; ++j) cf.a[j] = coeffs_host[j];
-    hipLaunchKernelGGL(perspective_paste_kernel, dim3(grid1((long)W * H), frames), dim3(256), 0, stream, crop, sw, sh, frame, W, H, cf,
+    hipLaunchKernelGGL(perspective_paste_kernel, dim3(vf_grid((long)W * H, 256, 8192), frames), dim3(256), 0, stream, crop, sw, sh, frame, W, H, cf,
                        (long)sw * sh * 3, (long)W * H * 3, 8, coeffs_dev);
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_frame_normalise_resize(const unsigned char* frame, int W, int H, float* out, int OW, int OH, int frames,
-                                     hipStream_t stream) {
+extern "C" int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out, int OW, int OH, int frames, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!frame || !out || frames <= 0 || W <= 0 || H <= 0 || OW <= 0 || OH <= 0) return VF_ERR_ARG;
-    hipLaunchKernelGGL(frame_normalise_resize_kernel, dim3(grid1((long)OW * OH), frames), dim3(256), 0, stream, frame, W, H, out, OW, OH,
+    hipLaunchKernelGGL(frame_normalise_resize_kernel, dim3(vf_grid((long)OW * OH, 256, 8192), frames), dim3(256), 0, stream, frame, W, H, out, OW, OH,
                        (long)W * H * 3, (long)OW * OH * 3);
-    return ok();
+    return vf_launched();
 }

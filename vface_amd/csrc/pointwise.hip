@@ -1,6 +1,7 @@
 // Bandwidth-bound kernels of the VFace UNet path (gfx950): normalisations, the flow-guided warp of Q/K
 // maps, layout packing and the DDIM update.  All loads/stores of 16-bit data are 16 B per lane.
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -718,14 +719,6 @@ __global__ void copy2d_kernel(const typename TT::elem* __restrict__ src, long ld
     }
 }
 
-inline int grid_for(long total, int block = 256, int cap = 8192) {
-    long g = (total + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
-
 }  // namespace
 
 
@@ -806,13 +799,9 @@ __global__ void vae_sample_kernel(const float* __restrict__ moments, long ldm, c
     }
 }
 
-#define DISPATCH_DTYPE(dtype, CALL)            \
-    if ((dtype) == VF_DTYPE_F16) { using TT = F16; CALL; } \
-    else if ((dtype) == VF_DTYPE_BF16) { using TT = BF16; CALL; } \
-    else return VF_ERR_DTYPE;
-
-int vf_launch_layernorm(const void* x, long ldx, const float* gamma, const float* beta, void* y, long ldy, int M,
-                        int C, float eps, int in_f32, int dtype, hipStream_t stream) {
+extern "C" int vface_layernorm(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy, int M, int C,
+                               float eps, int in_f32, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !gamma || !beta || !y || M <= 0 || C <= 0) return VF_ERR_ARG;
     if ((C & 7) || (ldx & (in_f32 ? 3 : 7)) || (ldy & 7) || (((uintptr_t)x | (uintptr_t)y) & 15)) return VF_ERR_ALIGN;
     if (C > 2048) return VF_ERR_SHAPE;
@@ -830,7 +819,7 @@ int vf_launch_layernorm(const void* x, long ldx, const float* gamma, const float
         }
     });
 #undef LN_LAUNCH
-    return ok();
+    return vf_launched();
 }
 
 int vf_gn_partial_floats(int nimg, int hw, int C, int groups) {
@@ -838,8 +827,9 @@ int vf_gn_partial_floats(int nimg, int hw, int C, int groups) {
     return nimg * ((hw + GN_PIX - 1) / GN_PIX) * 2 * groups;
 }
 
-int vf_launch_gn_stats(const void* x, long ldx, int nimg, int hw, int C, int groups, float eps, float* partial,
-                       float* stats, int in_f32, int dtype, hipStream_t stream) {
+extern "C" int vface_groupnorm_stats(const void* x, int64_t ldx, int nimg, int hw, int C, int groups, float eps, float* partial,
+                                     float* stats, int in_f32, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !partial || !stats || nimg <= 0 || hw <= 0 || C <= 0 || groups <= 0) return VF_ERR_ARG;
     if ((C & 7) || (ldx & (in_f32 ? 3 : 7)) || ((uintptr_t)x & 15)) return VF_ERR_ALIGN;
     if (groups > 64 || C % groups) return VF_ERR_SHAPE;
@@ -851,19 +841,21 @@ int vf_launch_gn_stats(const void* x, long ldx, int nimg, int hw, int C, int gro
     });
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(nimg), dim3(64), 0, stream, (const float*)partial, nchunks, groups,
                        (double)hw * (C / groups), eps, stats);
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_gn_coeffs_cols(const float* colstats, long ld, int nimg, int hw, int C, int groups, float eps, const float* gamma,
-                             const float* beta, float* ab, hipStream_t stream) {
+extern "C" int vface_groupnorm_coeffs_from_cols(const float* colstats, int64_t ld, int nimg, int hw, int C, int groups, float eps,
+                                                const float* gamma, const float* beta, float* ab, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!colstats || !gamma || !beta || !ab || nimg <= 0 || hw <= 0 || C <= 0 || groups <= 0) return VF_ERR_ARG;
     if ((hw & 63) || groups > 64 || C % groups || (ld & 1)) return VF_ERR_SHAPE;
     hipLaunchKernelGGL(gn_coeffs_cols_kernel, dim3(groups, nimg), dim3(64), 0, stream, colstats, ld, hw, C, groups, eps, gamma, beta, ab);
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_gn_apply(const void* x, long ldx, const float* stats, const float* gamma, const float* beta, void* y,
-                       long ldy, int nimg, int hw, int C, int groups, int silu, int in_f32, int dtype, hipStream_t stream) {
+extern "C" int vface_groupnorm_apply(const void* x, int64_t ldx, const float* stats, const float* gamma, const float* beta, void* y,
+                                     int64_t ldy, int nimg, int hw, int C, int groups, int silu, int in_f32, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !stats || !gamma || !beta || !y || nimg <= 0 || hw <= 0) return VF_ERR_ARG;
     if ((C & 7) || (ldx & (in_f32 ? 3 : 7)) || (ldy & 7) || (((uintptr_t)x | (uintptr_t)y) & 15)) return VF_ERR_ALIGN;
     if (groups > 64 || C % groups) return VF_ERR_SHAPE;
@@ -882,13 +874,13 @@ int vf_launch_gn_apply(const void* x, long ldx, const float* stats, const float*
             else hipLaunchKernelGGL((gn_apply_kernel<TT, false, true>), grid, dim3(256), 0, stream, x, ldx, stats, gamma, beta, (E*)y, ldy, hw, C, groups, silu, ppb);
         }
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_flow_warp(const void* src, long ld_src, long fs_src, const void* prev, long ld_prev,
-                        const float* flow, const float* flow_prev, void* dst, long ld_dst, long fs_dst, int F, int h,
-                        int w, int C, float alpha, float one_minus_alpha, int flags, int* dbg_x0, int* dbg_y0,
-                        int dtype, hipStream_t stream) {
+extern "C" int vface_flow_warp(const void* src, int64_t ld_src, int64_t fs_src, const void* prev, int64_t ld_prev, const float* flow,
+                               const float* flow_prev, void* dst, int64_t ld_dst, int64_t fs_dst, int F, int h, int w, int C, float alpha,
+                               float one_minus_alpha, int flags, int32_t* dbg_x0, int32_t* dbg_y0, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!src || !dst || F <= 0 || h <= 0 || w <= 0 || C <= 0) return VF_ERR_ARG;
     if (F > 1 && !flow) return VF_ERR_ARG;
     if (prev && !flow_prev) return VF_ERR_ARG;
@@ -898,23 +890,24 @@ int vf_launch_flow_warp(const void* src, long ld_src, long fs_src, const void* p
     // one source frame is addressed through a buffer descriptor with 32-bit byte offsets
     if ((((long)h * w - 1) * (ld_src > ld_prev ? ld_src : ld_prev) + C) * 2 >= 0xFFFFFFF0l) return VF_ERR_SHAPE;
     const long total = (long)h * w * (C / 8);
-    dim3 grid(grid_for(total, 256, 2048), F);
+    dim3 grid(vf_grid(total, 256, 2048), F);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         hipLaunchKernelGGL((flow_warp_kernel<TT>), grid, dim3(256), 0, stream, (const E*)src, ld_src, fs_src,
                            (const E*)prev, ld_prev, flow, flow_prev, (E*)dst, ld_dst, fs_dst, F, h, w, C, alpha, one_minus_alpha, flags,
                            dbg_x0, dbg_y0);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_flow_to_latent(const float* flow_px, float* out, int pairs, int H, int W, int factor, hipStream_t stream) {
+extern "C" int vface_flow_to_latent(const float* flow_px, float* out, int pairs, int H, int W, int factor, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!flow_px || !out || pairs <= 0 || H <= 0 || W <= 0 || factor <= 0) return VF_ERR_ARG;
     if ((H % factor) || (W % factor)) return VF_ERR_SHAPE;
     const long total = (long)pairs * 2 * (H / factor) * (W / factor);
-    hipLaunchKernelGGL(flow_to_latent_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, stream, flow_px, out, (long)pairs * 2,
+    hipLaunchKernelGGL(flow_to_latent_kernel, dim3(vf_grid(total, 256, 4096)), dim3(256), 0, stream, flow_px, out, (long)pairs * 2,
                        H, W, factor);
-    return ok();
+    return vf_launched();
 }
 
 int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, int dtype, hipStream_t stream) {
@@ -924,20 +917,22 @@ int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, 
         using E = typename TT::elem;
         hipLaunchKernelGGL((timestep_embedding_kernel<TT>), dim3((total + 255) / 256), dim3(256), 0, stream, t, (E*)out, N, dim);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_silu(const void* x, void* y, long count, int in_f32, int dtype, hipStream_t stream) {
+extern "C" int vface_silu(const void* x, void* y, int64_t count, int in_f32, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !y || count <= 0) return VF_ERR_ARG;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        if (in_f32) hipLaunchKernelGGL((silu_kernel<TT, true>), dim3(grid_for(count)), dim3(256), 0, stream, x, (E*)y, count);
-        else hipLaunchKernelGGL((silu_kernel<TT, false>), dim3(grid_for(count)), dim3(256), 0, stream, x, (E*)y, count);
+        if (in_f32) hipLaunchKernelGGL((silu_kernel<TT, true>), dim3(vf_grid(count, 256, 8192)), dim3(256), 0, stream, x, (E*)y, count);
+        else hipLaunchKernelGGL((silu_kernel<TT, false>), dim3(vf_grid(count, 256, 8192)), dim3(256), 0, stream, x, (E*)y, count);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, int N, float scale, int dtype, hipStream_t stream) {
+extern "C" int vface_softmax_rows(const float* S, int64_t lds_, void* P, int64_t ldp, int M, int N, float scale, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!S || !P || M <= 0 || N <= 0) return VF_ERR_ARG;
     if ((N & 3) || (lds_ & 3) || (ldp & 3) || ((uintptr_t)S & 15) || ((uintptr_t)P & 7)) return VF_ERR_ALIGN;
     if (N > 16384) return VF_ERR_SHAPE;
@@ -945,107 +940,115 @@ int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, 
         using E = typename TT::elem;
         hipLaunchKernelGGL((softmax_rows_kernel<TT>), dim3(M), dim3(256), 0, stream, S, lds_, (E*)P, ldp, N, scale);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_vae_sample(const float* moments, long ldm, const float* noise, float* z, int F, int hw, int zc, float scale,
-                         hipStream_t stream) {
+extern "C" int vface_vae_sample(const float* moments, int64_t ldm, const float* noise, float* z, int F, int hw, int zc, float scale,
+                                void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!moments || !z || F <= 0 || hw <= 0 || zc <= 0 || ldm < 2 * zc) return VF_ERR_ARG;
-    hipLaunchKernelGGL(vae_sample_kernel, dim3(grid_for((long)F * hw * zc)), dim3(256), 0, stream, moments, ldm, noise, z, F, hw, zc, scale);
-    return ok();
+    hipLaunchKernelGGL(vae_sample_kernel, dim3(vf_grid((long)F * hw * zc, 256, 8192)), dim3(256), 0, stream, moments, ldm, noise, z, F, hw, zc, scale);
+    return vf_launched();
 }
 
-int vf_launch_cast(const float* src, void* dst, long count, int dtype, hipStream_t stream) {
+extern "C" int vface_cast_f32(const float* src, void* dst, int64_t count, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!src || !dst || count <= 0) return VF_ERR_ARG;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((cast_kernel<TT>), dim3(grid_for(count)), dim3(256), 0, stream, src, (E*)dst, count);
+        hipLaunchKernelGGL((cast_kernel<TT>), dim3(vf_grid(count, 256, 8192)), dim3(256), 0, stream, src, (E*)dst, count);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_pack_input(const float* x, const float* inv, const float* inpaint, const float* mask, void* out,
-                         int F, int h, int w, int cpad, int dtype, hipStream_t stream) {
+extern "C" int vface_pack_unet_input(const float* x, const float* inv, const float* inpaint, const float* mask, void* out, int F, int h,
+                                     int w, int cpad, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !inpaint || !mask || !out || F <= 0 || h <= 0 || w <= 0) return VF_ERR_ARG;
     if (cpad < 9 || (cpad & 7)) return VF_ERR_SHAPE;
     const long total = (long)(inv ? 3 : 2) * F * h * w * cpad;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((pack_input_kernel<TT>), dim3(grid_for(total)), dim3(256), 0, stream, x, inv, inpaint, mask, (E*)out, F, h * w, cpad);
+        hipLaunchKernelGGL((pack_input_kernel<TT>), dim3(vf_grid(total, 256, 8192)), dim3(256), 0, stream, x, inv, inpaint, mask, (E*)out, F, h * w, cpad);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_nchw_to_nhwc(const float* x, void* out, int N, int C, int hw, int cpad, int dtype, hipStream_t stream) {
+extern "C" int vface_nchw_to_nhwc(const float* x, void* out, int N, int C, int hw, int cpad, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !out || N <= 0 || C <= 0 || hw <= 0 || cpad < C) return VF_ERR_ARG;
     const long total = (long)N * hw * cpad;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((nchw_to_nhwc_kernel<TT>), dim3(grid_for(total)), dim3(256), 0, stream, x, (E*)out, N, C, hw, cpad);
+        hipLaunchKernelGGL((nchw_to_nhwc_kernel<TT>), dim3(vf_grid(total, 256, 8192)), dim3(256), 0, stream, x, (E*)out, N, C, hw, cpad);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_nhwc_to_nchw_f32(const float* x, long ldx, float* out, int N, int C, int hw, hipStream_t stream) {
+extern "C" int vface_nhwc_to_nchw_f32(const float* x, int64_t ldx, float* out, int N, int C, int hw, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !out || N <= 0 || C <= 0 || hw <= 0 || ldx < C) return VF_ERR_ARG;
     const long total = (long)N * C * hw;
-    hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(grid_for(total)), dim3(256), 0, stream, x, ldx, out, N, C, hw);
-    return ok();
+    hipLaunchKernelGGL(nhwc_to_nchw_f32_kernel, dim3(vf_grid(total, 256, 8192)), dim3(256), 0, stream, x, ldx, out, N, C, hw);
+    return vf_launched();
 }
 
-int vf_launch_ddim_step(const float* eps, long lde, const float* x, const float* inv, float* x_prev, float* pred_x0,
-                        float* x_prev_recon, int F, int C, int hw, float scale, float a_t, float a_prev, float sigma_t,
-                        float sqrt_1m_at, const float* noise, int single, hipStream_t stream) {
+extern "C" int vface_ddim_step(const float* eps, int64_t lde, const float* x, const float* inv, float* x_prev, float* pred_x0,
+                               float* x_prev_recon, int F, int C, int hw, float scale, float a_t, float a_prev, float sigma_t,
+                               float sqrt_1m_at, const float* noise, int single, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!eps || !x || !x_prev || F <= 0 || C <= 0 || hw <= 0 || lde < C || single < 0 || single > 2) return VF_ERR_ARG;
     const long total = (long)F * C * hw;
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_for(total)), dim3(256), 0, stream, eps, lde, x, inv, x_prev, pred_x0,
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(vf_grid(total, 256, 8192)), dim3(256), 0, stream, eps, lde, x, inv, x_prev, pred_x0,
                        x_prev_recon, F, C, hw, scale, a_t, a_prev, sigma_t, sqrt_1m_at, noise, single);
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_copy2d(const void* src, long lds_, void* dst, long ldd, long rows, int cols, int dtype,
-                     hipStream_t stream) {
+extern "C" int vface_copy2d(const void* src, int64_t lds_, void* dst, int64_t ldd, int64_t rows, int cols, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!src || !dst || rows <= 0 || cols <= 0) return VF_ERR_ARG;
     if ((cols & 7) || (lds_ & 7) || (ldd & 7) || (((uintptr_t)src | (uintptr_t)dst) & 15)) return VF_ERR_ALIGN;
     const long total = rows * (cols / 8);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((copy2d_kernel<TT>), dim3(grid_for(total)), dim3(256), 0, stream, (const E*)src, lds_, (E*)dst, ldd, rows, cols);
+        hipLaunchKernelGGL((copy2d_kernel<TT>), dim3(vf_grid(total, 256, 8192)), dim3(256), 0, stream, (const E*)src, lds_, (E*)dst, ldd, rows, cols);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_temporal_gauss(const void* src, long ld_src, long fs_src, void* dst1, void* dst2, long ld_dst, long fs_dst,
-                             int F, int n, int C, int dtype, hipStream_t stream) {
+extern "C" int vface_temporal_gauss(const void* src, int64_t ld_src, int64_t fs_src, void* dst1, void* dst2, int64_t ld_dst, int64_t fs_dst,
+                                    int F, int n, int C, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!src || !dst1 || F <= 0 || n <= 0 || C <= 0) return VF_ERR_ARG;      // (dst2 optional: a batch without its last chunk)
     if ((C & 7) || (ld_src & 7) || (ld_dst & 7) || (fs_src & 7) || (fs_dst & 7)) return VF_ERR_ALIGN;
     if (((uintptr_t)src | (uintptr_t)dst1 | (uintptr_t)dst2) & 15) return VF_ERR_ALIGN;
     const long total = (long)n * (C / 8);
-    dim3 grid(grid_for(total, 256, 2048), F);
+    dim3 grid(vf_grid(total, 256, 2048), F);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         hipLaunchKernelGGL((temporal_gauss_kernel<TT>), grid, dim3(256), 0, stream, (const E*)src, ld_src, fs_src, (E*)dst1,
                            (E*)dst2, ld_dst, fs_dst, F, n, C);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_temporal_gauss_halo(const void* src, long ld_src, long fs_src, const void* prev, const void* next, long ld_h,
-                                  long fs_h, void* dst1, void* dst2, long ld_dst, long fs_dst, int F, int first, int Ftot, int n,
-                                  int C, int dtype, hipStream_t stream) {
+extern "C" int vface_temporal_gauss_halo(const void* src, int64_t ld_src, int64_t fs_src, const void* prev, const void* next, int64_t ld_h,
+                                         int64_t fs_h, void* dst1, void* dst2, int64_t ld_dst, int64_t fs_dst, int F, int first, int Ftot,
+                                         int n, int C, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!src || !dst1 || F <= 0 || n <= 0 || C <= 0 || first < 0 || Ftot < first + F) return VF_ERR_ARG;
     if ((first > 0 && !prev) || (first + F < Ftot && !next)) return VF_ERR_ARG;   // a window frame with no slab to read
     if ((prev || next) && (ld_h < C || fs_h < (long)n * ld_h)) return VF_ERR_SHAPE;
     if ((C & 7) || (ld_src & 7) || (ld_dst & 7) || (fs_src & 7) || (fs_dst & 7) || (ld_h & 7) || (fs_h & 7)) return VF_ERR_ALIGN;
     if (((uintptr_t)src | (uintptr_t)dst1 | (uintptr_t)dst2 | (uintptr_t)prev | (uintptr_t)next) & 15) return VF_ERR_ALIGN;
     const long total = (long)n * (C / 8);
-    dim3 grid(grid_for(total, 256, 2048), F);
+    dim3 grid(vf_grid(total, 256, 2048), F);
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         hipLaunchKernelGGL((temporal_gauss_halo_kernel<TT>), grid, dim3(256), 0, stream, (const E*)src, ld_src, fs_src, (const E*)prev,
                            (const E*)next, ld_h, fs_h, (E*)dst1, (E*)dst2, ld_dst, fs_dst, F, first, Ftot, n, C);
     });
-    return ok();
+    return vf_launched();
 }
 
 size_t vf_adain_workspace_bytes(long rows, int C) {
@@ -1077,7 +1080,7 @@ int vf_launch_adain_rows(const void* a, long lda, const void* b, long ldb, long 
             default: hipLaunchKernelGGL((adain_rows_kernel<TT, 4>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
         }
     });
-    return ok();
+    return vf_launched();
 }
 
 int vf_launch_adain_reduce_scale(const double* partial, long partial_rows, int C, void* ws, void* dst, long ldd, long rows,
@@ -1091,10 +1094,10 @@ int vf_launch_adain_reduce_scale(const double* partial, long partial_rows, int C
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
         hipLaunchKernelGGL(adain_reduce_kernel, dim3(1), dim3(256), 0, stream, partial, (int)partial_rows, C, inv);
-        hipLaunchKernelGGL((adain_scale_kernel<TT>), dim3(grid_for(rows * (C / 8))), dim3(256), 0, stream, fused, (long)C,
+        hipLaunchKernelGGL((adain_scale_kernel<TT>), dim3(vf_grid(rows * (C / 8), 256, 8192)), dim3(256), 0, stream, fused, (long)C,
                            (const float*)inv, (E*)dst, ldd, rows, C);
     });
-    return ok();
+    return vf_launched();
 }
 
 int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst, long ldd, long rows, int C, void* ws,
@@ -1118,16 +1121,17 @@ int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst,
             default: hipLaunchKernelGGL((adain_rows_kernel<TT, 4>), g, dim3(256), 0, stream, (const E*)a, lda, (const E*)b, ldb, fused, (long)C, (int)rows, C, partial); break;
         }
         hipLaunchKernelGGL(adain_reduce_kernel, dim3(1), dim3(256), 0, stream, (const double*)partial, (int)rows, C, inv);
-        hipLaunchKernelGGL((adain_scale_kernel<TT>), dim3(grid_for(rows * (C / 8))), dim3(256), 0, stream, (const float*)fused, (long)C,
+        hipLaunchKernelGGL((adain_scale_kernel<TT>), dim3(vf_grid(rows * (C / 8), 256, 8192)), dim3(256), 0, stream, (const float*)fused, (long)C,
                            (const float*)inv, (E*)dst, ldd, rows, C);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_gn_finalize_cols(const float* colstats, long ld, int nimg, int hw, int C, int groups, float eps, float* stats,
-                               hipStream_t stream) {
+extern "C" int vface_groupnorm_finalize_cols(const float* colstats, int64_t ld, int nimg, int hw, int C, int groups, float eps,
+                                             float* stats, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!colstats || !stats || nimg <= 0 || hw <= 0 || C <= 0 || groups <= 0) return VF_ERR_ARG;
     if ((hw & 63) || (C % groups) || ld < C) return VF_ERR_SHAPE;
     hipLaunchKernelGGL(gn_finalize_cols_kernel, dim3(groups, nimg), dim3(64), 0, stream, colstats, ld, hw, C, groups, eps, stats);
-    return ok();
+    return vf_launched();
 }

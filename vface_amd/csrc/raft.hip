@@ -14,17 +14,10 @@
 // PARITY UNPINNED: torchvision is a third-party dependency that is neither under /root/reference nor installed here, and its
 // weights are not available offline; these kernels are tested against oracle/raft.py, a restatement of the published model.
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
-
-inline int ok() { return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH; }
-inline unsigned grid1(long total, int per = 256) { return (unsigned)std::min<long>((total + per - 1) / per, 16384); }
-
-#define DISPATCH_DTYPE(dtype, CALL)                                \
-    if ((dtype) == VF_DTYPE_F16) { using TT = F16; CALL; }         \
-    else if ((dtype) == VF_DTYPE_BF16) { using TT = BF16; CALL; }  \
-    else return VF_ERR_DTYPE;
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_SIGMOID = 3 };
 __device__ __forceinline__ float act_f(float v, int act) {
@@ -270,8 +263,9 @@ __global__ __launch_bounds__(256) void convex_upsample_kernel(const float* __res
 
 }  // namespace
 
-int vf_launch_im2col(const void* x, long ldx, int nimg, int H, int W, int C, int KH, int KW, int stride, int pad_y, int pad_x, void* out,
-                     long ldo, int dtype, hipStream_t stream) {
+extern "C" int vface_im2col(const void* x, int64_t ldx, int nimg, int H, int W, int C, int KH, int KW, int stride, int pad_y, int pad_x,
+                            void* out, int64_t ldo, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !out || nimg <= 0 || H <= 0 || W <= 0 || C <= 0 || KH <= 0 || KW <= 0 || stride <= 0) return VF_ERR_ARG;
     if ((C & 7) || (ldx & 7) || (ldo & 7) || (((uintptr_t)x | (uintptr_t)out) & 15)) return VF_ERR_ALIGN;
     const int OH = (H + 2 * pad_y - KH) / stride + 1, OW = (W + 2 * pad_x - KW) / stride + 1;
@@ -279,16 +273,17 @@ int vf_launch_im2col(const void* x, long ldx, int nimg, int H, int W, int C, int
     const long M = (long)nimg * OH * OW;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((im2col_kernel<TT>), dim3(grid1(M * KH * KW * (C / 8))), dim3(256), 0, stream, (const E*)x, ldx, H, W, C, KH, KW, stride,
+        hipLaunchKernelGGL((im2col_kernel<TT>), dim3(vf_grid(M * KH * KW * (C / 8), 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, H, W, C, KH, KW, stride,
                            pad_y, pad_x, OH, OW, (E*)out, ldo, M);
     });
-    return ok();
+    return vf_launched();
 }
 
 int vf_chan_stats_slices(int hw) { return hw >= 16384 ? 16 : (hw >= 2048 ? 4 : 1); }
 
-int vf_launch_chan_stats(const void* x, long ldx, int nimg, int hw, int C, float eps, float* partial, float* stats, int dtype,
-                         hipStream_t stream) {
+extern "C" int vface_channel_stats(const void* x, int64_t ldx, int nimg, int hw, int C, float eps, float* partial, float* stats, int dtype,
+                                   void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !partial || !stats || nimg <= 0 || hw <= 0 || C <= 0) return VF_ERR_ARG;
     if ((C & 7) || (ldx & 7) || ((uintptr_t)x & 15)) return VF_ERR_ALIGN;
     const int S = vf_chan_stats_slices(hw);
@@ -298,50 +293,55 @@ int vf_launch_chan_stats(const void* x, long ldx, int nimg, int hw, int C, float
         hipLaunchKernelGGL((chan_stats_finalize_kernel<TT>), dim3(((long)nimg * C + 255) / 256), dim3(256), 0, stream, (const E*)x, ldx, partial, nimg,
                            hw, C, S, eps, stats);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_chan_norm_act(const void* x, long ldx, const float* stats, const void* res, long ldr, void* y, long ldy, float* y32,
-                            long ldy32, long M, int hw, int C, int act, int dtype, hipStream_t stream) {
+extern "C" int vface_channel_norm_act(const void* x, int64_t ldx, const float* stats, const void* res, int64_t ldr, void* y, int64_t ldy,
+                                      float* y32, int64_t ldy32, int64_t M, int hw, int C, int act, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || (!y && !y32) || M <= 0 || hw <= 0 || C <= 0 || act < 0 || act > 3) return VF_ERR_ARG;
     if ((C & 7) || (ldx & 7) || (ldy & 7) || (ldr & 7) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15)) return VF_ERR_ALIGN;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((chan_norm_act_kernel<TT>), dim3(grid1(M * (C / 8))), dim3(256), 0, stream, (const E*)x, ldx, stats, (const E*)res, ldr,
+        hipLaunchKernelGGL((chan_norm_act_kernel<TT>), dim3(vf_grid(M * (C / 8), 256, 16384)), dim3(256), 0, stream, (const E*)x, ldx, stats, (const E*)res, ldr,
                            (E*)y, ldy, y32, ldy32, M, hw, C, act);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_gru_gate(const void* zr, long ldzr, const float* h32, void* z, long ldz, void* rh, long ldrh, long M, int Hd, int dtype,
-                       hipStream_t stream) {
+extern "C" int vface_gru_gate(const void* zr, int64_t ldzr, const float* h32, void* z, int64_t ldz, void* rh, int64_t ldrh, int64_t M,
+                              int Hd, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!zr || !h32 || !z || !rh || M <= 0 || Hd <= 0) return VF_ERR_ARG;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((gru_gate_kernel<TT>), dim3(grid1(M * Hd)), dim3(256), 0, stream, (const E*)zr, ldzr, h32, (E*)z, ldz, (E*)rh, ldrh, M, Hd);
+        hipLaunchKernelGGL((gru_gate_kernel<TT>), dim3(vf_grid(M * Hd, 256, 16384)), dim3(256), 0, stream, (const E*)zr, ldzr, h32, (E*)z, ldz, (E*)rh, ldrh, M, Hd);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_gru_update(const void* q, long ldq, const void* z, long ldz, float* h32, void* h16a, long lda, void* h16b, long ldb, long M,
-                         int Hd, int dtype, hipStream_t stream) {
+extern "C" int vface_gru_update(const void* q, int64_t ldq, const void* z, int64_t ldz, float* h32, void* h16a, int64_t lda, void* h16b,
+                                int64_t ldb, int64_t M, int Hd, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!q || !z || !h32 || M <= 0 || Hd <= 0) return VF_ERR_ARG;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((gru_update_kernel<TT>), dim3(grid1(M * Hd)), dim3(256), 0, stream, (const E*)q, ldq, (const E*)z, ldz, h32, (E*)h16a, lda,
+        hipLaunchKernelGGL((gru_update_kernel<TT>), dim3(vf_grid(M * Hd, 256, 16384)), dim3(256), 0, stream, (const E*)q, ldq, (const E*)z, ldz, h32, (E*)h16a, lda,
                            (E*)h16b, ldb, M, Hd);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_avgpool2_f32(const float* x, float* y, long R, int h, int w, hipStream_t stream) {
+extern "C" int vface_avgpool2_f32(const float* x, float* y, int64_t R, int h, int w, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!x || !y || R <= 0 || h < 2 || w < 2) return VF_ERR_ARG;
-    hipLaunchKernelGGL(avgpool2_f32_kernel, dim3(grid1(R * (h / 2) * (w / 2))), dim3(256), 0, stream, x, y, R, h, w);
-    return ok();
+    hipLaunchKernelGGL(avgpool2_f32_kernel, dim3(vf_grid(R * (h / 2) * (w / 2), 256, 16384)), dim3(256), 0, stream, x, y, R, h, w);
+    return vf_launched();
 }
 
-int vf_launch_corr_lookup(const float* const* vols, const int* hs, const int* ws, int levels, const float* flow32, int h, int w, float scale,
-                          void* out, long ldo, long M, int dtype, hipStream_t stream) {
+extern "C" int vface_corr_lookup(const float* const* vols, const int* hs, const int* ws, int levels, const float* flow32, int h, int w,
+                                 float scale, void* out, int64_t ldo, int64_t M, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!vols || !hs || !ws || !flow32 || !out || levels <= 0 || levels > 4 || M <= 0 || h <= 0 || w <= 0) return VF_ERR_ARG;
     if (ldo < levels * 81) return VF_ERR_SHAPE;
     CorrLevels lv{};
@@ -351,25 +351,27 @@ int vf_launch_corr_lookup(const float* const* vols, const int* hs, const int* ws
     }
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((corr_lookup_kernel<TT>), dim3(grid1(M * levels * 81)), dim3(256), 0, stream, lv, levels, flow32, h, w, scale, (E*)out, ldo, M);
+        hipLaunchKernelGGL((corr_lookup_kernel<TT>), dim3(vf_grid(M * levels * 81, 256, 16384)), dim3(256), 0, stream, lv, levels, flow32, h, w, scale, (E*)out, ldo, M);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_flow_update(float* flow32, const float* delta32, long ldd, void* a, long lda, void* b, long ldb, void* c, long ldc, long M,
-                          int dtype, hipStream_t stream) {
+extern "C" int vface_flow_update(float* flow32, const float* delta32, int64_t ldd, void* a, int64_t lda, void* b, int64_t ldb, void* c,
+                                 int64_t ldc, int64_t M, int dtype, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!flow32 || M <= 0) return VF_ERR_ARG;
     DISPATCH_DTYPE(dtype, {
         using E = typename TT::elem;
-        hipLaunchKernelGGL((flow_update_kernel<TT>), dim3(grid1(M)), dim3(256), 0, stream, flow32, delta32, ldd, (E*)a, lda, (E*)b, ldb, (E*)c, ldc, M);
+        hipLaunchKernelGGL((flow_update_kernel<TT>), dim3(vf_grid(M, 256, 16384)), dim3(256), 0, stream, flow32, delta32, ldd, (E*)a, lda, (E*)b, ldb, (E*)c, ldc, M);
     });
-    return ok();
+    return vf_launched();
 }
 
-int vf_launch_convex_upsample(const float* mask32, long ldm, const float* flow32, float* out, int B, int h, int w, float mult,
-                              hipStream_t stream) {
+extern "C" int vface_convex_upsample(const float* mask32, int64_t ldm, const float* flow32, float* out, int B, int h, int w, float mult,
+                                     void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
     if (!mask32 || !flow32 || !out || B <= 0 || h <= 0 || w <= 0) return VF_ERR_ARG;
     if (ldm < 576) return VF_ERR_SHAPE;
-    hipLaunchKernelGGL(convex_upsample_kernel, dim3(grid1((long)B * h * w * 64)), dim3(256), 0, stream, mask32, ldm, flow32, out, B, h, w, mult);
-    return ok();
+    hipLaunchKernelGGL(convex_upsample_kernel, dim3(vf_grid((long)B * h * w * 64, 256, 16384)), dim3(256), 0, stream, mask32, ldm, flow32, out, B, h, w, mult);
+    return vf_launched();
 }

@@ -25,6 +25,7 @@
 // Persistent: a workgroup walks token tiles (its own stage sequence never stops between them); tiles that need all columns and
 // tiles that need the tail only are served by disjoint sets of workgroups, sized by their work.
 #include "common.hpp"
+#include "launch.hpp"
 #include "vface_kernels.hpp"
 
 namespace {
@@ -382,7 +383,7 @@ int launch_c(const StFrontParams& p0, hipStream_t stream) {
     }
     p.gridA = gridA;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
-    return hipGetLastError() == hipSuccess ? VF_OK : VF_ERR_LAUNCH;
+    return vf_launched();
 }
 
 template <class TT>

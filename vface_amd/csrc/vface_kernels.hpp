@@ -1,4 +1,6 @@
-// Internal launch interface between the C ABI (capi.cpp / include/vface_hip.h) and the kernels.
+// What capi.cpp, or one kernel file of another, needs from the kernel files: the parameter structs and launchers of the entry
+// points that capi.cpp sequences, and the launchers gemm.hip's dispatch calls across files.  An entry point that only validates
+// and launches is defined beside its kernel as the extern "C" function itself and is not declared here (include/vface_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,106 +117,13 @@ struct AttnParams {
 };
 int vf_launch_attention(const AttnParams& p, int dtype, hipStream_t stream);
 
-// in_f32: x is the fp32 residual-stream copy (ldx in floats)
-int vf_launch_layernorm(const void* x, long ldx, const float* gamma, const float* beta, void* y, long ldy, int M,
-                        int C, float eps, int in_f32, int dtype, hipStream_t stream);
-int vf_launch_gn_finalize_cols(const float* colstats, long ld, int nimg, int hw, int C, int groups, float eps, float* stats,
-                               hipStream_t stream);
-int vf_launch_gn_coeffs_cols(const float* colstats, long ld, int nimg, int hw, int C, int groups, float eps, const float* gamma,
-                             const float* beta, float* ab, hipStream_t stream);
-int vf_launch_gn_stats(const void* x, long ldx, int nimg, int hw, int C, int groups, float eps, float* partial,
-                       float* stats, int in_f32, int dtype, hipStream_t stream);
+// pointwise.hip / raft.hip: what capi.cpp's size queries and workspace checks call
 int vf_gn_partial_floats(int nimg, int hw, int C, int groups);
-int vf_launch_gn_apply(const void* x, long ldx, const float* stats, const float* gamma, const float* beta, void* y,
-                       long ldy, int nimg, int hw, int C, int groups, int silu, int in_f32, int dtype, hipStream_t stream);
-int vf_launch_flow_warp(const void* src, long ld_src, long fs_src, const void* prev, long ld_prev,
-                        const float* flow, const float* flow_prev, void* dst, long ld_dst, long fs_dst, int F, int h,
-                        int w, int C, float alpha, float one_minus_alpha, int flags, int* dbg_x0, int* dbg_y0, int dtype,
-                        hipStream_t stream);
-int vf_launch_flow_to_latent(const float* flow_px, float* out, int pairs, int H, int W, int factor, hipStream_t stream);
-// raft.hip: glue kernels of the RAFT-shaped flow producer (temporal_flow.py:27-38, 163-188)
-int vf_launch_im2col(const void* x, long ldx, int nimg, int H, int W, int C, int KH, int KW, int stride, int pad_y, int pad_x, void* out,
-                     long ldo, int dtype, hipStream_t stream);
 int vf_chan_stats_slices(int hw);
-int vf_launch_chan_stats(const void* x, long ldx, int nimg, int hw, int C, float eps, float* partial, float* stats, int dtype,
-                         hipStream_t stream);
-int vf_launch_chan_norm_act(const void* x, long ldx, const float* stats, const void* res, long ldr, void* y, long ldy, float* y32,
-                            long ldy32, long M, int hw, int C, int act, int dtype, hipStream_t stream);
-int vf_launch_gru_gate(const void* zr, long ldzr, const float* h32, void* z, long ldz, void* rh, long ldrh, long M, int Hd, int dtype,
-                       hipStream_t stream);
-int vf_launch_gru_update(const void* q, long ldq, const void* z, long ldz, float* h32, void* h16a, long lda, void* h16b, long ldb, long M,
-                         int Hd, int dtype, hipStream_t stream);
-int vf_launch_avgpool2_f32(const float* x, float* y, long R, int h, int w, hipStream_t stream);
-int vf_launch_corr_lookup(const float* const* vols, const int* hs, const int* ws, int levels, const float* flow32, int h, int w, float scale,
-                          void* out, long ldo, long M, int dtype, hipStream_t stream);
-int vf_launch_flow_update(float* flow32, const float* delta32, long ldd, void* a, long lda, void* b, long ldb, void* c, long ldc, long M,
-                          int dtype, hipStream_t stream);
-int vf_launch_convex_upsample(const float* mask32, long ldm, const float* flow32, float* out, int B, int h, int w, float mult,
-                              hipStream_t stream);
-// paste.hip: per-frame paste-back (VFace_inference_batch.py:597-636); in_kind 0 fp16 | 1 bf16 | 2 fp32
-int vf_launch_frame_to_u8(const void* x, unsigned char* out, int frames, int H, int W, int in_kind, hipStream_t stream);
-int vf_launch_resample_u8(const unsigned char* src, unsigned char* dst, int frames, int in_n, int out_n, int lines, int axis,
-                          const int* bounds, const int* kk, int ksize, hipStream_t stream);
-int vf_launch_perspective_paste(const unsigned char* crop, int sw, int sh, unsigned char* frame, int W, int H, int frames,
-                                const double* coeffs_dev, const double* coeffs_host, hipStream_t stream);
-int vf_launch_frame_normalise_resize(const unsigned char* frame, int W, int H, float* out, int OW, int OH, int frames,
-                                     hipStream_t stream);
-// intake.hip: frame -> aligned crop -> sampler tensors (alignmengt.py:99-145, video_swap_dataset.py:135-240, VFace_inference_batch.py:459)
-int vf_launch_quad_crop(const unsigned char* frames, int Ws, int Hs, unsigned char* out, int S, int nframes, const double* quads,
-                        const int* windows, hipStream_t stream);
-int vf_launch_dataset_tensors(const unsigned char* crop, const unsigned char* label, const unsigned char* member, int W, int H,
-                              float* image, float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH,
-                              int nframes, hipStream_t stream);
-// parsing.hip: glue of the face-parsing network (pretrained/face_parsing/{face_parsing_demo,model,resnet}.py)
-int vf_launch_parse_prefilter(const unsigned char* crops, int W2, int H2, int factor, void* out, long ldo, int nframes, int dtype,
-                              hipStream_t stream);
-int vf_launch_maxpool3x3s2(const void* x, long ldx, int nimg, int H, int W, int C, void* y, long ldy, int dtype, hipStream_t stream);
-int vf_launch_channel_gate(const void* x, long ldx, const float* g, long ldg, const float* rvec, long ldrv, const void* rten, long ldr,
-                           int add_x, void* y, long ldy, long M, int hw, int C, int dtype, hipStream_t stream);
-int vf_launch_pooled_linear(const float* a, long lda, int sa, const float* W, const float* bias, float* out, long ldo, int nimg, int N,
-                            int K, int act, hipStream_t stream);
-int vf_launch_upsample_argmax_u8(const float* logits, long ld, int nframes, int h, int w, int ncls, const unsigned char* table,
-                                 unsigned char* out, int H, int W, hipStream_t stream);
-// clip.hip: glue of the CLIP image embedder and the conditioning mix (ldm/modules/encoders/modules.py:211-264, ddpm.py:872-1045)
-int vf_launch_clip_patches(const float* img, int H, int W, const float* mask, int prep, void* out, long ldo, int B, int G, int* dbg_x0,
-                           int* dbg_y0, int dtype, hipStream_t stream);
-int vf_launch_clip_embed(const void* tok, long ldt, int tok_f32, const float* cls, const float* pos, const float* gamma,
-                         const float* beta, float eps, float* x32, long ldo, int B, int P, int C, int dtype, hipStream_t stream);
-int vf_launch_act(const void* x, long ldx, void* y, long ldy, long rows, int cols, int kind, int dtype, hipStream_t stream);
-int vf_launch_cond_mix(const float* a, int rows_a, float wa, const float* b, int rows_b, float wb, const float* c, int rows_c, float wc,
-                       float wsum, float* out32, long ldo32, void* out16, long ldo16, int B, int N, int dtype, hipStream_t stream);
-// arcface.hip: glue of the identity network (ddpm.py:91-124, src/Face_models/encoders/{model_irse,helpers}.py)
-int vf_launch_id_prep(const float* img, int H, int W, const float* mask, int prep, int clip_img, void* out, long ldo, int B, int dtype,
-                      hipStream_t stream);
-int vf_launch_prelu(const void* x, long ldx, const float* slope, void* y, long ldy, const float* za, const float* zb, void* z, long ldz,
-                    long M, int C, int dtype, hipStream_t stream);
-int vf_launch_se_gate_add(const void* res, long ldr, const float* g, long ldg, const void* sc, long lds, int sc_stride, int nimg, int H,
-                          int W, int C, void* y, long ldy, const float* za, const float* zb, void* z, long ldz, int dtype,
-                          hipStream_t stream);
-int vf_launch_l2norm_rows(const float* x, long ldx, float* out, long ldo, int B, int N, hipStream_t stream);
 int vf_launch_timestep_embedding(const long long* t, void* out, int N, int dim, int dtype, hipStream_t stream);
-int vf_launch_silu(const void* x, void* y, long count, int in_f32, int dtype, hipStream_t stream);
-int vf_launch_softmax_rows(const float* S, long lds_, void* P, long ldp, int M, int N, float scale, int dtype, hipStream_t stream);
-int vf_launch_vae_sample(const float* moments, long ldm, const float* noise, float* z, int F, int hw, int zc, float scale,
-                         hipStream_t stream);
-int vf_launch_pack_input(const float* x, const float* inv, const float* inpaint, const float* mask, void* out,
-                         int F, int h, int w, int cpad, int dtype, hipStream_t stream);
-int vf_launch_nchw_to_nhwc(const float* x, void* out, int N, int C, int hw, int cpad, int dtype, hipStream_t stream);
-int vf_launch_nhwc_to_nchw_f32(const float* x, long ldx, float* out, int N, int C, int hw, hipStream_t stream);
-int vf_launch_ddim_step(const float* eps, long lde, const float* x, const float* inv, float* x_prev, float* pred_x0,
-                        float* x_prev_recon, int F, int C, int hw, float scale, float a_t, float a_prev, float sigma_t,
-                        float sqrt_1m_at, const float* noise, int single, hipStream_t stream);
-int vf_launch_copy2d(const void* src, long lds, void* dst, long ldd, long rows, int cols, int dtype,
-                     hipStream_t stream);
-int vf_launch_cast(const float* src, void* dst, long count, int dtype, hipStream_t stream);
-int vf_launch_temporal_gauss(const void* src, long ld_src, long fs_src, void* dst1, void* dst2, long ld_dst, long fs_dst,
-                             int F, int n, int C, int dtype, hipStream_t stream);
 size_t vf_adain_workspace_bytes(long rows, int C);
 int vf_launch_adain(const void* a, long lda, const void* b, long ldb, void* dst, long ldd, long rows, int C, void* ws,
                     int dtype, hipStream_t stream);
-int vf_launch_temporal_gauss_halo(const void* src, long ld_src, long fs_src, const void* prev, const void* next, long ld_h,
-                                  long fs_h, void* dst1, void* dst2, long ld_dst, long fs_dst, int F, int first, int Ftot, int n,
-                                  int C, int dtype, hipStream_t stream);
 size_t vf_adain_rows_workspace_bytes(long rows, int C);
 int vf_launch_adain_rows(const void* a, long lda, const void* b, long ldb, long rows, int C, double* partial, void* ws,
                          int dtype, hipStream_t stream);
