@@ -65,45 +65,67 @@ def attn_block(sd, pre, x):
     return x + _conv(sd, pre + ".proj_out", o, padding=0)
 
 
-def encoder(sd, spec: VAESpec, x, pre="encoder"):
-    """model.py:434-459."""
-    h = _conv(sd, pre + ".conv_in", x)
+def _tap(taps, name, h):
+    if taps is not None:
+        taps[name] = h
+    return h
+
+
+def downsample(sd, pre, x):
+    """model.py:72-77: asymmetric (trailing) zero padding, then stride 2."""
+    return _conv(sd, pre + ".conv", F.pad(x, (0, 1, 0, 1)), stride=2, padding=0)
+
+
+def upsample(sd, pre, x):
+    """model.py:55-58: nearest x2, then the 3x3 convolution."""
+    return _conv(sd, pre + ".conv", F.interpolate(x, scale_factor=2.0, mode="nearest"))
+
+
+def norm_out_conv(sd, pre, x):
+    """``conv_out(nonlinearity(norm_out(h)))``, the tail of both networks (model.py:455-458, :562-565)."""
+    return _conv(sd, pre + ".conv_out", _gn_swish(sd, pre + ".norm_out", x))
+
+
+def encoder(sd, spec: VAESpec, x, pre="encoder", taps=None):
+    """model.py:434-459.  ``taps`` (a dict, optional) receives the output of every stage under the names of
+    tests/golden/cases_vae.py::enc_stages."""
+    h = _tap(taps, "enc.conv_in", _conv(sd, pre + ".conv_in", x))
     nres = len(spec.ch_mult)
     for lvl in range(nres):
         for blk in range(spec.num_res_blocks):
             h = resnet_block(sd, f"{pre}.down.{lvl}.block.{blk}", h)
             if f"{pre}.down.{lvl}.attn.{blk}.q.weight" in sd:
                 h = attn_block(sd, f"{pre}.down.{lvl}.attn.{blk}", h)
+            _tap(taps, f"enc.down.{lvl}.{blk}", h)
         if lvl != nres - 1:
-            h = F.pad(h, (0, 1, 0, 1))                                     # :72-77 asymmetric padding, then stride 2
-            h = _conv(sd, f"{pre}.down.{lvl}.downsample.conv", h, stride=2, padding=0)
-    h = resnet_block(sd, pre + ".mid.block_1", h)
-    h = attn_block(sd, pre + ".mid.attn_1", h)
-    h = resnet_block(sd, pre + ".mid.block_2", h)
-    return _conv(sd, pre + ".conv_out", _gn_swish(sd, pre + ".norm_out", h))
+            h = _tap(taps, f"enc.down.{lvl}.ds", downsample(sd, f"{pre}.down.{lvl}.downsample", h))
+    h = _tap(taps, "enc.mid1", resnet_block(sd, pre + ".mid.block_1", h))
+    h = _tap(taps, "enc.attn", attn_block(sd, pre + ".mid.attn_1", h))
+    h = _tap(taps, "enc.mid2", resnet_block(sd, pre + ".mid.block_2", h))
+    return norm_out_conv(sd, pre, h)
 
 
-def decoder(sd, spec: VAESpec, z, pre="decoder"):
-    """model.py:534-568."""
-    h = _conv(sd, pre + ".conv_in", z)
-    h = resnet_block(sd, pre + ".mid.block_1", h)
-    h = attn_block(sd, pre + ".mid.attn_1", h)
-    h = resnet_block(sd, pre + ".mid.block_2", h)
+def decoder(sd, spec: VAESpec, z, pre="decoder", taps=None):
+    """model.py:534-568.  ``taps``: as in ``encoder`` (cases_vae.py::dec_stages)."""
+    h = _tap(taps, "dec.conv_in", _conv(sd, pre + ".conv_in", z))
+    h = _tap(taps, "dec.mid1", resnet_block(sd, pre + ".mid.block_1", h))
+    h = _tap(taps, "dec.attn", attn_block(sd, pre + ".mid.attn_1", h))
+    h = _tap(taps, "dec.mid2", resnet_block(sd, pre + ".mid.block_2", h))
     nres = len(spec.ch_mult)
     for lvl in reversed(range(nres)):
         for blk in range(spec.num_res_blocks + 1):
             h = resnet_block(sd, f"{pre}.up.{lvl}.block.{blk}", h)
             if f"{pre}.up.{lvl}.attn.{blk}.q.weight" in sd:
                 h = attn_block(sd, f"{pre}.up.{lvl}.attn.{blk}", h)
+            _tap(taps, f"dec.up.{lvl}.{blk}", h)
         if lvl != 0:
-            h = F.interpolate(h, scale_factor=2.0, mode="nearest")         # :55-58
-            h = _conv(sd, f"{pre}.up.{lvl}.upsample.conv", h)
-    return _conv(sd, pre + ".conv_out", _gn_swish(sd, pre + ".norm_out", h))
+            h = _tap(taps, f"dec.up.{lvl}.us", upsample(sd, f"{pre}.up.{lvl}.upsample", h))
+    return norm_out_conv(sd, pre, h)
 
 
-def encode_moments(sd, spec: VAESpec, x):
+def encode_moments(sd, spec: VAESpec, x, taps=None):
     """AutoencoderKL.encode up to the Gaussian's parameters (autoencoder.py:323-327): [B, 2*embed_dim, h, w]."""
-    return _conv(sd, "quant_conv", encoder(sd, spec, x), padding=0)
+    return _conv(sd, "quant_conv", encoder(sd, spec, x, taps=taps), padding=0)
 
 
 def sample(moments, noise=None, scale_factor=1.0):
@@ -115,9 +137,9 @@ def sample(moments, noise=None, scale_factor=1.0):
     return (mean + torch.exp(0.5 * logvar) * noise) * scale_factor
 
 
-def decode(sd, spec: VAESpec, z):
+def decode(sd, spec: VAESpec, z, taps=None):
     """AutoencoderKL.decode (autoencoder.py:329-333)."""
-    return decoder(sd, spec, _conv(sd, "post_quant_conv", z, padding=0))
+    return decoder(sd, spec, _conv(sd, "post_quant_conv", z, padding=0), taps=taps)
 
 
 def param_shapes(spec: VAESpec) -> Dict[str, Sequence[int]]:

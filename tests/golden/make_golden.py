@@ -548,6 +548,103 @@ def gen_vae():
     save("vae_lowp", **lowp)
 
 
+def gen_vae_stages():
+    """vae_stages.npz: the first stage past 64 mid-attention tokens and at H != W (cases, inputs and the kept elements:
+    tests/golden/cases_vae.py), wrapped as gen_vae wraps the reference's Encoder / Decoder.
+      ragged  the ``small`` configuration, two frames of 80 x 96 (latent 10 x 12, n = 120): the fp64 run's output after every stage
+              VAEEngine sequences (forward hooks on the reference's own sub-modules; K_STAGE seeded elements each, stored as fp32),
+              its final outputs (moments / z_mode / z_sample whole, ``dec`` at K_DEC seeded elements, fp64), the fp32 run's final
+              outputs, the reference under torch.autocast fp16 and bf16, and in fp32 arithmetic with fp16-rounded weights;
+      wide    the shipped configuration, one frame of 192 x 256 (latent 24 x 32, n = 768): final outputs only, fp64, fp32 and the
+              two autocast runs (seconds each on the CPU, so both are recorded).
+    Every decoder run decodes the SAME latent, the fp64 run's z_sample rounded to fp32, over the scale factor.  Autocast ``dec`` is
+    kept in its own 16-bit type (bf16 as its bit pattern, ``*_bits``: numpy has no such type); the latent-sized autocast outputs
+    pass through the fp32 DiagonalGaussianDistribution as in gen_vae and are fp32."""
+    from ldm.modules.diffusionmodules.model import Decoder, Encoder
+    from ldm.modules.distributions.distributions import DiagonalGaussianDistribution
+    import builtins
+    import cases_vae as cv
+
+    def kl(dd):
+        class KL(torch.nn.Module):
+            def __init__(self):
+                super().__init__()
+                pr, builtins.print = builtins.print, (lambda *a, **k: None)   # the constructors print
+                self.encoder, self.decoder = Encoder(**dd), Decoder(**dd)
+                builtins.print = pr
+                self.quant_conv = torch.nn.Conv2d(2 * dd["z_channels"], 2 * 4, 1)
+                self.post_quant_conv = torch.nn.Conv2d(4, dd["z_channels"], 1)
+        return synth.fill_module_(KL().eval(), seed=0, prefix="vae.")
+
+    def hook(m, taps):
+        def rec(name):
+            return lambda mod, inp, out: taps.__setitem__(name, out.detach())
+        hs = []
+        for side, net in (("enc", m.encoder), ("dec", m.decoder)):
+            hs += [net.conv_in.register_forward_hook(rec(f"{side}.conv_in")), net.mid.block_1.register_forward_hook(rec(f"{side}.mid1")),
+                   net.mid.attn_1.register_forward_hook(rec(f"{side}.attn")), net.mid.block_2.register_forward_hook(rec(f"{side}.mid2"))]
+            levels, key = (net.down, "down") if side == "enc" else (net.up, "up")
+            for lvl, L in enumerate(levels):
+                hs += [blk.register_forward_hook(rec(f"{side}.{key}.{lvl}.{b}")) for b, blk in enumerate(L.block)]
+                if hasattr(L, "downsample"):
+                    hs.append(L.downsample.register_forward_hook(rec(f"enc.down.{lvl}.ds")))
+                if hasattr(L, "upsample"):
+                    hs.append(L.upsample.register_forward_hook(rec(f"dec.up.{lvl}.us")))
+        return hs
+
+    out = {}
+    for case, c in cv.CASES.items():
+        dd = cv.DD[c["cfg"]]
+        x, noise = cv.inputs(case)
+        t0 = time.time()
+
+        def run(m, f64=False):
+            mo = m.quant_conv(m.encoder(x.double())) if f64 else m.quant_conv(m.encoder(x)).float()
+            po = DiagonalGaussianDistribution(mo)
+            return mo, po.mode() * cv.SCALE, (po.mean + po.std * (noise.double() if f64 else noise)) * cv.SCALE
+
+        with torch.no_grad():
+            m64, taps = kl(dd).double(), {}
+            hs = hook(m64, taps) if case == "ragged" else []
+            mo, zm, zs = run(m64, True)
+            zdec = zs.float() / cv.SCALE                                      # what every run decodes
+            dec = m64.decoder(m64.post_quant_conv(zdec.double()))
+            for h in hs:
+                h.remove()
+            if case == "ragged":
+                assert sorted(taps) == sorted(cv.enc_stages() + cv.dec_stages()), sorted(taps)
+                for k, v in taps.items():
+                    out[f"{case}.{k}"] = cv.take(case, k, v).float()
+                    out[f"{case}.{k}.shape"] = np.array(v.shape)
+            out[f"{case}.moments"], out[f"{case}.z_mode"], out[f"{case}.z_sample"] = mo, zm, zs
+            out[f"{case}.dec"] = cv.take(case, "dec", dec, cv.K_DEC)
+            m = kl(dd)
+            mo, zm, zs = run(m)
+            out[f"{case}.moments_f32"], out[f"{case}.z_mode_f32"], out[f"{case}.z_sample_f32"] = mo, zm, zs
+            out[f"{case}.dec_f32"] = cv.take(case, "dec", m.decoder(m.post_quant_conv(zdec)), cv.K_DEC)
+            for tag, dt in (("f16", torch.float16), ("bf16", torch.bfloat16)):
+                if tag not in cv.AUTOCAST[case]:
+                    continue
+                with torch.autocast("cpu", dtype=dt):
+                    _, zm, zs = run(m)
+                    d16 = m.decoder(m.post_quant_conv(zdec))
+                assert d16.dtype == dt
+                out[f"{case}.z_mode_autocast_{tag}"], out[f"{case}.z_sample_autocast_{tag}"] = zm, zs
+                d16 = cv.take(case, "dec", d16, cv.K_DEC)
+                if dt == torch.float16:
+                    out[f"{case}.dec_autocast_f16"] = d16
+                else:
+                    out[f"{case}.dec_autocast_bf16_bits"] = d16.view(torch.int16).numpy().view(np.uint16)
+                sys.stdout.write(f"  {case} autocast {tag}: {time.time() - t0:.0f} s so far\n")
+            if case == "ragged":
+                _round_weights_(m)
+                _, zm, zs = run(m)
+                out[f"{case}.z_mode_w16"], out[f"{case}.z_sample_w16"] = zm, zs
+                out[f"{case}.dec_w16"] = cv.take(case, "dec", m.decoder(m.post_quant_conv(zdec)), cv.K_DEC)
+        out[f"{case}.n_params"] = float(sum(p.numel() for p in m.parameters()))
+    save("vae_stages", **out)
+
+
 def gen_paste():
     """Paste-back (VFace_inference_batch.py:597-636): what PILLOW (the reference's own dependency, 12.2.0 in this image) returns
     for that block's calls on seeded inputs -- `Image.resize(.., BILINEAR)` up / down / one axis, and `putalpha(255)` +
@@ -590,7 +687,7 @@ if __name__ == "__main__":
     import builtins
     _print = builtins.print
     gens = {"fsai": gen_fsai, "warp": gen_warp, "warp_cuda": gen_warp_cuda_form, "attn": gen_attn_module, "tiny": gen_tiny_unet, "tiny_f5": gen_tiny_unet_f5, "ddim": gen_ddim,
-            "vae": gen_vae, "paste": gen_paste}
+            "vae": gen_vae, "vae_stages": gen_vae_stages, "paste": gen_paste}
     gens["lowp"] = lambda: gen_lowp(a.full)
     if a.full:
         gens["full"] = gen_full_unet

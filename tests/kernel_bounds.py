@@ -189,8 +189,22 @@ def attention_ref_and_bound(q, k, v, scale, dt, chunk_bytes=4.0e8):
     return torch.cat(o_all), torch.cat(b_all)
 
 
+def softmax_rows_ref_and_bound(S, scale, dt):
+    """``vface_softmax_rows``: P = softmax(S scale) over the columns of the fp32 ``S [M, N]`` in fp64, and its per-element bound
+    (test_glue_kernels_gpu.py::test_softmax_rows, test_vae_stages_gpu.py).  Relative to p: the exponent of 2 is fma(s, c, -max c)
+    with c = fl(scale log2 e): c is off by 2 u relative and each of the two terms rounds once, so the argument is off by 4 u A,
+    A = max|s| scale log2 e, for numerator and denominator alike: 8 ln2 u A; the row sum is 16 + 8 + 3 fp32 sums, the reciprocal and
+    the product 2 more; E = ``cpu_fp32_rel_error`` of torch's fp32 softmax on these rows for the exp2.  Then 0.5 ulp of the type,
+    and 2^-126 for a flushed intermediate."""
+    lg = S.double() * scale
+    ref = torch.softmax(lg, 1)
+    E = cpu_fp32_rel_error(torch.softmax, S * scale, dim=1)
+    A = lg.abs().amax(1, keepdim=True) * 1.4426950408889634
+    return ref, (E + (8 * math.log(2) * A + 29) * U32) * ref + 0.5 * ulp(ref, dt) + TINY32
+
+
 # ------------------------------------------------------------------------------------------------ GEMM and convolution
-ACC_ULPS = 1.0            # fp32 roundings allowed per accumulated product, in units of U32 (see gemm_ref_and_bound)
+ACC_ULPS = 1.0           # fp32 roundings allowed per accumulated product, in units of U32 (see gemm_ref_and_bound)
 GELU_AS_ABS = 7.5e-8      # |error| of Phi from Abramowitz & Stegun 7.1.26 (csrc/common.hpp, gelu_erf_f)
 
 

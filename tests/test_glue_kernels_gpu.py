@@ -17,7 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from kernel_bounds import TINY32, U32, assert_within, cpu_fp32_rel_error, rnd, same_bits, sentinel, ulp
+from kernel_bounds import TINY32, U32, assert_within, cpu_fp32_rel_error, rnd, same_bits, sentinel, softmax_rows_ref_and_bound, ulp
 
 pytestmark = pytest.mark.gpu
 
@@ -684,11 +684,7 @@ def test_softmax_rows(dt, M, N):
     od = oh.to(DEV)
     h.softmax_rows(S.to(DEV), od, M=M, N=N, scale=scale, ld_s=N + 4, ld_p=N + 4)
     got = od.cpu()
-    lg = S[:, :N] * scale                                   # exact: a power of two
-    ref = torch.softmax(lg.double(), 1)
-    E = cpu_fp32_rel_error(torch.softmax, lg, dim=1)
-    A = lg.abs().amax(1, keepdim=True).double() * 1.4426950408889634
-    bound = (E + (8 * math.log(2) * A + 29) * U32) * ref + 0.5 * ulp(ref, dt) + TINY32
+    ref, bound = softmax_rows_ref_and_bound(S[:, :N], scale, dt)      # (S scale is exact: a power of two)
     assert_within(got[:M, :N], ref, bound, f"softmax N={N}")
     assert float(got[0, N // 3]) == 1.0 and int((got[0, :N] != 0).sum()) == 1, "one dominant logit takes all the mass"
     sums = got[:M, :N].double().sum(1)

@@ -371,6 +371,36 @@ def test_vae_encode_sample_decode_match_reference(tag, res, nb):
         assert rel_l2(dec, g[f"{tag}.dec"]) < 1e-5
 
 
+@pytest.mark.parametrize("case", ["ragged", "wide"])
+def test_vae_stages_match_reference_past_64_tokens(case):
+    """tests/golden/vae_stages.npz (cases_vae.py): the mid attention at n = 120 (10 x 12) and n = 768 (24 x 32), H != W, two frames.
+    The oracle is held at EVERY recorded intermediate of ``ragged`` (the fp64 run's values, on the fixture's elements) and at the
+    final outputs of both cases, to the tolerance of the test above; the fixture's own fp32 run sits inside the same tolerance."""
+    import os, sys
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+    import cases_vae as cv
+    g = load_golden("vae_stages")
+    spec = VAE_SPECS[cv.CASES[case]["cfg"]]
+    sd = vae_state_dict(spec)
+    assert sum(int(np.prod(v.shape)) for v in sd.values()) == int(g[f"{case}.n_params"])
+    x, noise = cv.inputs(case)
+    taps = {}
+    with torch.no_grad():
+        moments = ovae.encode_moments(sd, spec, x, taps=taps)
+        z = ovae.sample(moments, noise, cv.SCALE)
+        dec = ovae.decode(sd, spec, g[f"{case}.z_sample"].float() / cv.SCALE, taps=taps)
+    assert rel_l2(moments, g[f"{case}.moments"]) < 1e-5 and rel_l2(g[f"{case}.moments_f32"], g[f"{case}.moments"]) < 1e-5
+    assert rel_l2(ovae.sample(moments, None, cv.SCALE), g[f"{case}.z_mode"]) < 1e-5
+    assert rel_l2(z, g[f"{case}.z_sample"]) < 1e-5
+    assert rel_l2(cv.take(case, "dec", dec, cv.K_DEC), g[f"{case}.dec"]) < 1e-5
+    assert rel_l2(g[f"{case}.dec_f32"], g[f"{case}.dec"]) < 1e-5
+    if case == "ragged":
+        assert sorted(taps) == sorted(cv.enc_stages() + cv.dec_stages())
+        for k, v in taps.items():
+            assert tuple(v.shape) == tuple(int(s) for s in g[f"ragged.{k}.shape"]), k
+            assert rel_l2(cv.take(case, k, v), g[f"ragged.{k}"]) < 1e-5, k
+
+
 def test_cuda_form_indices_fixture_and_flow_to_latent():
     """Round-2 additions: the oracle's CUDA-form division rule reproduces the committed (emulated) index fixture and differs
     from the CPU form exactly where floor() sits on an integer; the latent flow resample is the area mean / factor."""

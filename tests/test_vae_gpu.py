@@ -1,5 +1,7 @@
 """First-stage KL-VAE on the GPU: the HIP path against the fixture the reference's own Encoder / Decoder
-produced (tests/golden/vae.npz), against the oracle, and size-independent properties at 512x512."""
+produced (tests/golden/vae.npz), against the oracle, and size-independent properties at 512x512.  The engine stage by stage, the
+mid attention past 64 tokens, H != W and the up-front size check: test_vae_stages_gpu.py.  ``test_softmax_rows_kernel`` and
+``test_trailing_pad_stride2_conv`` hold every element against fp64 in both types (bounds: kernel_bounds.py), at their earlier shapes."""
 import numpy as np
 import pytest
 import torch
@@ -72,31 +74,46 @@ def test_vae_cpu_tensors_fail_loudly():
 
 
 def test_softmax_rows_kernel():
+    """7 x 16, 64 x 4096, 3 x 9216 (scale 0.37, scores N(0, 9)): per element against fp64 in fp16 and bf16, row sums within the summed
+    bounds; the earlier rel-L2 < 1e-3 in fp16 stays."""
+    from kernel_bounds import assert_within, softmax_rows_ref_and_bound
     from vface_amd import hip
-    for (M, N) in [(7, 16), (64, 4096), (3, 9216)]:
-        s = synth.synth_normal(f"sm.{M}.{N}", (M, N)) * 3
-        out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-        hip.softmax_rows(s.to(DEV), out, M=M, N=N, scale=0.37)
-        ref = torch.softmax(s * 0.37, -1)
-        assert rel_l2(out.float().cpu(), ref) < 1e-3
-        assert torch.allclose(out.float().sum(-1).cpu(), torch.ones(M), atol=2e-3)
+    for dt in (torch.float16, torch.bfloat16):
+        for (M, N) in [(7, 16), (64, 4096), (3, 9216)]:
+            s = synth.synth_normal(f"sm.{M}.{N}", (M, N)) * 3
+            out = torch.empty(M, N, dtype=dt, device=DEV)
+            hip.softmax_rows(s.to(DEV), out, M=M, N=N, scale=0.37)
+            ref, bound = softmax_rows_ref_and_bound(s, 0.37, dt)
+            got = out.cpu()
+            assert_within(got, ref, bound, f"softmax {dt} {M}x{N}")
+            assert bool(((got.double().sum(1) - 1.0).abs() <= bound.sum(1)).all())
+            if dt == torch.float16:
+                assert rel_l2(got.float(), ref) < 1e-3
+                assert torch.allclose(got.float().sum(-1), torch.ones(M), atol=2e-3)
 
 
 def test_trailing_pad_stride2_conv():
-    """Downsample (model.py:72-77): F.pad(0,1,0,1) + stride-2 padding-0 conv."""
+    """Downsample (model.py:72-77): F.pad(0,1,0,1) + stride-2 padding-0 conv, through the kernels the default rule picks: per
+    element against fp64 in fp16 and bf16 inside a sentinel frame; the earlier rel-L2 < 1e-3 in fp16 stays."""
     import math
-    import torch.nn.functional as F
+    from kernel_bounds import Framed, assert_within, conv_ref_and_bound
     from vface_amd import hip
     from vface_amd.packing import pack_conv3x3
-    for cin, cout, H in [(64, 64, 16), (128, 128, 32), (24, 32, 10)]:
-        x = synth.synth_normal(f"ds.x.{cin}", (2, cin, H, H)).half()
-        w = (synth.synth_normal(f"ds.w.{cin}", (cout, cin, 3, 3)) / math.sqrt(9 * cin)).half()
-        b = synth.synth_normal(f"ds.b.{cin}", (cout,))
-        ref = F.conv2d(F.pad(x.float(), (0, 1, 0, 1)), w.float(), b, stride=2, padding=0)
-        out = torch.empty(2, H // 2, H // 2, cout, dtype=torch.float16, device=DEV)
-        hip.conv3x3(x.permute(0, 2, 3, 1).contiguous().to(DEV), pack_conv3x3(w).to(DEV), out, nimg=2, H=H, W=H, cin=cin,
-                    cout=cout, ldx=cin, ldy=cout, stride=2, bias=b.to(DEV), flags=hip.CONV_PAD_TRAILING)
-        assert rel_l2(out.float().cpu().permute(0, 3, 1, 2), ref) < 1e-3
+    for dt in (torch.float16, torch.bfloat16):
+        for cin, cout, H in [(64, 64, 16), (128, 128, 32), (24, 32, 10)]:
+            x = synth.synth_normal(f"ds.x.{cin}", (2, cin, H, H)).to(dt)
+            w = (synth.synth_normal(f"ds.w.{cin}", (cout, cin, 3, 3)) / math.sqrt(9 * cin)).to(dt)
+            b = synth.synth_normal(f"ds.b.{cin}", (cout,))
+            M, rps = 2 * (H // 2) ** 2, (H // 2) ** 2
+            out = Framed(M, cout, dt)
+            hip.conv3x3(x.permute(0, 2, 3, 1).contiguous().to(DEV), pack_conv3x3(w.float()).to(dt).to(DEV), out.view, nimg=2, H=H, W=H,
+                        cin=cin, cout=cout, ldx=cin, ldy=out.ld, stride=2, bias=b.to(DEV), flags=hip.CONV_PAD_TRAILING)
+            splits = max(1, hip.load().vface_splitk_workspace_bytes(M, cout, 9 * cin, hip.CONV_PAD_TRAILING, rps) // (M * cout * 4))
+            ref, bound = conv_ref_and_bound(x, w, dt, stride=2, pad=(0, 1, 0, 1), bias=b, splits=splits)
+            got = out.result(f"trailing conv {cin}")
+            assert_within(got, ref, bound, f"trailing-pad stride-2 conv {dt} {cin}->{cout} {H}x{H}")
+            if dt == torch.float16:
+                assert rel_l2(got.float(), ref) < 1e-3
 
 
 def test_vae_full_size_properties():

@@ -248,6 +248,14 @@ def splitk_workspace(device, M: int, N: int, K: int, flags: int = 0, rows_per_sa
 
 
 # ---------------------------------------------------------------------------------------------- wrappers
+# What a caller can check before it launches anything (csrc/dispatch.cpp ``validate``: ``K & 7``, ``lda & 7``, ``ldw & 7`` are
+# VFACE_ERR_ALIGN and an operand view of 4 GiB - 16 bytes or more is VFACE_ERR_SHAPE; ``vface_softmax_rows``: ``N & 3`` and
+# ``N > 16384``).  A GEMM whose K is a row of softmax output needs both rules of its length: a multiple of 8, at most 16384.
+GEMM_K_MULTIPLE = 8
+SOFTMAX_MAX_COLS = 16384
+OPERAND_BYTES_LIMIT = 0xFFFFFFF0
+
+
 def gemm(a: torch.Tensor, wt: torch.Tensor, out: torch.Tensor, *, M: int, N: int, K: int, lda: int, ldc: int,
          ldw: Optional[int] = None, bias=None, rowbias=None, rows_per_sample: int = 1, residual=None, ldr: int = 0,
          a2=None, lda2: int = 0, k1: int = 0, a2_row_mod: int = 0, flags: int = 0, colstats=None, split_k: bool = True,

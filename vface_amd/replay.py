@@ -4,6 +4,7 @@ the bit self-check and the both-ways timing that decide whether an engine keeps 
 inherits from ``_StepReplay``, says what one forward computes; no kernel is called from this file."""
 from __future__ import annotations
 
+import gc
 import os
 import warnings
 from typing import Dict, Optional
@@ -562,15 +563,25 @@ class _StepReplay:
             # have grown them to their final size (hip.py grows by REPLACING the tensor)
             fixed = lambda: [{k: v.data_ptr() for k, v in d.items()} for d in (hip._splitk_ws, hip._zeros)]
             before = fixed()
+            gc.collect()                             # (before mem0: what it frees is not part of this capture's pool)
             torch.cuda.synchronize()
             mem0 = torch.cuda.memory_allocated(self.device)
             seg = _GraphSegments(self, real_exchange)
             if real_exchange is not None:
                 self.halo_exchange = seg             # start_exchange / finish_exchange cut the capture (see _GraphSegments)
-            with torch.cuda.stream(seg.stream):
-                seg.begin()
-                eps = self.forward_nhwc(Act(xs, x.N, x.H, x.W), ts, context)
-                seg.end(None)
+            # No garbage collection inside the capture pass: a cycle collected there can release device objects of an earlier
+            # configuration (its graphs, their pool, events), and releasing them while this thread captures is a fatal runtime
+            # error, not a Python exception.  Collected above, as ``torch.cuda.graph`` does; the collector stays off until the end.
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.stream(seg.stream):
+                    seg.begin()
+                    eps = self.forward_nhwc(Act(xs, x.N, x.H, x.W), ts, context)
+                    seg.end(None)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             torch.cuda.current_stream().wait_stream(seg.stream)
             pool_bytes = max(0, torch.cuda.memory_allocated(self.device) - mem0)
             if fixed() != before:
