@@ -329,6 +329,32 @@ int vface_quad_crop(const uint8_t* frames, int W, int H, uint8_t* out, int out_s
 int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, const uint8_t* member, int W, int H, float* image,
                           float* inpaint_image, float* inpaint_mask, float* mask_latent, int OW, int OH, int nframes, void* stream);
 
+/* vface_source_tensors: what REFace/scripts/VFace_inference_batch.py makes of the SOURCE image once per clip (:324-355, :462, :468),
+ *   one launch for nimg sources; no atomics, no allocation, capturable; an image's bits do not depend on nimg.
+ *   crop  [nimg][S][S][3] uint8: the aligned crop (:254-258); img [nimg][H][W][3] uint8: the crop after `resize((W, H),
+ *   Image.BILINEAR)` (:350, Pillow bilinear = vface_resample_u8); label [nimg][H][W] uint8 (any value 0..255); member[256] uint8:
+ *   non-zero where the label is on the `preserve_mask_src_FFHQ` list (project_ffhq.yaml:217-224).
+ *     mask        [nimg][1][H][W]    fp32 = isin(label, preserve) = ToTensor(255 m)                               (:324-341)
+ *     masked      [nimg][3][H][W]    fp32 = (u8 / 255 - 0.5) / 0.5 * mask          ref_img_inv_ori                 (:350-352)
+ *     inpaint     [nimg][3][H][W]    fp32 = masked * (1 - mask): x m (1 - m), zero for a {0, 1} mask; reproduced as it is (:354-355)
+ *     mask_latent [nimg][1][OH][OW]  fp32 = Resize([OH, OW])(1 - mask): bilinear, align_corners false, no antialias, fp32 in
+ *                 vface_frame_normalise_resize's order, from the label map itself (as vface_dataset_tensors)      (:462, :468)
+ *     clip_image  [nimg][3][OC][OC]  fp32 = (q / 255 - mean_c) / std_c * Resize((OC, OC))(mask): get_tensor_clip() (:96-104) of
+ *                 q = A.Resize(OC, OC)(crop), times the tensor-resized mask in the same fp32 order; each fp32 operation rounded
+ *                 once (div, sub, div, mul)                                                                        (:342-347)
+ *     clip_u8     [nimg][OC][OC][3]  uint8 = q itself; optional (NULL = not written)
+ *   q is the 8-bit 2-tap resize of albumentations' default, cv2.INTER_LINEAR, in OpenCV's 11-bit fixed-point form: per output
+ *   index d on an axis n_in -> n_out, f = (d + 0.5) n_in / n_out - 0.5 in double, s = floor(f), t = f - s (s < 0: s = 0, t = 0;
+ *   s >= n_in - 1: s = n_in - 1, t = 0), second tap min(s + 1, n_in - 1), w1 = rint(2048 t), w0 = rint(2048 (1 - t)); rows
+ *   R = p[s] w0 + p[s'] w1 in int32, q = (((v0 (R0 >> 4)) >> 16) + ((v1 (R1 >> 4)) >> 16) + 2) >> 2.  The host builds the tables
+ *   (vface_amd/scripts/resample.py `linear_taps_u8`): xtap / ytap int32 [OC][2] = (s, s'), xw / yw int16 [OC][2] = (w0, w1).
+ *   Parity with cv2.resize is NOT pinned: OpenCV is not available to this project's tests.
+ *   Any required pointer NULL or any size <= 0: VFACE_ERR_ARG before the first HIP call. */
+int vface_source_tensors(const uint8_t* crop, int S, const uint8_t* img, const uint8_t* label, const uint8_t* member, int W, int H,
+                         const int32_t* xtap, const int16_t* xw, const int32_t* ytap, const int16_t* yw, float* mask, float* masked,
+                         float* inpaint, float* mask_latent, int OW, int OH, float* clip_image, uint8_t* clip_u8, int OC, int nimg,
+                         void* stream);
+
 /* ---- face parsing: aligned crop -> label map (BiSeNet over ResNet-18) ---------------------------------------------------------
  * The reference runs `faceParsing_demo` -> `FaceParser.forward` -> `BiSeNet` (REFace/pretrained/face_parsing/{face_parsing_demo,
  * model,resnet}.py; scripts/VFace_inference_batch.py:251, 292-294) one frame at a time in fp32.  Its convolutions are vface_conv3x3 /

@@ -15,6 +15,11 @@
 //   mask_latent_kernel       transforms.Resize on the mask tensor (VFace_inference_batch.py:459 = F.interpolate bilinear,
 //                            align_corners = False, no antialias).  It reads the LABEL map, not inpaint_mask, so it does not depend
 //                            on dataset_tensors_kernel's writes and may share its stream position with it.
+//   source_tensors_kernel    the SOURCE image's side of VFace_inference_batch.py (:324-355, :462, :468): preserve mask, masked image,
+//                            its (zero) inpaint image, the latent mask and the CLIP-normalised 224 x 224 image times the resized mask,
+//                            one launch.  The 8-bit resize inside it stands for albumentations' A.Resize (cv2.INTER_LINEAR): OpenCV's
+//                            11-bit fixed-point form as DESIGN §9 states it; parity with cv2.resize itself is NOT pinned (OpenCV is
+//                            not available to the tests).
 //
 // The Lanczos shrink (:108-114) and the bicubic 512 x 512 resize (video_swap_dataset.py:139) are resample_u8_kernel of paste.hip
 // with other tap tables (vface_amd/scripts/intake.py).  HBM-bound byte work, no LDS, one thread per output pixel, coalesced along x.
@@ -100,26 +105,100 @@ __global__ __launch_bounds__(256) void dataset_tensors_kernel(const unsigned cha
     }
 }
 
-// label [F][H][W] -> out [F][1][OH][OW] = resize_bilinear(1 - member[label]); frame_normalise_resize_kernel's arithmetic on one channel
+// one bilinear sample of a {0, 1} map read through the membership table, frame_normalise_resize_kernel's fp32 order on one channel;
+// `invert`: 1 - member (an inpaint mask) or member itself (the source's preserve mask)
+__device__ __forceinline__ float member_bilinear(const unsigned char* __restrict__ label, const unsigned char* __restrict__ member,
+                                                 int W, int H, int ox, int oy, float sx, float sy, bool invert) {
+#pragma clang fp contract(off)
+    const float fy = fmaxf(sy * ((float)oy + 0.5f) - 0.5f, 0.0f), fx = fmaxf(sx * ((float)ox + 0.5f) - 0.5f, 0.0f);
+    const int y0 = min((int)fy, H - 1), x0 = min((int)fx, W - 1);
+    const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
+    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
+    const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
+    auto px = [&](int yy, int xx) {
+        const float m = member[label[(long)yy * W + xx]] ? 1.0f : 0.0f;
+        return invert ? 1.0f - m : m;
+    };
+    const float top = lx0 * px(y0, x0) + lx1 * px(y0, x1);
+    const float bot = lx0 * px(y1, x0) + lx1 * px(y1, x1);
+    return ly0 * top + ly1 * bot;
+}
+
+// label [F][H][W] -> out [F][1][OH][OW] = resize_bilinear(1 - member[label])
 __global__ __launch_bounds__(256) void mask_latent_kernel(const unsigned char* __restrict__ label,
                                                           const unsigned char* __restrict__ member, int W, int H,
                                                           float* __restrict__ out, int OW, int OH) {
-#pragma clang fp contract(off)
     label += (long)blockIdx.y * H * W;
     out += (long)blockIdx.y * OH * OW;
     const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
     const long total = (long)OW * OH;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int oy = (int)(i / OW), ox = (int)(i - (long)oy * OW);
-        const float fy = fmaxf(sy * ((float)oy + 0.5f) - 0.5f, 0.0f), fx = fmaxf(sx * ((float)ox + 0.5f) - 0.5f, 0.0f);
-        const int y0 = min((int)fy, H - 1), x0 = min((int)fx, W - 1);
-        const int y1 = min(y0 + 1, H - 1), x1 = min(x0 + 1, W - 1);
-        const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-        const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-        auto px = [&](int yy, int xx) { return 1.0f - (member[label[(long)yy * W + xx]] ? 1.0f : 0.0f); };
-        const float top = lx0 * px(y0, x0) + lx1 * px(y0, x1);
-        const float bot = lx0 * px(y1, x0) + lx1 * px(y1, x1);
-        out[i] = ly0 * top + ly1 * bot;
+        out[i] = member_bilinear(label, member, W, H, ox, oy, sx, sy, true);
+    }
+}
+
+// The source image's tensors (VFace_inference_batch.py:324-355, :462, :468) in one launch.  Work items of one image, in this order:
+//   [0, H W)                   mask = isin(label, preserve) (:324-341), masked = get_tensor()(img) * mask (:350-352),
+//                              inpaint = masked * (1 - mask) (:354-355: x m (1 - m), zero for a {0, 1} mask; kept as the reference has it)
+//   [H W, H W + OH OW)         mask_latent = Resize([OH, OW])(1 - mask) (:462, :468)
+//   [.., + OC OC)              clip_image = get_tensor_clip()(A.Resize(OC, OC)(crop)) * Resize((OC, OC))(mask) (:342-347); the 8-bit
+//                              resize is the 11-bit fixed-point 2-tap form (include/vface_hip.h), taps and weights from the host's tables
+// crop [nimg][S][S][3], img [nimg][H][W][3], label [nimg][H][W]; xtap / ytap [OC][2] source indices, xw / yw [OC][2] weights
+__global__ __launch_bounds__(256) void source_tensors_kernel(
+    const unsigned char* __restrict__ crop, int S, const unsigned char* __restrict__ img, const unsigned char* __restrict__ label,
+    const unsigned char* __restrict__ member, int W, int H, const int* __restrict__ xtap, const short* __restrict__ xw,
+    const int* __restrict__ ytap, const short* __restrict__ yw, float* __restrict__ mask, float* __restrict__ masked,
+    float* __restrict__ inpaint, float* __restrict__ mask_latent, int OW, int OH, float* __restrict__ clip_image,
+    unsigned char* __restrict__ clip_u8, int OC) {
+#pragma clang fp contract(off)
+    const long hw = (long)H * W, nlat = (long)OH * OW, nclip = (long)OC * OC;
+    crop += (long)blockIdx.y * S * S * 3;
+    img += (long)blockIdx.y * hw * 3;
+    label += (long)blockIdx.y * hw;
+    mask += (long)blockIdx.y * hw;
+    masked += (long)blockIdx.y * hw * 3;
+    inpaint += (long)blockIdx.y * hw * 3;
+    mask_latent += (long)blockIdx.y * nlat;
+    clip_image += (long)blockIdx.y * nclip * 3;
+    if (clip_u8) clip_u8 += (long)blockIdx.y * nclip * 3;
+    const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, stdv[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+    const long total = hw + nlat + nclip;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        if (i < hw) {
+            const float m = member[label[i]] ? 1.0f : 0.0f;               // ToTensor(255 or 0) = {1, 0}
+            const float keep = 1.0f - m;
+            mask[i] = m;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = ((float)img[i * 3 + c] / 255.0f - 0.5f) / 0.5f * m;
+                masked[(long)c * hw + i] = v;
+                inpaint[(long)c * hw + i] = v * keep;
+            }
+        } else if (i < hw + nlat) {
+            const long j = i - hw;
+            const int oy = (int)(j / OW), ox = (int)(j - (long)oy * OW);
+            mask_latent[j] = member_bilinear(label, member, W, H, ox, oy, (float)W / (float)OW, (float)H / (float)OH, true);
+        } else {
+            const long j = i - hw - nlat;
+            const int oy = (int)(j / OC), ox = (int)(j - (long)oy * OC);
+            // (the tables come from the host: re-clamped so that no tap can leave the crop)
+            const int xa = min(max(xtap[ox * 2], 0), S - 1), xb = min(max(xtap[ox * 2 + 1], 0), S - 1);
+            const int ya = min(max(ytap[oy * 2], 0), S - 1), yb = min(max(ytap[oy * 2 + 1], 0), S - 1);
+            const int w0 = xw[ox * 2], w1 = xw[ox * 2 + 1], v0 = yw[oy * 2], v1 = yw[oy * 2 + 1];
+            const unsigned char* r0 = crop + (long)ya * S * 3;
+            const unsigned char* r1 = crop + (long)yb * S * 3;
+            const float mr = member_bilinear(label, member, W, H, ox, oy, (float)W / (float)OC, (float)H / (float)OC, false);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int R0 = r0[xa * 3 + c] * w0 + r0[xb * 3 + c] * w1;
+                const int R1 = r1[xa * 3 + c] * w0 + r1[xb * 3 + c] * w1;
+                const int q = (((v0 * (R0 >> 4)) >> 16) + ((v1 * (R1 >> 4)) >> 16) + 2) >> 2;
+                const unsigned char q8 = (unsigned char)min(max(q, 0), 255);
+                if (clip_u8) clip_u8[j * 3 + c] = q8;
+                clip_image[(long)c * nclip + j] = ((float)q8 / 255.0f - mean[c]) / stdv[c] * mr;
+            }
+        }
     }
 }
 
@@ -145,5 +224,22 @@ extern "C" int vface_dataset_tensors(const uint8_t* crop, const uint8_t* label, 
                        inpaint_image, inpaint_mask, (long)W * H);
     hipLaunchKernelGGL(mask_latent_kernel, dim3(vf_grid((long)OW * OH, 256, 8192), nframes), dim3(256), 0, stream, label, member, W, H, mask_latent,
                        OW, OH);
+    return vf_launched();
+}
+
+extern "C" int vface_source_tensors(const uint8_t* crop, int S, const uint8_t* img, const uint8_t* label, const uint8_t* member, int W,
+                                    int H, const int32_t* xtap, const int16_t* xw, const int32_t* ytap, const int16_t* yw, float* mask,
+                                    float* masked, float* inpaint, float* mask_latent, int OW, int OH, float* clip_image,
+                                    uint8_t* clip_u8, int OC, int nimg, void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
+    if (!crop || !img || !label || !member || !xtap || !xw || !ytap || !yw) return VF_ERR_ARG;
+    if (!mask || !masked || !inpaint || !mask_latent || !clip_image) return VF_ERR_ARG;      // (clip_u8 is optional)
+    if (nimg <= 0 || S <= 0 || W <= 0 || H <= 0 || OW <= 0 || OH <= 0 || OC <= 0) return VF_ERR_ARG;
+    if (nimg > 65535 || (long)S * S > 0x7fffffffL / 3 || (long)W * H > 0x7fffffffL / 3 || (long)OC * OC > 0x7fffffffL / 3 ||
+        (long)OW * OH > 0x7fffffffL)
+        return VF_ERR_SHAPE;
+    const long total = (long)W * H + (long)OW * OH + (long)OC * OC;
+    hipLaunchKernelGGL(source_tensors_kernel, dim3(vf_grid(total, 256, 8192), nimg), dim3(256), 0, stream, crop, S, img, label, member, W, H,
+                       xtap, xw, ytap, yw, mask, masked, inpaint, mask_latent, OW, OH, clip_image, clip_u8, OC);
     return vf_launched();
 }

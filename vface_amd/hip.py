@@ -84,6 +84,8 @@ SIGNATURES = {
     "vface_frame_normalise_resize": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vface_source_tensors": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
+                                       _i32, _i32, _vp]),
     "vface_parse_prefilter": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp]),
     "vface_maxpool3x3s2": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i32, _vp]),
     "vface_channel_gate": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
@@ -581,6 +583,47 @@ def dataset_tensors(crop: torch.Tensor, label: torch.Tensor, member: torch.Tenso
                                       _stream())
     _check(rc, "vface_dataset_tensors")
     return image, inpaint, mask, mlat
+
+
+def source_tensors(crop: torch.Tensor, img: torch.Tensor, label: torch.Tensor, member: torch.Tensor, taps, latent: Tuple[int, int],
+                   clip_size: int, out=None, clip_u8: Optional[torch.Tensor] = None):
+    """The source image's tensors (VFace_inference_batch.py:324-355, :462, :468) in one launch: uint8 aligned crops [N, S, S, 3],
+    the same crops after the Pillow-bilinear resize ``img`` [N, H, W, 3] (:350), uint8 label maps [N, H, W]; ``member``:
+    ``label_membership(preserve_labels)``; ``taps`` = ``(xtap, xw, ytap, yw)``, the device tables of ``resample.linear_taps_u8(S,
+    clip_size)`` (int32 [clip_size, 2] / int16 [clip_size, 2]); ``latent`` = (h, w).  Returns fp32 ``mask [N, 1, H, W], masked
+    [N, 3, H, W], inpaint [N, 3, H, W], mask_latent [N, 1, h, w], clip_image [N, 3, clip_size, clip_size]`` (written into the five
+    tensors of ``out`` if given); ``clip_u8`` uint8 [N, clip_size, clip_size, 3], if given, receives the 8-bit resize itself.  That
+    resize is OpenCV's 11-bit fixed-point form as DESIGN §9 states it; parity with ``cv2.resize`` is not pinned."""
+    if crop.dtype != torch.uint8 or crop.dim() != 4 or crop.shape[3] != 3 or crop.shape[1] != crop.shape[2] or not crop.is_contiguous():
+        raise VFaceHipError("source_tensors: crops must be contiguous uint8 [N, S, S, 3]")
+    N, S = crop.shape[0], crop.shape[1]
+    if img.dtype != torch.uint8 or img.dim() != 4 or img.shape[0] != N or img.shape[3] != 3 or not img.is_contiguous():
+        raise VFaceHipError("source_tensors: img must be contiguous uint8 [N, H, W, 3], one per crop")
+    H, W = img.shape[1], img.shape[2]
+    if label.dtype != torch.uint8 or tuple(label.shape) != (N, H, W) or not label.is_contiguous():
+        raise VFaceHipError(f"source_tensors: label maps must be contiguous uint8 {[N, H, W]}, img's size; got {list(label.shape)}")
+    if member.dtype != torch.uint8 or tuple(member.shape) != (256,) or not member.is_contiguous():
+        raise VFaceHipError("source_tensors: member must be the uint8 [256] table of label_membership()")
+    oh, ow, oc = int(latent[0]), int(latent[1]), int(clip_size)
+    if min(N, S, H, W, oh, ow, oc) <= 0:
+        raise VFaceHipError("source_tensors: N, S, H, W, the latent grid and clip_size must be positive")
+    xtap, xw, ytap, yw = taps
+    for t, dt in ((xtap, torch.int32), (xw, torch.int16), (ytap, torch.int32), (yw, torch.int16)):
+        if t.dtype != dt or tuple(t.shape) != (oc, 2) or not t.is_contiguous():
+            raise VFaceHipError("source_tensors: taps must be int32 [clip_size, 2] / int16 [clip_size, 2] tables (linear_taps_u8)")
+    shapes = [(N, 1, H, W), (N, 3, H, W), (N, 3, H, W), (N, 1, oh, ow), (N, 3, oc, oc)]
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=crop.device) for s in shapes)
+    for t, s in zip(out, shapes):
+        if t.dtype != torch.float32 or tuple(t.shape) != s or not t.is_contiguous():
+            raise VFaceHipError(f"source_tensors: outputs must be contiguous fp32 {shapes}")
+    if clip_u8 is not None and (clip_u8.dtype != torch.uint8 or tuple(clip_u8.shape) != (N, oc, oc, 3) or not clip_u8.is_contiguous()):
+        raise VFaceHipError(f"source_tensors: clip_u8 must be contiguous uint8 {[N, oc, oc, 3]}")
+    mask, masked, inpaint, mlat, clip_image = out
+    rc = load().vface_source_tensors(_p(crop), S, _p(img), _p(label), _p(member), W, H, _p(xtap), _p(xw), _p(ytap), _p(yw), _p(mask),
+                                     _p(masked), _p(inpaint), _p(mlat), ow, oh, _p(clip_image), _p(clip_u8), oc, N, _stream())
+    _check(rc, "vface_source_tensors")
+    return mask, masked, inpaint, mlat, clip_image
 
 
 # ---- glue of the face-parsing network (csrc/parsing.hip; include/vface_hip.h "face parsing") ----

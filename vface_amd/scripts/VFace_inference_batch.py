@@ -7,7 +7,7 @@ CLIP/ArcFace/landmark conditioning, the KL-VAE and paste-back (``:193-528, 596-6
 build: it needs checkpoints and third-party models that are not available offline.  ``--synthetic``
 therefore stands in for those stages with seeded synthetic latents / conditioning / flow of the right shapes and
 writes the denoised latents; without it the script stops with a message saying what is missing.  The widening flags
-(``--with_vae``, ``--raft_flow``, ``--intake``, ``--parse``, ``--paste_back``, ``--clip_cond``) replace one stand-in each by the
+(``--with_vae``, ``--raft_flow``, ``--intake``, ``--source_intake``, ``--parse``, ``--paste_back``, ``--clip_cond``) replace one stand-in each by the
 stage itself on the GPU (synthetic weights unless ``--ckpt`` covers it).
 
     python -m vface_amd.scripts.VFace_inference_batch --synthetic --n_frames 24 --n_samples 8 --ddim_steps 50
@@ -78,6 +78,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="with --intake: the label maps come from the face parser on the GPU -- faceParsing_demo on the aligned "
                         "crops (:251, :292-294; pretrained/face_parsing, vface_amd/parsing.py) -- instead of synthetic rings; needs "
                         "--H 512 --W 512, the size of the reference's map (video_swap_dataset.py:139)")
+    p.add_argument("--source_intake", action="store_true",
+                   help="with --intake: the source image's side runs on the GPU too -- a (synthetic) source frame and quad go through "
+                        "the aligned crop, the label map (the parser's with --parse), the preserve mask, the masked 512 x 512 image, "
+                        "its latents and the CLIP-normalised 224 x 224 image (:254-355, :462-468; scripts/intake.py FrameIntake.source, "
+                        "scripts/source.py) once per clip, and every batch's inversion takes [target ; source] as the reference "
+                        "builds it (:509-527); with --clip_cond the source's CLIP / identity features come from that image")
     p.add_argument("--faceParsing_ckpt", type=str, default=None,
                    help="face-parsing state dict (Other_dependencies/face_parsing/79999_iter.pth); default synthetic weights")
     p.add_argument("--faceParser_name", type=str, default="default", help="default (BiSeNet) | segnext (mmseg: not built)")
@@ -88,8 +94,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--clip_cond", action="store_true",
                    help="the conditioning tokens come from the conditioning stage on the GPU -- FrozenCLIPEmbedder (ViT-L/14, mapper2) "
                         "and conditioning_with_feat (:437-442, :491-500; vface_amd/clip.py) on the batch's frames: the intake's image "
-                        "and mask with --intake, seeded images otherwise -- instead of seeded N(0, 1); the ArcFace features, the "
-                        "landmarks and the source image stay seeded inputs")
+                        "and mask with --intake, seeded images otherwise -- instead of seeded N(0, 1); the ArcFace features and the "
+                        "landmarks stay seeded inputs, and so does the source image unless --source_intake makes it")
     p.add_argument("--arcface", action="store_true",
                    help="with --clip_cond: the identity features of the mix come from ArcFace IR-SE50 on the GPU (IDLoss.extract_feats, "
                         "ddpm.py:91-124, :1010; vface_amd/arcface.py) -- once for the source image, once per batch for the masked "
@@ -247,6 +253,7 @@ def _quad_coeffs(size, quad):
 
 
 REMOVE_MASK_TAR_FFHQ = (1, 2, 3, 5, 6, 7, 9)      # models/REFace/configs/project_ffhq.yaml: remove_mask_tar_FFHQ
+PRESERVE_MASK_SRC_FFHQ = (1, 2, 3, 5, 6, 7, 9)    # project_ffhq.yaml:217-224: preserve_mask_src_FFHQ (the source's face region)
 
 
 def synthetic_intake_inputs(F_: int, S_: int, H: int, W: int, seed: int):
@@ -283,6 +290,12 @@ def check_parse_options(opt):
         raise SystemExit(f"--faceParser_name: default | segnext; got {opt.faceParser_name!r}")
 
 
+def check_source_options(opt):
+    """--source_intake runs the source image through the intake's kernels and sizes."""
+    if getattr(opt, "source_intake", False) and not getattr(opt, "intake", False):
+        raise SystemExit("--source_intake makes the source's tensors with the frame intake: it needs --intake")
+
+
 def run_synthetic(opt) -> dict:
     from ..ldm.models.diffusion.ddim_w_inv import DDIMSampler, HookPlan
     from ..ldm.models.diffusion.ddpm import LatentDiffusion
@@ -291,6 +304,8 @@ def run_synthetic(opt) -> dict:
     if getattr(opt, "intake", False) and not opt.with_vae:
         raise SystemExit("--intake makes the pixels the VAE encodes: it needs --with_vae")
     check_parse_options(opt)
+    check_source_options(opt)
+    source_intake = bool(getattr(opt, "source_intake", False))
     dev = torch.device("cuda", 0)
     dt = torch.float16 if opt.compute_dtype == "fp16" else torch.bfloat16
     cfg = load_unet_config(opt.config)
@@ -320,7 +335,7 @@ def run_synthetic(opt) -> dict:
             synth.fill_arcface_(model.face_ID_model.facenet, seed=5, prefix="face_ID_model.facenet.")
     model = model.to(dev).eval()
     e_source, id_source = None, None
-    if clip_cond:       # :437: the source image, resized and CLIP-normalised, is encoded once per clip and broadcast
+    if clip_cond and not source_intake:       # :437: the source image, resized and CLIP-normalised, is encoded once per clip and broadcast
         source224 = synth.synth_normal("cli.source224", (1, 3, 224, 224)).to(dev)
         e_source = model.get_learned_conditioning(source224)
         if arcface:     # :437 -> ddpm.py:1010: the source's identity, once per clip
@@ -348,6 +363,22 @@ def run_synthetic(opt) -> dict:
         from ..pretrained.face_parsing import FaceParser
         parser = FaceParser(seg_ckpt=opt.faceParsing_ckpt, size=1024, device=dev, dtype=dt)
         parser.seg.engine      # fold and upload the weights now, not inside the first batch's `parse` stage
+    source_state, source_seconds = None, None
+    if source_intake:       # :254-355, :436-438, :462-468: once per clip; a seeded frame and quad stand in for the photo and dlib
+        from .source import prepare_source
+        src_frames, src_quads, src_labels = synthetic_intake_inputs(1, opt.frame_size, opt.H, opt.W, opt.seed + 500)
+        src_lmk = synth.synth_normal("cli.landmarks_src", (1, 136)).to(dev) * 0.1 + 0.5
+        src_id = None if arcface else synth.synth_normal("cli.id_feat_src", (1, 512)).to(dev)
+        src_frames, src_labels = src_frames.to(dev), src_labels.to(dev)
+        torch.cuda.synchronize()
+        ts_ = time.time()
+        src = intake.source(src_frames, src_quads, labels_u8=None if parser is not None else src_labels, parser=parser,
+                            preserve_labels=PRESERVE_MASK_SRC_FFHQ, convert_to_seg12=opt.seg12)
+        source_state = prepare_source(model, src, landmarks_src=src_lmk, id_feat=src_id)
+        torch.cuda.synchronize()
+        source_seconds = time.time() - ts_
+        if clip_cond:
+            e_source, id_source = source_state.e_source, source_state.id_source
     nbatches = opt.n_frames // F_       # DataLoader(batch_size=n_samples, drop_last=True) (:376-382)
     # --pipeline_inversion: the DDIM inversion of batch k + 1 runs beside the sampling of batch k (DDIMSampler.sample_while_inverting:
     # the batches are independent, :413, :529-553); batch 0's inversion runs alone, the last batch's sampling too
@@ -430,15 +461,24 @@ def run_synthetic(opt) -> dict:
             flow = [f[None] for f in synth.synth_flow(F_ - 1, h, w, seed=opt.seed + batch_id)]
         inv_store = {}
         invert_kw = None
+        if source_state is not None and batch_id == 0:
+            stages["source_intake"] = source_seconds
         if opt.no_inversion:
             sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
             for s in sampler.ddim_timesteps:
                 inv_store[int(s)] = d(synth.synth_normal(tag(f"inv{int(s)}"), (F_, opt.C, h, w)))
         else:
             # :531-540: invert [target ; source] (2F), hooks off; the target half is cached per timestep
-            z2 = d(synth.synth_normal(tag("z2"), (2 * F_, opt.C, h, w)))
-            kw2 = {"inpaint_image": torch.cat([z_inp, z_inp]), "inpaint_mask": torch.cat([mask, mask])}
-            invert_kw = dict(x=z2, cond=torch.cat([tc, c]), S=opt.ddim_steps, shape=[opt.C, h, w], eta=opt.ddim_eta,
+            if source_state is not None:    # :488-490, :509-525: z2_tar = encode(prior), prior = the batch's image; the source's own half
+                ts_ = stage(stages, "_", time.time())
+                z2_tar = model.get_first_stage_encoding(model.encode_first_stage(img)).detach()
+                stage(stages, "vae_encode", ts_)
+                z2, cond2, kw2 = source_state.inversion_operands(z2_tar, tc, z_inp, mask, cond_src=None if clip_cond else c)
+            else:
+                z2 = d(synth.synth_normal(tag("z2"), (2 * F_, opt.C, h, w)))
+                cond2 = torch.cat([tc, c])
+                kw2 = {"inpaint_image": torch.cat([z_inp, z_inp]), "inpaint_mask": torch.cat([mask, mask])}
+            invert_kw = dict(x=z2, cond=cond2, S=opt.ddim_steps, shape=[opt.C, h, w], eta=opt.ddim_eta,
                              unconditional_guidance_scale=opt.scale, unconditional_conditioning=None,
                              inverse_dir=inv_store, batch_size=F_, test_model_kwargs=kw2, max_steps=opt.max_steps)
         return {"id": batch_id, "c": c, "uc": uc, "tc": tc, "z_inp": z_inp, "mask": mask, "flow": flow, "inv_store": inv_store,
@@ -529,6 +569,7 @@ def run_synthetic(opt) -> dict:
         results.append({"batch": batch_id, "frames": F_, "sample_seconds": dt_s, "batch_wall_seconds": time.time() - t_batch,
                         "samples": samples if getattr(opt, "return_samples", False) else None,
                         "labels": cur["labels"] if getattr(opt, "return_samples", False) else None,
+                        "inversion_cache": dict(cur["inv_store"]) if getattr(opt, "return_samples", False) else None,
                         "finite": bool(torch.isfinite(samples).all()) and (pixels is None or bool(torch.isfinite(pixels).all())),
                         "pixels": None if pixels is None else list(pixels.shape),
                         "pasted": None if pasted is None else list(pasted.shape), "paste_seconds": paste_s,
@@ -550,6 +591,7 @@ def main(argv=None):
                  "that are not available offline; run with --synthetic, or feed real latents through "
                  "vface_amd.ldm.models.diffusion.ddim_w_inv.DDIMSampler (see INTEGRATION.md).")
     check_parse_options(opt)
+    check_source_options(opt)
     if not torch.cuda.is_available():
         sys.exit("An MI355X is required: the VFace hot path has no CPU fallback.")
     return run_synthetic(opt)

@@ -23,13 +23,25 @@ the inputs here.  Host work is limited to O(F) scalars and the per-size tap tabl
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .. import hip
-from .resample import resample_coeffs
+from .resample import linear_taps_u8, resample_coeffs
+from .VFace_inference_batch import PRESERVE_MASK_SRC_FFHQ
+
+
+class SourceTensors(NamedTuple):
+    """What ``FrameIntake.source`` makes of the source image(s) (VFace_inference_batch.py:254-355, :462, :468)."""
+    crop: torch.Tensor                   # uint8 [n, S, S, 3]        the aligned crop (:254-258)
+    labels: torch.Tensor                 # uint8 [n, H, W]           the parser's map (:263), or the one given
+    clip_image: torch.Tensor             # fp32 [n, 3, c, c]         ref_image_tensor (:343-347)
+    mask: torch.Tensor                   # fp32 [n, 1, H, W]         reference_mask_tensor (:341)
+    masked: torch.Tensor                 # fp32 [n, 3, H, W]         ref_img_inv_ori (:350-352)
+    inpaint_image: torch.Tensor          # fp32 [n, 3, H, W]         ref_img_inv_ori_inpaint (:354-355), zero as in the reference
+    inpaint_mask_latent: torch.Tensor    # fp32 [n, 1, h, w]         inpaint_mask_src (:462, :468)
 
 
 def quad_from_landmarks(lm) -> np.ndarray:
@@ -116,6 +128,7 @@ class FrameIntake:
         self.device = torch.device(device)
         self._tables: Dict[Tuple[int, int, str], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._members: Dict[Tuple[int, ...], torch.Tensor] = {}
+        self._linear: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
 
     def _table(self, in_size: int, out_size: int, filter: str):
         key = (in_size, out_size, filter)
@@ -177,6 +190,37 @@ class FrameIntake:
             self._members[key] = hip.label_membership(key, self.device)
         img = self.resize_u8(crops_u8.contiguous(), self.W, self.H, "bicubic")                  # :139
         return hip.dataset_tensors(img, labels_u8.contiguous(), self._members[key], self.latent)
+
+    def _member(self, labels: Sequence[int]) -> torch.Tensor:
+        key = tuple(sorted(int(v) for v in labels))
+        if key not in self._members:
+            self._members[key] = hip.label_membership(key, self.device)
+        return self._members[key]
+
+    def source(self, frames_u8: torch.Tensor, quads, labels_u8: Optional[torch.Tensor] = None, parser=None,
+               preserve_labels: Sequence[int] = PRESERVE_MASK_SRC_FFHQ, clip_size: int = 224,
+               convert_to_seg12: bool = True) -> SourceTensors:
+        """The source image's side of ``VFace_inference_batch.py`` (:254-355, :462, :468): uint8 frames [n, Hs, Ws, 3] (device),
+        one quad [4, 2] each, and either the label maps uint8 [n, H, W] or a ``FaceParser`` that makes them from the aligned crop
+        (:263) -> ``SourceTensors``.  ``crop`` (:254-258), the parser, ``resize((W, H), Image.BILINEAR)`` (:350; Pillow's
+        bilinear, not the bicubic default the target frames get) and one ``hip.source_tensors`` launch.  The 224 x 224 resize of
+        :343 (albumentations ``A.Resize``, ``cv2.INTER_LINEAR``) is OpenCV's 11-bit fixed-point form as DESIGN §9 states it;
+        parity with ``cv2.resize`` is not pinned."""
+        if labels_u8 is None and parser is None:
+            raise ValueError("source: give the label maps (labels_u8) or the face parser that makes them (parser)")
+        crop = self.crop(frames_u8, quads)
+        if labels_u8 is None:
+            labels_u8 = parser.labels(crop, convert_to_seg12=convert_to_seg12)
+        self._check(labels_u8, "label maps")
+        S, c = self.image_size, int(clip_size)
+        if (S, c) not in self._linear:
+            taps, weights = linear_taps_u8(S, c)
+            self._linear[(S, c)] = (torch.from_numpy(taps).to(self.device), torch.from_numpy(weights).to(self.device))
+        taps, weights = self._linear[(S, c)]
+        img = self.resize_u8(crop, self.W, self.H, "bilinear")                                  # :350
+        mask, masked, inpaint, mlat, clip_image = hip.source_tensors(crop, img, labels_u8.contiguous(), self._member(preserve_labels),
+                                                                     (taps, weights, taps, weights), self.latent, c)
+        return SourceTensors(crop, labels_u8, clip_image, mask, masked, inpaint, mlat)
 
     def __call__(self, frames_u8: torch.Tensor, quads, labels_u8: torch.Tensor, remove_labels: Sequence[int]):
         """Frames + quads + label maps -> ``image, inpaint_image, inpaint_mask, mask_latent, inv_transforms``; the last is the

@@ -78,3 +78,28 @@ def resample_coeffs(in_size: int, out_size: int, filter: str = "bilinear") -> Tu
     fixed = w * float(1 << PRECISION_BITS)
     kk = np.where(w < 0, np.trunc(-0.5 + fixed), np.trunc(0.5 + fixed)).astype(np.int32)
     return np.stack([xmin, xmax], 1).astype(np.int32), kk
+
+
+LINEAR_COEF_BITS = 11            # OpenCV resize: INTER_RESIZE_COEF_BITS, weights are 11-bit fixed point
+
+
+def linear_taps_u8(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Tap tables of the 8-bit 2-tap linear resize ``hip.source_tensors`` runs for ``A.Resize`` (albumentations' default,
+    ``cv2.INTER_LINEAR``) from ``in_size`` to ``out_size`` samples: ``taps`` int32 [out_size, 2] = the two source samples and
+    ``weights`` int16 [out_size, 2] = their 11-bit fixed-point weights.  Half-pixel centres, no antialias: for output ``d``,
+    ``f = (d + 0.5) * in / out - 0.5`` in double, ``s = floor(f)``, ``t = f - s``; below the first sample and from the last one
+    on, the tap is that sample with weight 2048; ``w1 = rint(2048 t)``, ``w0 = rint(2048 (1 - t))``, round half to even.  This is
+    OpenCV's long-standing fixed-point form as DESIGN §9 states it; parity with ``cv2.resize`` is not pinned (OpenCV is not
+    available to the tests)."""
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError("linear_taps_u8: sizes must be positive")
+    f = (np.arange(out_size, dtype=np.float64) + 0.5) * float(in_size) / float(out_size) - 0.5
+    s = np.floor(f)
+    t = f - s
+    low, high = s < 0, s >= in_size - 1
+    s = np.where(low, 0, np.where(high, in_size - 1, s)).astype(np.int64)
+    t = np.where(low | high, 0.0, t)
+    one = float(1 << LINEAR_COEF_BITS)
+    taps = np.stack([s, np.minimum(s + 1, in_size - 1)], 1).astype(np.int32)
+    weights = np.stack([np.rint(one * (1.0 - t)), np.rint(one * t)], 1).astype(np.int16)
+    return taps, weights
