@@ -303,6 +303,18 @@ int vface_perspective_paste(const uint8_t* crop, int crop_w, int crop_h, uint8_t
  * kernel differs from it by <= 2 ulp (tests bound it at 2e-6). */
 int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out, int OW, int OH, int frames, void* stream);
 
+/* ---- video mux, colour half (REFace/scripts/VFace_inference_batch.py:646-654) ------------------------------------------------
+ * The reference writes the pasted frames as PNG (:636) and asks ffmpeg for `-pix_fmt yuv420p -colorspace bt709 -color_range tv`
+ * at 10 fps (:646-654); swscale converts on the host.  vface_rgb_to_yuv420 makes that conversion on the device, so the host
+ * receives 1.5 bytes per pixel instead of 3 (vface_amd/scripts/mux.py writes them as YUV4MPEG2; H.264 and audio are not built).
+ *   rgb [frames][H][W][3], the layout the paste-back returns -> out: one I420 frame per frame, frame f at out + f * frame_stride:
+ *   Y [H][W], Cb [ch][cw], Cr [ch][cw], cw = (W + 1) / 2, ch = (H + 1) / 2.  Bytes between frames are not written.
+ *   Integer arithmetic, stated once in tests/mux_model.py and equal to it bit for bit: 16-bit BT.709 limited-range coefficients,
+ *   half-up rounding, luma per pixel, chroma from the mean of the pixels of a 2 x 2 block that exist (centre-sited).  W and H
+ *   may be odd; no alignment is required of either pointer or of frame_stride.
+ *   NULL pointer, W, H or frames <= 0: VFACE_ERR_ARG; frame_stride < W * H + 2 * cw * ch: VFACE_ERR_SHAPE -- before the first HIP call. */
+int vface_rgb_to_yuv420(const uint8_t* rgb, int W, int H, uint8_t* out, int64_t frame_stride, int frames, void* stream);
+
 /* ---- frame intake: decoded frame -> aligned crop -> the sampler's tensors (the mirror image of the paste-back) ---------------
  * The reference runs these steps per frame on the host with Pillow and numpy.  The Lanczos shrink of a large face
  * (alignmengt.py:108-114) and the bicubic resize to 512 x 512 (video_swap_dataset.py:139) are vface_resample_u8 with the tap

@@ -82,6 +82,7 @@ SIGNATURES = {
     "vface_resample_u8": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     "vface_perspective_paste": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_frame_normalise_resize": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vface_rgb_to_yuv420": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _i32, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vface_source_tensors": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
@@ -516,6 +517,33 @@ def frame_normalise_resize(frame: torch.Tensor, OH: int, OW: int) -> torch.Tenso
     F_, H, W, _ = frame.shape
     out = torch.empty(F_, 3, OH, OW, dtype=torch.float32, device=frame.device)
     _check(load().vface_frame_normalise_resize(_p(frame), W, H, _p(out), OW, OH, F_, _stream()), "vface_frame_normalise_resize")
+    return out
+
+
+def i420_frame_bytes(W: int, H: int) -> int:
+    """Bytes of one I420 frame: Y [H][W] + Cb and Cr [(H + 1) / 2][(W + 1) / 2]."""
+    return W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)
+
+
+def rgb_to_yuv420(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 frames [F, H, W, 3] (what ``PasteBack.paste`` returns) -> uint8 [F, frame_bytes]: per frame the I420 planes Y [H][W],
+    Cb [ch][cw], Cr [ch][cw] -- BT.709, limited range, chroma centre-sited; the integer arithmetic of ``tests/mux_model.py``, bit
+    for bit (csrc/mux.hip).  ``out``: a uint8 [F, frame_bytes] view with unit column stride and a row stride of at least
+    frame_bytes (frames inside a larger buffer); the bytes between frames are not written."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise VFaceHipError("rgb_to_yuv420: frames must be contiguous uint8 [F, H, W, 3]")
+    F_, H, W, _ = frames_u8.shape
+    if min(F_, H, W) <= 0:
+        raise VFaceHipError("rgb_to_yuv420: F, H and W must be positive")
+    n = i420_frame_bytes(W, H)
+    if out is None:
+        out = torch.empty(F_, n, dtype=torch.uint8, device=frames_u8.device)
+    elif (out.dtype != torch.uint8 or tuple(out.shape) != (F_, n) or out.stride(1) != 1 or (F_ > 1 and out.stride(0) < n)
+          or out.device != frames_u8.device):
+        raise VFaceHipError(f"rgb_to_yuv420: out must be a uint8 {[F_, n]} view on the frames' device, unit column stride, "
+                            f"row stride >= {n}")
+    stride = out.stride(0) if F_ > 1 else max(out.stride(0), n)
+    _check(load().vface_rgb_to_yuv420(_p(frames_u8), W, H, _p(out), stride, F_, _stream()), "vface_rgb_to_yuv420")
     return out
 
 

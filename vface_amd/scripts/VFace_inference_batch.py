@@ -2,15 +2,22 @@
 
 What runs here is the part of ``run_inference`` that is the hot path (``:529-594``): optional DDIM inversion of
 the target latents into a latent cache, then ``sampler.sample`` over batches of ``--n_samples`` frames with the
-shipped hook schedule.  Everything around it in the reference -- video decoding, dlib crop/align, face parsing,
-CLIP/ArcFace/landmark conditioning, the KL-VAE and paste-back (``:193-528, 596-670``) -- is out of scope of this
-build: it needs checkpoints and third-party models that are not available offline.  ``--synthetic``
-therefore stands in for those stages with seeded synthetic latents / conditioning / flow of the right shapes and
-writes the denoised latents; without it the script stops with a message saying what is missing.  The widening flags
-(``--with_vae``, ``--raft_flow``, ``--intake``, ``--source_intake``, ``--parse``, ``--paste_back``, ``--clip_cond``) replace one stand-in each by the
-stage itself on the GPU (synthetic weights unless ``--ckpt`` covers it).
+shipped hook schedule.  ``--synthetic`` stands in for everything around it in the reference -- video decoding, dlib
+crop/align, face parsing, CLIP/ArcFace/landmark conditioning, the KL-VAE and paste-back (``:193-528, 596-670``) -- with
+seeded synthetic latents / conditioning / flow of the right shapes and writes the denoised latents.  The widening flags
+(``--with_vae``, ``--raft_flow``, ``--intake``, ``--source_intake``, ``--parse``, ``--paste_back``, ``--clip_cond``, ``--arcface``) replace one
+stand-in each by the stage itself on the GPU (synthetic weights unless ``--ckpt`` covers it).
 
     python -m vface_amd.scripts.VFace_inference_batch --synthetic --n_frames 24 --n_samples 8 --ddim_steps 50
+
+Without ``--synthetic`` the run is a real clip's (``run_clip``): every one of those stages, on frames, a source image and a
+landmarks file from disk (``scripts/clip_io.py``; dlib and the video decoder stay outside, so the ``{index}.png`` frames the
+reference writes at ``:285`` and dlib's 68 points are inputs), the pasted frames out as PNG (``:636``) and, with ``--video_out``, as
+a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps (``:646-654``; ``scripts/mux.py``).  H.264 and
+audio are not built.
+
+    python -m vface_amd.scripts.VFace_inference_batch --target_frames clip/ --src_image src.png --landmarks clip.npz \\
+        --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.y4m
 """
 from __future__ import annotations
 
@@ -60,6 +67,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--precision", type=str, choices=["full", "autocast"], default="autocast")
     # additions of this build
     p.add_argument("--synthetic", action="store_true", help="synthetic latents/conditioning/flow instead of video I/O")
+    p.add_argument("--target_frames", type=str, default=None,
+                   help="real-clip run: folder of the target clip's frames, {index}.png (or .jpg) as the reference writes them (:285); "
+                        "taken in the order of the integer index, the first --n_frames of them")
+    p.add_argument("--src_image", type=str, default=None, help="real-clip run: the source image (the identity to put in)")
+    p.add_argument("--landmarks", type=str, default=None,
+                   help="real-clip run: .npz with dlib's 68 points, which this build does not compute -- frames [N, 68, 2] (a NaN row = "
+                        "no face found), source [68, 2], optionally crops [N, 68, 2] and source_crop [68, 2] (scripts/clip_io.py)")
+    p.add_argument("--video_out", type=str, default=None,
+                   help="real-clip run: write the pasted frames as a YUV4MPEG2 file (yuv420p, BT.709, tv range, 10 fps: :646-654; "
+                        "scripts/mux.py) -- the hand-off to an encoder; H.264 and audio are not built")
+    p.add_argument("--synthetic_weights", action="store_true",
+                   help="real-clip run on seeded weights for every model (the seeds of --synthetic) instead of --ckpt, "
+                        "--faceParsing_ckpt and --raft_ckpt: for tests and smoke runs")
     p.add_argument("--raft_flow", action="store_true",
                    help="compute the optical flow from the (synthetic) target frames with the RAFT-shaped producer "
                         "(temporal_flow.return_flow, VFace_inference_batch.py:550-553) instead of a synthetic field; implies "
@@ -297,6 +317,52 @@ def check_source_options(opt):
 
 
 def run_synthetic(opt) -> dict:
+    return _run_pipeline(opt, None)
+
+
+CLIP_STAGES = ("with_vae", "intake", "parse", "paste_back", "clip_cond", "arcface", "source_intake", "raft_flow")
+
+
+def run_clip(opt) -> dict:
+    """The reference's whole chain on a clip from disk (``--target_frames``, ``--src_image``, ``--landmarks``): the stages of
+    ``run_synthetic`` with every widening flag on (``CLIP_STAGES``; ``--fusion`` as given), fed by ``scripts/clip_io.ClipInputs``
+    instead of the seeded stand-ins -- decoded frames, quads from dlib's landmarks (``quad_from_landmarks``), the source image, the
+    conditioning landmarks and ``uc = learnable_vector`` (:423).  A frame without landmarks takes the crop, label map and inverse
+    transform of the frame before it and zero conditioning landmarks, and is pasted into its own frame (:297-303).  Pasted
+    frames go to ``Base_dir/results/{index}.png`` (:636) unless ``--skip_save``, and to ``--video_out`` as YUV4MPEG2
+    (scripts/mux.py).  Where the landmarks file has no ``crops``, the conditioning landmarks are derived from the frame points;
+    that stands in for the reference's second detection on the crop and is not equal to it (scripts/clip_io.py).
+    Returns the record of ``run_synthetic``; every batch also carries ``frame_ids`` and, with ``opt.return_samples``,
+    ``pasted_frames``, ``crops`` and ``conditioning``."""
+    from .clip_io import ClipInputs
+    check_clip_options(opt)
+    clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
+    return _run_pipeline(opt, clip)
+
+
+def check_clip_options(opt):
+    """What a real-clip run needs on its command line, checked without a GPU; switches every stage of ``CLIP_STAGES`` on."""
+    for flag in ("target_frames", "src_image", "landmarks"):
+        if not getattr(opt, flag, None):
+            raise SystemExit(f"a real-clip run needs --{flag} (frames, source image and landmarks come from disk; dlib and the "
+                             "video decoder are outside this build, INTEGRATION.md), or run the seeded stand-ins with --synthetic")
+    ckpts = ("ckpt", "faceParsing_ckpt", "raft_ckpt")
+    if getattr(opt, "synthetic_weights", False):
+        given = [f for f in ckpts if getattr(opt, f, None)]
+        if given:
+            raise SystemExit(f"--synthetic_weights seeds every model: drop --{given[0]}")
+    else:
+        for flag in ckpts:
+            if not getattr(opt, flag, None):
+                raise SystemExit(f"a real-clip run needs --{flag} (or --synthetic_weights for a run on seeded weights)")
+    for name in CLIP_STAGES:
+        setattr(opt, name, True)
+    check_parse_options(opt)        # H x W other than 512 x 512 is refused: the parser's map
+
+
+def _run_pipeline(opt, clip) -> dict:
+    """``clip``: None = the seeded stand-ins of ``--synthetic``; a ``clip_io.ClipInputs`` = frames, quads, landmarks and source from
+    disk.  The stages are the same code either way."""
     from ..ldm.models.diffusion.ddim_w_inv import DDIMSampler, HookPlan
     from ..ldm.models.diffusion.ddpm import LatentDiffusion
     from ..utils import synth
@@ -333,6 +399,8 @@ def run_synthetic(opt) -> dict:
             synth.fill_module_(getattr(model, name), seed=5, prefix=name + ".")
         if arcface:
             synth.fill_arcface_(model.face_ID_model.facenet, seed=5, prefix="face_ID_model.facenet.")
+        if clip is not None:    # (read as `uc` below; a --synthetic run draws its `uc` per batch and leaves the module's own draw)
+            model.learnable_vector.data.copy_(synth.synth_normal("cli.learnable_vector", (1, 1, 768)))
     model = model.to(dev).eval()
     e_source, id_source = None, None
     if clip_cond and not source_intake:       # :437: the source image, resized and CLIP-normalised, is encoded once per clip and broadcast
@@ -353,7 +421,7 @@ def run_synthetic(opt) -> dict:
     F_ = opt.n_samples
     os.makedirs(opt.Base_dir, exist_ok=True)
     results, t_all = [], time.time()
-    paster, raft = None, None
+    paster, raft, writer = None, None, None
     intake = None
     if getattr(opt, "intake", False):
         from .intake import FrameIntake
@@ -366,10 +434,14 @@ def run_synthetic(opt) -> dict:
     source_state, source_seconds = None, None
     if source_intake:       # :254-355, :436-438, :462-468: once per clip; a seeded frame and quad stand in for the photo and dlib
         from .source import prepare_source
-        src_frames, src_quads, src_labels = synthetic_intake_inputs(1, opt.frame_size, opt.H, opt.W, opt.seed + 500)
-        src_lmk = synth.synth_normal("cli.landmarks_src", (1, 136)).to(dev) * 0.1 + 0.5
+        if clip is not None:    # the photo, its quad from dlib's points, its landmarks on the crop; the label map is the parser's
+            src_frames, src_quads, src_labels = clip.source_u8, clip.source_quad, None
+            src_lmk = torch.from_numpy(clip.source_landmarks).to(dev)
+        else:
+            src_frames, src_quads, src_labels = synthetic_intake_inputs(1, opt.frame_size, opt.H, opt.W, opt.seed + 500)
+            src_lmk = synth.synth_normal("cli.landmarks_src", (1, 136)).to(dev) * 0.1 + 0.5
         src_id = None if arcface else synth.synth_normal("cli.id_feat_src", (1, 512)).to(dev)
-        src_frames, src_labels = src_frames.to(dev), src_labels.to(dev)
+        src_frames, src_labels = src_frames.to(dev), None if src_labels is None else src_labels.to(dev)
         torch.cuda.synchronize()
         ts_ = time.time()
         src = intake.source(src_frames, src_quads, labels_u8=None if parser is not None else src_labels, parser=parser,
@@ -389,23 +461,39 @@ def run_synthetic(opt) -> dict:
         stages[name] = stages.get(name, 0.0) + time.time() - t_start
         return time.time()
 
+    carried = {}        # what a clip's batch hands to the next: the last frame's label map
+
     def prepare(batch_id):
         """Everything of a batch up to (not including) its DDIM inversion: conditioning, VAE encoding, flow."""
         nonlocal raft
         tag = lambda s: f"cli.{s}.{batch_id}"
         d = lambda t: t.to(dev)
         stages = {}
-        c, uc, tc = (d(synth.synth_normal(tag(k), (F_, 1, 768))) for k in ("c", "uc", "tc"))
-        img, frames, inv_tf, labels, inpaint_mask = None, None, None, None, None
+        img, frames, inv_tf, labels, inpaint_mask, crops, given = None, None, None, None, None, None, None
+        if clip is not None:    # :423 uc = learnable_vector per frame; c and tc come from the conditioning stage below
+            given = clip.batch(batch_id, F_)
+            uc = model.learnable_vector.detach().float().repeat(F_, 1, 1)
+            c = tc = None
+        else:
+            c, uc, tc = (d(synth.synth_normal(tag(k), (F_, 1, 768))) for k in ("c", "uc", "tc"))
         if intake is not None:
-            frames, quads, labels = synthetic_intake_inputs(F_, opt.frame_size, opt.H, opt.W, opt.seed + 1000 + batch_id)
-            frames, labels = d(frames), d(labels)
+            if given is not None:       # a frame without landmarks is cut with the quad, and from the pixels, of the frame it takes
+                frames, crop_frames, quads, labels = d(given["frames"]), d(given["crop_frames"]), given["quads"], None
+            else:
+                frames, quads, labels = synthetic_intake_inputs(F_, opt.frame_size, opt.H, opt.W, opt.seed + 1000 + batch_id)
+                frames, labels = d(frames), d(labels)
+                crop_frames = frames
             ts_ = stage(stages, "_", time.time())
             if parser is not None:      # :251, :292-294: the parser sees the aligned crop, the dataset reads its map
                 from .intake import inv_transforms
-                crops = intake.crop(frames, quads)
+                crops = intake.crop(crop_frames, quads)
                 ts_ = stage(stages, "intake", ts_)
                 labels = parser.labels(crops, convert_to_seg12=opt.seg12)
+                if given is not None:   # :297-303: no landmarks = the label map of the frame before, across a batch boundary too
+                    for f in range(F_):
+                        if not given["found"][f]:
+                            labels[f] = labels[f - 1] if f else carried["labels"]
+                    carried["labels"] = labels[-1].clone()
                 ts_ = stage(stages, "parse", ts_)
                 img, inpaint_image, inpaint_mask, mask = intake.tensors(crops, labels, REMOVE_MASK_TAR_FFHQ)
                 inv_tf = inv_transforms(quads, intake.image_size)
@@ -431,6 +519,8 @@ def run_synthetic(opt) -> dict:
             keep = inpaint_mask if inpaint_mask is not None else d(synth.synth_mask(F_, opt.H, opt.W))
             idf, idf_t = (d(synth.synth_normal(tag(k), (F_, 512))) for k in ("id_feat", "id_feat_tar"))
             lmk = d(synth.synth_normal(tag("landmarks"), (F_, 136)) * 0.1 + 0.5)
+            if given is not None:       # ddpm.py:1068-1099: the points on the crop, in pixels; zeros where no face was found
+                lmk = d(torch.from_numpy(given["landmarks"]))
             ts_ = stage(stages, "_", time.time())
             enc = model.cond_stage_model
             e_tar = enc.encode_from_frames(tar)
@@ -483,7 +573,7 @@ def run_synthetic(opt) -> dict:
                              inverse_dir=inv_store, batch_size=F_, test_model_kwargs=kw2, max_steps=opt.max_steps)
         return {"id": batch_id, "c": c, "uc": uc, "tc": tc, "z_inp": z_inp, "mask": mask, "flow": flow, "inv_store": inv_store,
                 "invert_kw": invert_kw, "inverted": invert_kw is None, "stages": stages, "frames": frames, "inv_transforms": inv_tf,
-                "labels": labels}
+                "labels": labels, "crops": crops, "frame_ids": None if given is None else given["frame_ids"]}
 
     def sample_kwargs(b):
         # :541 start code = the cached latent of the second-highest timestep ("ddim_latents_961.pt" at 50 steps)
@@ -539,8 +629,11 @@ def run_synthetic(opt) -> dict:
             from .paste_back import PasteBack
             if paster is None:
                 # (--precision autocast, the reference's default: its decoded tensor is float16 and :597-608 quantise in float16)
+                # (a clip from disk is rarely square: its background is resized to the frame's own (width, height), where :623
+                #  swaps the two and Pillow then refuses to compose; on square frames the two are the same bits)
                 paster = PasteBack(H=opt.H, W=opt.W, device=dev, encode_decode=PasteBack.vae_round_trip(model),
-                                   half_arithmetic=opt.precision == "autocast")
+                                   half_arithmetic=opt.precision == "autocast",
+                                   frame_size_order="reference" if clip is None else "width_height")
             if intake is not None:      # the frames the crops were cut from and the inverse of that cut (:68-71, :625)
                 frames, co = cur["frames"], cur["inv_transforms"]
             else:
@@ -557,7 +650,20 @@ def run_synthetic(opt) -> dict:
             torch.cuda.synchronize()
             paste_s = time.time() - t1
             stages["paste_back"] = paste_s
-        if not opt.skip_save:
+        if clip is not None:
+            if getattr(opt, "video_out", None):      # :646-654: yuv420p, BT.709, tv range, 10 fps; in frame order
+                if writer is None:
+                    from .mux import Y4MWriter
+                    writer = Y4MWriter(opt.video_out, pasted.shape[2], pasted.shape[1])
+                ts_ = stage(stages, "_", time.time())
+                writer.write(pasted)
+                stage(stages, "video_out", ts_)
+            if not opt.skip_save:
+                from PIL import Image
+                os.makedirs(os.path.join(opt.Base_dir, "results"), exist_ok=True)
+                for f, index in enumerate(cur["frame_ids"]):                                       # :636
+                    Image.fromarray(pasted[f].cpu().numpy()).save(os.path.join(opt.Base_dir, "results", f"{index}.png"))
+        elif not opt.skip_save:
             if pasted is not None:
                 from PIL import Image
                 for f in range(F_):                                                                # :636
@@ -574,9 +680,15 @@ def run_synthetic(opt) -> dict:
                         "pixels": None if pixels is None else list(pixels.shape),
                         "pasted": None if pasted is None else list(pasted.shape), "paste_seconds": paste_s,
                         "stage_seconds": {k: v for k, v in stages.items() if k != "_"}})
+        if clip is not None:
+            keep = bool(getattr(opt, "return_samples", False))
+            results[-1].update(frame_ids=list(cur["frame_ids"]), pasted_frames=pasted if keep else None,
+                               crops=cur["crops"] if keep else None, conditioning=cur["c"] if keep else None)
         print(f"batch {batch_id}: {F_} frames sampled in {dt_s:.2f} s")
         t_batch = time.time()
         cur = nxt if nxt is not None else (prepare(batch_id + 1) if batch_id + 1 < nbatches else None)
+    if writer is not None:
+        writer.close()
     return {"batches": results, "total_seconds": time.time() - t_all}
 
 
@@ -585,11 +697,11 @@ def main(argv=None):
     torch.manual_seed(opt.seed)  # seed_everything(42) (:862)
     if opt.plms:
         raise NotImplementedError("--plms selects PLMSSampler, which is outside the VFace hot path (SURVEY §2)")
-    if not opt.synthetic:
-        sys.exit("Only the denoising hot path is built here.  Video decoding, dlib/BiSeNet pre-processing, CLIP/ArcFace "
-                 "conditioning and paste-back (VFace_inference_batch.py:193-528,603-670) need checkpoints "
-                 "that are not available offline; run with --synthetic, or feed real latents through "
-                 "vface_amd.ldm.models.diffusion.ddim_w_inv.DDIMSampler (see INTEGRATION.md).")
+    if not opt.synthetic:       # a clip from disk; its arguments are checked before the GPU is asked for
+        check_clip_options(opt)
+        if not torch.cuda.is_available():
+            sys.exit("An MI355X is required: the VFace hot path has no CPU fallback.")
+        return run_clip(opt)
     check_parse_options(opt)
     check_source_options(opt)
     if not torch.cuda.is_available():

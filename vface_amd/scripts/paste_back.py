@@ -35,12 +35,19 @@ class PasteBack:
     ``[F, 3, H, W] fp32 in [-1, 1] -> decoded [F, 3, H, W]`` (``PasteBack.vae_round_trip(model)`` builds it from a
     ``LatentDiffusion`` with a first stage); ``None`` pastes over the untouched original frame instead (no VAE built).
     ``half_arithmetic``: quantise float16 decoder outputs with float16 arithmetic, as the reference's default
-    ``--precision autocast`` run does (``hip.frame_to_u8``); the default is the fp32 arithmetic of ``--precision full``."""
+    ``--precision autocast`` run does (``hip.frame_to_u8``); the default is the fp32 arithmetic of ``--precision full``.
+    ``frame_size_order``: ``"reference"`` resizes the round-tripped background to (orig height, orig width) as :623 does, so only
+    square frames compose; ``"width_height"`` resizes it to the frame's own (width, height) -- the same bits on a square frame,
+    and the only way a 1920 x 1080 clip runs at all (the real-clip run of the command line asks for it)."""
 
     def __init__(self, H: int = 512, W: int = 512, canvas: int = 1024, device="cuda:0",
-                 encode_decode: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, half_arithmetic: bool = False):
+                 encode_decode: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, half_arithmetic: bool = False,
+                 frame_size_order: str = "reference"):
+        if frame_size_order not in ("reference", "width_height"):
+            raise ValueError(f"frame_size_order: reference | width_height; got {frame_size_order!r}")
         self.H, self.W, self.canvas = H, W, canvas
         self.half_arithmetic = half_arithmetic
+        self.frame_size_order = frame_size_order
         self.device = torch.device(device)
         self.encode_decode = encode_decode
         self._tables: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -86,6 +93,8 @@ class PasteBack:
             return frames_u8.clone()
         x = hip.frame_normalise_resize(frames_u8, self.H, self.W)
         rec = self.encode_decode(x)
+        if self.frame_size_order == "width_height":
+            return self.resize_u8(self._to_u8(rec), Wo, Ho)
         out = self.resize_u8(self._to_u8(rec), Ho, Wo)      # (width, height) := (orig height, orig width), :623
         if tuple(out.shape[1:3]) != (Ho, Wo):
             raise ValueError("images do not match")
