@@ -23,7 +23,8 @@ def small_cfg():
 
 @pytest.fixture(scope="module")
 def clip(tmp_path_factory):
-    """The clip on disk (written once) and three runs of it: twice as it is, once with a landmarks file without `crops`."""
+    """The clip on disk (written once) and four runs of it: twice as it is, once with a landmarks file without `crops`, once with
+    `--pipeline_inversion`."""
     import yaml
     from vface_amd.scripts import VFace_inference_batch as cli
     root = tmp_path_factory.mktemp("clip")
@@ -43,17 +44,18 @@ def clip(tmp_path_factory):
     np.savez(root / "lm_nocrops.npz", frames=lm, source=src_lm)
     (root / "small.yaml").write_text(yaml.safe_dump({"model": {"params": {"unet_config": {"params": small_cfg()}}}}))
 
-    def run(tag, landmarks="lm.npz"):
+    def run(tag, landmarks="lm.npz", more=()):
         args = ["--target_frames", str(root / "frames"), "--src_image", str(root / "src.png"), "--landmarks", str(root / landmarks),
                 "--video_out", str(root / f"{tag}.y4m"), "--synthetic_weights", "--config", str(root / "small.yaml"),
                 "--H", "512", "--W", "512", "--max_steps", "1", "--ddim_steps", "50", "--n_frames", str(N), "--n_samples", "2",
-                "--Base_dir", str(root / tag)]
+                "--Base_dir", str(root / tag), *more]
         opt = cli.build_parser().parse_args(args)
         opt.return_samples = True
         torch.manual_seed(opt.seed)
         return cli.run_clip(opt)["batches"]
 
-    return {"root": root, "frames": frames, "quads": quads, "a": run("a"), "b": run("b"), "nocrops": run("c", "lm_nocrops.npz")}
+    return {"root": root, "frames": frames, "quads": quads, "a": run("a"), "b": run("b"), "nocrops": run("c", "lm_nocrops.npz"),
+            "pipelined": run("d", more=["--pipeline_inversion"])}
 
 
 def cat(batches, key):
@@ -73,6 +75,15 @@ def test_clip_run_is_complete_and_repeatable(clip):
     pasted = cat(a, "pasted_frames")
     assert pasted.dtype == torch.uint8 and tuple(pasted.shape) == (N, FH, FW, 3)
     assert not torch.equal(pasted, torch.from_numpy(clip["frames"]).to(DEV))
+
+
+def test_pipelined_inversion_gives_the_same_clip(clip):
+    """Two batches with the frame without landmarks on the boundary: batch 1 is prepared -- its label map inherited -- before batch
+    0 is sampled, and every tensor equals the sequential run's."""
+    a, p = clip["a"], clip["pipelined"]
+    assert ["sampling_beside_next_inversion" in x["stage_seconds"] for x in p] == [True, False] and "next_parse" in p[0]["stage_seconds"]
+    for key in ("samples", "pasted_frames", "crops", "labels", "conditioning"):
+        assert torch.equal(cat(a, key), cat(p, key)), key
 
 
 def test_outputs_on_disk_are_the_pasted_frames(clip):

@@ -48,7 +48,7 @@ def main():
     from vface_amd.raft import RAFT
     from vface_amd.scripts import temporal_flow as tflow
     from vface_amd.scripts.paste_back import PasteBack
-    from vface_amd.scripts.VFace_inference_batch import _quad_coeffs
+    from vface_amd.scripts.inputs import _quad_coeffs
     raft = RAFT()
     synth.fill_module_(raft, seed=0, prefix="raft.")
     raft = raft.to(DEV).eval()
@@ -158,7 +158,7 @@ def bench_intake(F_, R, image_size=1024, Hs=1080, Ws=1920):
     from PIL import Image
     from vface_amd import hip
     from vface_amd.scripts.intake import FrameIntake, crop_plan
-    from vface_amd.scripts.VFace_inference_batch import REMOVE_MASK_TAR_FFHQ
+    from vface_amd.scripts.intake import REMOVE_MASK_TAR_FFHQ
     S, lat = image_size, (R // 8, R // 8)
     frames = torch.randint(0, 256, (F_, Hs, Ws, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(1)).to(DEV)
     labels = torch.randint(0, 19, (F_, R, R), dtype=torch.uint8, generator=torch.Generator().manual_seed(2)).to(DEV)

@@ -1,0 +1,196 @@
+"""What a run's stages are fed, batch by batch: two providers with one interface (``scripts/pipeline.py`` asks, never looks at
+which of the two it was handed).
+
+``SeededInputs`` is the ``--synthetic`` run: seeded stand-ins for everything a stage that is switched off would have made, and for
+what video decoding, dlib and the source photo hand to the stages that are on.  ``ClipRunInputs`` is a clip from disk
+(``clip_io.ClipInputs``): frames, quads, landmarks and source from files; every stage is on, so it has no stand-ins.
+
+The questions, for batch ``k`` of ``F = --n_samples`` frames (tensors on the provider's device unless stated):
+
+    frame_ids(k)            the clip's frame indices, or None (the record and the PNG names)
+    tokens(k)               c, uc, tc [F, 1, 768]; None = made by the conditioning stage (uc: the model's learnable_vector)
+    intake_frames(k)        frames to paste into, frames to crop from, quads [F, 4, 2] (host), label maps or None = ask the parser
+    inherits(k)             per frame: does it take the label map of the frame before (no landmarks, :297-303)?
+    carry_labels(k, maps)   the label maps with the inherited ones put in; remembers batch k's last map for batch k + 1
+    landmarks(k)            conditioning landmarks [F, 136]
+    source()                source frame [1, Hs, Ws, 3], quad (host), label map or None, landmarks [1, 136], identity features or None
+    learnable_vector()      a seeded value for the model's learnable_vector on seeded weights, or None = leave the module's own
+
+and, where a stage is off (seeded only): ``images`` ``latents`` ``latent_mask`` ``keep_mask`` ``id_feats`` ``flow``
+``inversion_cache`` ``inversion_latents`` ``paste_target`` ``source_clip_image``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..utils import synth
+
+
+def _quad_coeffs(size, quad):
+    """Eight PIL perspective coefficients (output pixel -> crop coordinates) that land the ``size`` x ``size`` crop on ``quad``
+    (four frame-space corners, clockwise from top-left) -- what ``crop_and_align_face`` (:58-73) stores per frame."""
+    src = [(0, 0), (size, 0), (size, size), (0, size)]
+    A, B = [], []
+    for (x, y), (u, v) in zip(quad, src):
+        A += [[x, y, 1, 0, 0, 0, -u * x, -u * y], [0, 0, 0, x, y, 1, -v * x, -v * y]]
+        B += [u, v]
+    return np.linalg.solve(np.array(A, float), np.array(B, float))
+
+
+def synthetic_intake_inputs(F_: int, S_: int, H: int, W: int, seed: int):
+    """Stand-ins for what video decoding, landmark detection and face parsing hand to the intake: seeded uint8 frames
+    [F, S, S, 3], one quad [4, 2] per frame (NW, SW, SE, NE; half the frame wide, rotating and drifting from frame to frame, the
+    first one partly outside the frame) and a label map [F, H, W] with the parser's values 0..18 in rings round the centre."""
+    gen = torch.Generator().manual_seed(seed)
+    frames = torch.randint(0, 256, (F_, S_, S_, 3), dtype=torch.uint8, generator=gen)
+    quads = np.empty((F_, 4, 2), np.float64)
+    for f in range(F_):
+        c = np.array([S_ * (0.15 if f == 0 else 0.5) + 3.0 * f, S_ * 0.5 + 2.0 * f])
+        th = 0.05 * (f + 1)
+        x = S_ / 4.0 * np.array([np.cos(th), np.sin(th)])
+        y = np.flipud(x) * [-1, 1]
+        quads[f] = np.stack([c - x - y, c - x + y, c + x + y, c + x - y])
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+    r = torch.hypot((ys - (H - 1) / 2) / (0.5 * H), (xs - (W - 1) / 2) / (0.5 * W))
+    labels = torch.stack([((r * 12).long() + f) % 19 for f in range(F_)]).to(torch.uint8)
+    return frames, quads, labels
+
+
+class SeededInputs:
+    """The stand-ins of ``--synthetic``.  Every draw is a function of its tag (``cli.{name}.{k}``) or seed alone, so the order in
+    which a run asks is free."""
+    frame_size_order = "reference"      # (PasteBack: :623 as written; the seeded frames are square)
+    record_keys = ()                    # a batch's record carries no key beyond the common ones
+
+    def __init__(self, opt, device):
+        self.opt, self.device, self.F = opt, torch.device(device), opt.n_samples
+        self.h, self.w = opt.H // opt.f, opt.W // opt.f
+
+    def _normal(self, k, name, shape):
+        return synth.synth_normal(f"cli.{name}.{k}", shape).to(self.device)
+
+    def frame_ids(self, k):
+        return None
+
+    def tokens(self, k):
+        return tuple(self._normal(k, name, (self.F, 1, 768)) for name in ("c", "uc", "tc"))
+
+    def intake_frames(self, k):
+        o = self.opt
+        frames, quads, labels = synthetic_intake_inputs(self.F, o.frame_size, o.H, o.W, o.seed + 1000 + k)
+        frames = frames.to(self.device)
+        return frames, frames, quads, labels.to(self.device)
+
+    def inherits(self, k):
+        return [False] * self.F
+
+    def carry_labels(self, k, labels):
+        return labels
+
+    def landmarks(self, k):
+        return (synth.synth_normal(f"cli.landmarks.{k}", (self.F, 136)) * 0.1 + 0.5).to(self.device)
+
+    def source(self):
+        o = self.opt
+        frames, quads, labels = synthetic_intake_inputs(1, o.frame_size, o.H, o.W, o.seed + 500)
+        lmk = synth.synth_normal("cli.landmarks_src", (1, 136)).to(self.device) * 0.1 + 0.5
+        idf = None if o.arcface else synth.synth_normal("cli.id_feat_src", (1, 512)).to(self.device)
+        return frames.to(self.device), quads, labels.to(self.device), lmk, idf
+
+    def learnable_vector(self):
+        return None     # (a seeded run draws its `uc` per batch)
+
+    # ---- stand-ins for the products of stages that are off
+    def images(self, k):
+        o = self.opt
+        return torch.stack([synth.synth_normal(f"cli.img{f}.{k}", (3, o.H, o.W)).clamp(-1, 1) for f in range(self.F)]).to(self.device)
+
+    def latents(self, k):
+        return (synth.synth_normal(f"cli.inp.{k}", (self.F, self.opt.C, self.h, self.w)) * 0.18215).to(self.device)
+
+    def latent_mask(self, k):
+        return synth.synth_mask(self.F, self.h, self.w).to(self.device)
+
+    def keep_mask(self, k):
+        return synth.synth_mask(self.F, self.opt.H, self.opt.W).to(self.device)
+
+    def id_feats(self, k):
+        return tuple(self._normal(k, name, (self.F, 512)) for name in ("id_feat", "id_feat_tar"))
+
+    def flow(self, k):
+        """A host field per frame pair; with ``--flow_pixels`` at pixel resolution, its latent resample a +-2-cell motion."""
+        o = self.opt
+        if o.flow_pixels:
+            return [f[None] * o.f for f in synth.synth_flow(self.F - 1, o.H, o.W, seed=o.seed + k)]
+        return [f[None] for f in synth.synth_flow(self.F - 1, self.h, self.w, seed=o.seed + k)]
+
+    def inversion_cache(self, k, timesteps):
+        return {int(s): self._normal(k, f"inv{int(s)}", (self.F, self.opt.C, self.h, self.w)) for s in timesteps}
+
+    def inversion_latents(self, k):
+        return self._normal(k, "z2", (2 * self.F, self.opt.C, self.h, self.w))
+
+    def paste_target(self, k, canvas):
+        """Original frames and ``inv_transforms_all`` rows (:625) where no intake made them: the ``canvas`` lands on the central
+        half of the frame, slightly sheared."""
+        S_ = self.opt.frame_size
+        gen = torch.Generator().manual_seed(self.opt.seed + 1000 + k)
+        frames = torch.randint(0, 256, (self.F, S_, S_, 3), dtype=torch.uint8, generator=gen).to(self.device)
+        q = S_ / 4.0
+        return frames, [_quad_coeffs(canvas, [(q + 3 * f, q), (3 * q, q + f), (3 * q - f, 3 * q), (q, 3 * q - 2 * f)])
+                        for f in range(self.F)]
+
+    def source_clip_image(self):
+        return synth.synth_normal("cli.source224", (1, 3, 224, 224)).to(self.device)
+
+
+class ClipRunInputs:
+    """A ``clip_io.ClipInputs`` behind the same questions.  A frame without landmarks is cut with the quad, and from the pixels, of
+    the frame it takes (``clip_io.fallback_indices``), inherits that frame's label map -- across a batch boundary too, which is
+    the one thing this object carries from batch to batch -- and has zero conditioning landmarks."""
+    frame_size_order = "width_height"   # (a clip is rarely square: paste_back.PasteBack)
+    record_keys = ("frame_ids", "pasted_frames", "crops", "conditioning")
+
+    def __init__(self, clip, opt, device):
+        self.clip, self.device, self.F = clip, torch.device(device), opt.n_samples
+        self._last_labels = {}      # batch id -> its last frame's label map, for the first frame of the batch after it
+
+    def _rows(self, k):
+        return slice(k * self.F, (k + 1) * self.F)
+
+    def frame_ids(self, k):
+        return list(self.clip.frame_ids[self._rows(k)])
+
+    def tokens(self, k):
+        return None, None, None     # :423 uc = learnable_vector; c and tc come from the conditioning stage
+
+    def intake_frames(self, k):
+        given = self.clip.batch(k, self.F)
+        return given["frames"].to(self.device), given["crop_frames"].to(self.device), given["quads"], None
+
+    def inherits(self, k):
+        return [not bool(found) for found in self.clip.found[self._rows(k)]]
+
+    def carry_labels(self, k, labels):
+        for f, inherited in enumerate(self.inherits(k)):
+            if inherited:
+                labels[f] = labels[f - 1] if f else self._last_labels[k - 1]
+        self._last_labels = {k: labels[-1].clone()}
+        return labels
+
+    def landmarks(self, k):     # ddpm.py:1068-1099: the points on the crop, in pixels; zeros where no face was found
+        return torch.from_numpy(self.clip.landmarks[self._rows(k)]).to(self.device)
+
+    def source(self):           # the photo, its quad from dlib's points, its landmarks on the crop; the label map is the parser's
+        c = self.clip
+        return c.source_u8.to(self.device), c.source_quad, None, torch.from_numpy(c.source_landmarks).to(self.device), None
+
+    def learnable_vector(self):
+        return synth.synth_normal("cli.learnable_vector", (1, 1, 768))
+
+    def _no_stand_in(self, *a):
+        raise RuntimeError("a clip from disk runs every stage (CLIP_STAGES): there is no stand-in for a stage's product")
+
+    images = latents = latent_mask = keep_mask = id_feats = flow = _no_stand_in
+    inversion_cache = inversion_latents = paste_target = source_clip_image = _no_stand_in

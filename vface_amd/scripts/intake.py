@@ -30,7 +30,9 @@ import torch
 
 from .. import hip
 from .resample import linear_taps_u8, resample_coeffs
-from .VFace_inference_batch import PRESERVE_MASK_SRC_FFHQ
+
+REMOVE_MASK_TAR_FFHQ = (1, 2, 3, 5, 6, 7, 9)      # models/REFace/configs/project_ffhq.yaml: remove_mask_tar_FFHQ
+PRESERVE_MASK_SRC_FFHQ = (1, 2, 3, 5, 6, 7, 9)    # project_ffhq.yaml:217-224: preserve_mask_src_FFHQ (the source's face region)
 
 
 class SourceTensors(NamedTuple):

@@ -1,0 +1,60 @@
+"""Where a finished batch goes: one object per run with ``write(batch)`` and ``close()``.  ``batch`` is the loop's state of the
+batch (``scripts/pipeline.py`` ``Batch``): ``samples``, ``pixels``, ``pasted``, ``frame_ids`` and its stage timer."""
+from __future__ import annotations
+
+import os
+
+import torch
+
+
+def _save_png(frame_u8, path):
+    from PIL import Image
+    Image.fromarray(frame_u8.cpu().numpy()).save(path)                                             # :636
+
+
+class SeededOutputs:
+    """``--synthetic``: ``samples_batch{k}.pt``, ``pixels_batch{k}.pt`` and ``pasted_b{k}_f{f}.png`` under ``--Base_dir``,
+    nothing with ``--skip_save``."""
+
+    def __init__(self, opt):
+        self.dir, self.save = opt.Base_dir, not opt.skip_save
+        os.makedirs(self.dir, exist_ok=True)
+
+    def write(self, b):
+        if not self.save:
+            return
+        if b.pasted is not None:
+            for f in range(b.pasted.shape[0]):
+                _save_png(b.pasted[f], os.path.join(self.dir, f"pasted_b{b.id}_f{f}.png"))
+        torch.save(b.samples.cpu(), os.path.join(self.dir, f"samples_batch{b.id}.pt"))
+        if b.pixels is not None:
+            torch.save(b.pixels.cpu(), os.path.join(self.dir, f"pixels_batch{b.id}.pt"))
+
+    def close(self):
+        pass
+
+
+class ClipOutputs:
+    """A clip from disk: the pasted frames as ``Base_dir/results/{index}.png`` (:636) unless ``--skip_save`` and, with
+    ``--video_out``, as YUV4MPEG2 in frame order (:646-654: yuv420p, BT.709, tv range, 10 fps; scripts/mux.py), the batch's
+    ``video_out`` stage.  The file is opened by the first batch, whose frames give its size."""
+
+    def __init__(self, opt):
+        self.dir, self.save, self.video_out, self.writer = opt.Base_dir, not opt.skip_save, opt.video_out, None
+        os.makedirs(self.dir, exist_ok=True)
+
+    def write(self, b):
+        if self.video_out:
+            if self.writer is None:
+                from .mux import Y4MWriter
+                self.writer = Y4MWriter(self.video_out, b.pasted.shape[2], b.pasted.shape[1])
+            with b.timer("video_out"):
+                self.writer.write(b.pasted)
+        if self.save:
+            os.makedirs(os.path.join(self.dir, "results"), exist_ok=True)
+            for f, index in enumerate(b.frame_ids):
+                _save_png(b.pasted[f], os.path.join(self.dir, "results", f"{index}.png"))
+
+    def close(self):
+        if self.writer is not None:
+            self.writer.close()
