@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VFACE_ABI_VERSION 8   /* 8 (later additions, nothing changed): + vface_clip_patches, vface_clip_embed, vface_act, vface_cond_mix (the conditioning stage) and vface_attention at dh = 64; 8: 7 minus the composite hooked-attn1 call and its workspace query (a hooked attn1 is a sequence of single-kernel calls issued by the caller), nothing else changed; 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
+#define VFACE_ABI_VERSION 8   /* 8 (later additions, nothing changed): + vface_clip_patches, vface_clip_embed, vface_act, vface_cond_mix (the conditioning stage), vface_attention at dh = 64 and vface_yuv420_to_rgb (video in); 8: 7 minus the composite hooked-attn1 call and its workspace query (a hooked attn1 is a sequence of single-kernel calls issued by the caller), nothing else changed; 7 (later additions, nothing changed): + vface_temporal_gauss_halo, vface_adain_rows_workspace_bytes, vface_adain_rows, vface_adain_reduce_scale (the frame-sharded temporal / adaIn edits); 7: + the VFACE_TUNE_BIG_W256 / VFACE_TUNE_BIG_W320 flag bits of vface_gemm (the big tile's width: 256 x 256 beside 256 x 320, chosen by the library per launch; same results), nothing else of 6 changed; 6: + the VFACE_TUNE_BIG_TILE / VFACE_TUNE_NO_BIG_TILE flag bits of vface_gemm (csrc/gemm_big.hip: the 256 x 320 tile, chosen by the library from 192 tiles on; same results), nothing else of 5 changed; 5: + vface_st_front, vface_attn_out_ffn_fused, vface_attn_out_ffn_proj_fused, vface_gn_silu_conv3x3_small, vface_linear_small; vface_attention's v_sets carries the live-set count in bits 8..15, vface_pack_unet_input / vface_ddim_step take the two-branch batch; nothing else of 4 changed (4: + vface_ffn_fused, the flow-producer glue, the paste-back entry points) */
 
 #define VFACE_OK 0
 #define VFACE_ERR_ARG (-1)
@@ -314,6 +314,24 @@ int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out,
  *   may be odd; no alignment is required of either pointer or of frame_stride.
  *   NULL pointer, W, H or frames <= 0: VFACE_ERR_ARG; frame_stride < W * H + 2 * cw * ch: VFACE_ERR_SHAPE -- before the first HIP call. */
 int vface_rgb_to_yuv420(const uint8_t* rgb, int W, int H, uint8_t* out, int64_t frame_stride, int frames, void* stream);
+
+/* ---- video in, colour half (REFace/scripts/VFace_inference_batch.py:240-285) --------------------------------------------------
+ * The reference decodes the target video on the host (cv2.VideoCapture, BGR -> RGB, PNG per frame, :240-285).  The H.264 decoder
+ * is not built here either; vface_amd/scripts/demux.py reads the YUV4MPEG2 file any decoder writes (`ffmpeg -i in.mp4 clip.y4m`),
+ * the host uploads the I420 planes -- 1.5 bytes per pixel instead of 3 -- and vface_yuv420_to_rgb makes the 8-bit RGB frames on
+ * the device: the inverse direction of vface_rgb_to_yuv420, same frame layout.
+ *   i420: frame f at i420 + f * frame_stride: Y [H][W], Cb [ch][cw], Cr [ch][cw], cw = (W + 1) / 2, ch = (H + 1) / 2; bytes
+ *   between frames are not read -> rgb [frames][H][W][3], dense.
+ *   matrix: 0 = BT.709, 1 = BT.601 (Y4M cannot tag it); full_range: 0 = limited (`tv`: Y offset 16, scales 255/219 and 255/224),
+ *   1 = full; chroma: 0 = nearest, 1 = centre-sited (C420jpeg; what vface_rgb_to_yuv420 writes), 2 = left (C420mpeg2: horizontally
+ *   co-sited, vertically centred) -- the chroma of a pixel is the weighted sum of its four neighbouring samples in sixteenths,
+ *   neighbour indices clamped into the plane.
+ *   Integer arithmetic, stated once in tests/demux_model.py and equal to it bit for bit: 16-bit coefficients, one half-up rounding,
+ *   then the clamp to 0..255.  W and H may be odd; no alignment is required of either pointer or of frame_stride.
+ *   NULL pointer, W, H or frames <= 0, matrix / full_range / chroma outside their values: VFACE_ERR_ARG; frame_stride <
+ *   W * H + 2 * cw * ch, or more than 2^31 - 1 strips of 2 rows x 16 pixels in all: VFACE_ERR_SHAPE -- before the first HIP call. */
+int vface_yuv420_to_rgb(const uint8_t* i420, int64_t frame_stride, int W, int H, int frames, uint8_t* rgb, int matrix,
+                        int full_range, int chroma, void* stream);
 
 /* ---- frame intake: decoded frame -> aligned crop -> the sampler's tensors (the mirror image of the paste-back) ---------------
  * The reference runs these steps per frame on the host with Pillow and numpy.  The Lanczos shrink of a large face

@@ -83,6 +83,7 @@ SIGNATURES = {
     "vface_perspective_paste": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_frame_normalise_resize": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_rgb_to_yuv420": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _i32, _vp]),
+    "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vface_source_tensors": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
@@ -544,6 +545,41 @@ def rgb_to_yuv420(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -
                             f"row stride >= {n}")
     stride = out.stride(0) if F_ > 1 else max(out.stride(0), n)
     _check(load().vface_rgb_to_yuv420(_p(frames_u8), W, H, _p(out), stride, F_, _stream()), "vface_rgb_to_yuv420")
+    return out
+
+
+YUV_MATRICES = {"bt709": 0, "bt601": 1}
+YUV_CHROMA = {"nearest": 0, "centre": 1, "left": 2}
+
+
+def yuv420_to_rgb(i420: torch.Tensor, W: int, H: int, matrix: str = "bt709", full_range: bool = False, chroma: str = "centre",
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """I420 frames, device uint8 [F, n >= frame_bytes] rows (Y [H][W], Cb [ch][cw], Cr [ch][cw]; a view with a row stride is fine,
+    the bytes past frame_bytes are not read) -> uint8 [F, H, W, 3] RGB: the inverse direction of ``rgb_to_yuv420``, the integer
+    arithmetic of ``tests/demux_model.py`` bit for bit (csrc/demux.hip).  ``matrix``: bt709 | bt601; ``full_range``: limited (tv)
+    or full; ``chroma``: nearest | centre (C420jpeg, what ``rgb_to_yuv420`` writes) | left (C420mpeg2).  ``out``: a contiguous
+    uint8 [F, H, W, 3] tensor on the frames' device."""
+    if matrix not in YUV_MATRICES:
+        raise VFaceHipError(f"yuv420_to_rgb: matrix is one of {sorted(YUV_MATRICES)}; got {matrix!r}")
+    if chroma not in YUV_CHROMA:
+        raise VFaceHipError(f"yuv420_to_rgb: chroma is one of {sorted(YUV_CHROMA)}; got {chroma!r}")
+    W, H = int(W), int(H)
+    if not isinstance(i420, torch.Tensor) or i420.dtype != torch.uint8 or i420.dim() != 2:
+        raise VFaceHipError("yuv420_to_rgb: frames must be uint8 [F, >= frame_bytes] rows")
+    F_ = i420.shape[0]
+    if min(F_, H, W) <= 0:
+        raise VFaceHipError("yuv420_to_rgb: F, H and W must be positive")
+    n = i420_frame_bytes(W, H)
+    if i420.shape[1] < n or i420.stride(1) != 1 or (F_ > 1 and i420.stride(0) < n):
+        raise VFaceHipError(f"yuv420_to_rgb: a {W} x {H} I420 frame is {n} bytes; frames must be rows of at least that many bytes with "
+                            f"unit column stride, row stride >= {n}; got {tuple(i420.shape)}, strides {tuple(i420.stride())}")
+    if out is None:
+        out = torch.empty(F_, H, W, 3, dtype=torch.uint8, device=i420.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F_, H, W, 3) or not out.is_contiguous() or out.device != i420.device:
+        raise VFaceHipError(f"yuv420_to_rgb: out must be a contiguous uint8 {[F_, H, W, 3]} tensor on the frames' device")
+    stride = i420.stride(0) if F_ > 1 else max(i420.stride(0), n)
+    _check(load().vface_yuv420_to_rgb(_p(i420), stride, W, H, F_, _p(out), YUV_MATRICES[matrix], int(bool(full_range)),
+                                      YUV_CHROMA[chroma], _stream()), "vface_yuv420_to_rgb")
     return out
 
 

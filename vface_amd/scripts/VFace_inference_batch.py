@@ -11,12 +11,17 @@ stand-in each by the stage itself on the GPU (synthetic weights unless ``--ckpt`
     python -m vface_amd.scripts.VFace_inference_batch --synthetic --n_frames 24 --n_samples 8 --ddim_steps 50
 
 Without ``--synthetic`` the run is a real clip's (``run_clip``): every one of those stages, on frames, a source image and a
-landmarks file from disk (``scripts/clip_io.py``; dlib and the video decoder stay outside, so the ``{index}.png`` frames the
-reference writes at ``:285`` and dlib's 68 points are inputs), the pasted frames out as PNG (``:636``) and, with ``--video_out``, as
-a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps (``:646-654``; ``scripts/mux.py``).  H.264 and
-audio are not built.
+landmarks file from disk (``scripts/clip_io.py``; dlib and the H.264 decoder stay outside, so dlib's 68 points and the decoded clip
+are inputs: the ``{index}.png`` frames the reference writes at ``:285``, or -- ``--target_video`` -- the YUV4MPEG2 file any decoder
+writes, whose I420 planes are uploaded and converted to RGB on the GPU, ``scripts/demux.py``, csrc/demux.hip), the pasted frames out
+as PNG (``:636``) and, with ``--video_out``, as a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps
+(``:646-654``; ``scripts/mux.py``).  H.264 and audio are not built.
 
     python -m vface_amd.scripts.VFace_inference_batch --target_frames clip/ --src_image src.png --landmarks clip.npz \\
+        --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.y4m
+
+    ffmpeg -i in.mp4 -pix_fmt yuv420p clip.y4m
+    python -m vface_amd.scripts.VFace_inference_batch --target_video clip.y4m --src_image src.png --landmarks clip.npz \\
         --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.y4m
 
 This module is the command line and nothing else: the flags (``build_parser``), their normalisation and every dependency between
@@ -82,6 +87,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--target_frames", type=str, default=None,
                    help="real-clip run: folder of the target clip's frames, {index}.png (or .jpg) as the reference writes them (:285); "
                         "taken in the order of the integer index, the first --n_frames of them")
+    p.add_argument("--target_video", type=str, default=None,
+                   help="real-clip run: the target clip as a YUV4MPEG2 file instead of --target_frames (`ffmpeg -i in.mp4 -pix_fmt yuv420p "
+                        "clip.y4m`; 8-bit progressive 4:2:0, scripts/demux.py): the I420 planes are uploaded, 1.5 bytes per pixel, and "
+                        "converted to RGB on the GPU (csrc/demux.hip); frame ids 0 .. --n_frames - 1")
+    p.add_argument("--video_in_matrix", choices=["bt709", "bt601"], default=None,
+                   help="with --target_video: the matrix of the file, which Y4M cannot tag.  Default bt709: what --video_out writes and "
+                        "HD material carries; bt601 is what an untagged swscale conversion uses")
+    p.add_argument("--chroma_upsample", choices=["sited", "nearest"], default=None,
+                   help="with --target_video: sited (default) = interpolate the chroma where the header says its samples sit "
+                        "(C420jpeg: centre; C420mpeg2: left); nearest = repeat each sample over its 2 x 2 block")
     p.add_argument("--src_image", type=str, default=None, help="real-clip run: the source image (the identity to put in)")
     p.add_argument("--landmarks", type=str, default=None,
                    help="real-clip run: .npz with dlib's 68 points, which this build does not compute -- frames [N, 68, 2] (a NaN row = "
@@ -208,8 +223,11 @@ def check_clip_options(opt):
     """What a real-clip run needs on its command line, checked without a GPU; switches every stage of ``CLIP_STAGES`` on (in
     ``opt`` itself)."""
     given = normalise_options(opt)
+    check_video_in_options(given)
+    if given.target_video and given.target_frames:
+        raise SystemExit("--target_video and --target_frames both name the target clip: give one of them")
     for flag in ("target_frames", "src_image", "landmarks"):
-        if not vars(given)[flag]:
+        if not vars(given)[flag] and not (flag == "target_frames" and given.target_video):
             raise SystemExit(f"a real-clip run needs --{flag} (frames, source image and landmarks come from disk; dlib and the "
                              "video decoder are outside this build, INTEGRATION.md), or run the seeded stand-ins with --synthetic")
     for flag in ("ckpt", "faceParsing_ckpt", "raft_ckpt"):
@@ -222,9 +240,18 @@ def check_clip_options(opt):
     check_parse_options(opt)        # H x W other than 512 x 512 is refused: the parser's map
 
 
+def check_video_in_options(opt):
+    """--video_in_matrix and --chroma_upsample say how --target_video is read: without it they would be ignored, so they are refused."""
+    opt = normalise_options(opt)
+    for flag in ("video_in_matrix", "chroma_upsample"):
+        if vars(opt)[flag] is not None and not opt.target_video:
+            raise SystemExit(f"--{flag} says how --target_video is converted: it needs --target_video FILE.y4m")
+
+
 def check_options(opt):
     """Every dependency between flags, on normalised options, before anything is built.  Without ``--synthetic`` the run is a
     clip's: its files and checkpoints are asked for and every stage is switched on."""
+    check_video_in_options(opt)
     if not opt.synthetic:
         check_clip_options(opt)
     if opt.intake and not opt.with_vae:
@@ -254,7 +281,11 @@ def _run(opt) -> dict:
         inputs, sink_type = providers.SeededInputs(opt, dev), outputs.SeededOutputs
     else:
         from .clip_io import ClipInputs
-        clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
+        if opt.target_video:
+            from .demux import Y4MReader
+            clip = ClipInputs.from_video(Y4MReader(opt.target_video), opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
+        else:
+            clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         inputs, sink_type = providers.ClipRunInputs(clip, opt, dev), outputs.ClipOutputs
     run = build_run(opt, inputs, load_unet_config(opt.config))
     sink = sink_type(opt)

@@ -1,5 +1,9 @@
 """What a real-clip run reads from disk: the target frames, the source image and the landmarks file.  Host only (Pillow, numpy).
 
+The target clip comes as the folder of ``{index}.png`` files the reference's own decoding writes, or as a YUV4MPEG2 file
+(``ClipInputs.from_video`` over a ``scripts/demux.Y4MReader``: the batches then carry the file's I420 rows, which
+``inputs.ClipRunInputs`` uploads and converts on the device); the H.264 decoder itself stays outside either way.
+
 The reference decodes the target video into ``{index}.png`` files (``REFace/scripts/VFace_inference_batch.py:285``) and runs dlib
 on every frame and, a second time, on every aligned crop (``ddpm.py:1068-1099`` ``get_landmarks``).  dlib is outside this build
 (``scripts/intake.py:21-22``), so the landmarks are an input file, ``--landmarks FILE.npz``:
@@ -147,13 +151,33 @@ class ClipInputs:
     of the frame it TAKES its crop from (``fallback_indices``); ``landmarks`` the conditioning rows [n, 136]."""
 
     def __init__(self, target_frames: str, src_image: str, landmarks: str, n_frames: int, H: int, W: int, image_size: int = 1024):
-        from .intake import inv_transforms, quad_from_landmarks
         listed = list_frames(target_frames)
         if len(listed) < n_frames:
             raise SystemExit(f"--target_frames {target_frames}: {len(listed)} frame file(s), --n_frames asks for {n_frames}")
         listed = listed[:n_frames]
+        self.video = None           # (a folder of frame files)
         self.frame_ids = [i for i, _ in listed]
         self.paths = [p for _, p in listed]
+        self.size = None            # (H, W) of the clip's frames, known after the first batch
+        self._set_up(src_image, landmarks, n_frames, H, W, image_size)
+
+    @classmethod
+    def from_video(cls, video, src_image: str, landmarks: str, n_frames: int, H: int, W: int, image_size: int = 1024):
+        """The same inputs over a ``scripts/demux.Y4MReader`` instead of a folder: frame ids 0 .. n_frames - 1, and ``batch`` hands
+        out the I420 rows of the file, uint8 [F, frame_bytes], where the folder form hands out RGB frames (the conversion is the
+        device's: ``inputs.ClipRunInputs``).  One frame size by construction."""
+        if len(video) < n_frames:
+            raise SystemExit(f"--target_video {video.path}: {len(video)} frame(s), --n_frames asks for {n_frames}")
+        self = cls.__new__(cls)
+        self.video = video
+        self.frame_ids = list(range(n_frames))
+        self.paths = None
+        self.size = (video.H, video.W)
+        self._set_up(src_image, landmarks, n_frames, H, W, image_size)
+        return self
+
+    def _set_up(self, src_image, landmarks, n_frames, H, W, image_size):
+        from .intake import inv_transforms, quad_from_landmarks
         self.source_u8 = load_image(src_image)[None]                 # [1, Hs, Ws, 3]
         lm = load_landmarks(landmarks, n_frames)
         self.found, self.take = fallback_indices(lm.frames[:n_frames])
@@ -162,20 +186,28 @@ class ClipInputs:
         self.landmarks = conditioning_landmarks(lm, self.found, self.take, self.coeffs, range(n_frames), image_size, H, W)
         self.source_quad = quad_from_landmarks(lm.source)[None]
         self.source_landmarks = source_conditioning_landmarks(lm, inv_transforms(self.source_quad, image_size)[0], image_size, H, W)
-        self.size = None            # (H, W) of the clip's frames, known after the first batch
+
+    def _read(self, indices) -> torch.Tensor:
+        """Frames ``indices`` of the clip: RGB [n, Hs, Ws, 3] from a folder (checked against the clip's size), I420 rows
+        [n, frame_bytes] from a video file."""
+        if self.video is not None:
+            return self.video.read(indices)
+        frames = load_frames([self.paths[i] for i in indices])
+        if self.size is None:
+            self.size = tuple(frames.shape[1:3])
+        if tuple(frames.shape[1:3]) != self.size:
+            raise SystemExit(f"--target_frames: {self.paths[indices[0]]} is {frames.shape[2]} x {frames.shape[1]}, the clip's first frames "
+                             f"are {self.size[1]} x {self.size[0]}: the frames of a clip must all be one size")
+        return frames
 
     def batch(self, batch_id: int, F: int) -> dict:
         """Frames ``[batch_id * F, (batch_id + 1) * F)`` of the clip: ``frames`` uint8 [F, Hs, Ws, 3], each frame itself (pasted
         into); ``crop_frames``: the frames the crops are cut from (a frame without landmarks: the one it takes, read again);
-        ``quads`` [F, 4, 2], ``coeffs`` [F, 8], ``landmarks`` float32 [F, 136], ``found`` bool [F], ``frame_ids``."""
+        ``quads`` [F, 4, 2], ``coeffs`` [F, 8], ``landmarks`` float32 [F, 136], ``found`` bool [F], ``frame_ids``.  Over a video file
+        ``frames`` and ``crop_frames`` are I420 rows [F, frame_bytes] (``from_video``)."""
         sl = slice(batch_id * F, (batch_id + 1) * F)
         own = list(range(sl.start, sl.stop))
-        frames = load_frames([self.paths[i] for i in own])
-        if self.size is None:
-            self.size = tuple(frames.shape[1:3])
-        if tuple(frames.shape[1:3]) != self.size:
-            raise SystemExit(f"--target_frames: {self.paths[own[0]]} is {frames.shape[2]} x {frames.shape[1]}, the clip's first frames "
-                             f"are {self.size[1]} x {self.size[0]}: the frames of a clip must all be one size")
+        frames = self._read(own)
         crop_frames = frames
         if any(self.take[i] != i for i in own):
             crop_frames = frames.clone()
@@ -183,6 +215,9 @@ class ClipInputs:
                 t = int(self.take[i])
                 if t != i:
                     # (a frame of an earlier batch passed the size check when its own batch was read)
-                    crop_frames[row] = frames[t - sl.start] if t >= sl.start else load_image(self.paths[t])
+                    crop_frames[row] = frames[t - sl.start] if t >= sl.start else self._read_again(t)
         return {"frames": frames, "crop_frames": crop_frames, "quads": self.quads[sl], "coeffs": self.coeffs[sl],
                 "landmarks": self.landmarks[sl], "found": self.found[sl], "frame_ids": [self.frame_ids[i] for i in own]}
+
+    def _read_again(self, t: int) -> torch.Tensor:
+        return self.video.read([t])[0] if self.video is not None else load_image(self.paths[t])

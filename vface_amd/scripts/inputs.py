@@ -12,6 +12,8 @@ The questions, for batch ``k`` of ``F = --n_samples`` frames (tensors on the pro
     intake_frames(k)        frames to paste into, frames to crop from, quads [F, 4, 2] (host), label maps or None = ask the parser
     inherits(k)             per frame: does it take the label map of the frame before (no landmarks, :297-303)?
     carry_labels(k, maps)   the label maps with the inherited ones put in; remembers batch k's last map for batch k + 1
+    own_seconds(k)          stage name -> wall seconds of device work the provider did itself for batch k (``video_in``: the upload
+                            and colour conversion of a clip read from a video file); asked once, after ``intake_frames``
     landmarks(k)            conditioning landmarks [F, 136]
     source()                source frame [1, Hs, Ws, 3], quad (host), label map or None, landmarks [1, 136], identity features or None
     learnable_vector()      a seeded value for the model's learnable_vector on seeded weights, or None = leave the module's own
@@ -20,6 +22,8 @@ and, where a stage is off (seeded only): ``images`` ``latents`` ``latent_mask`` 
 ``inversion_cache`` ``inversion_latents`` ``paste_target`` ``source_clip_image``.
 """
 from __future__ import annotations
+
+import time
 
 import numpy as np
 import torch
@@ -88,6 +92,9 @@ class SeededInputs:
     def carry_labels(self, k, labels):
         return labels
 
+    def own_seconds(self, k):
+        return {}
+
     def landmarks(self, k):
         return (synth.synth_normal(f"cli.landmarks.{k}", (self.F, 136)) * 0.1 + 0.5).to(self.device)
 
@@ -148,13 +155,18 @@ class SeededInputs:
 class ClipRunInputs:
     """A ``clip_io.ClipInputs`` behind the same questions.  A frame without landmarks is cut with the quad, and from the pixels, of
     the frame it takes (``clip_io.fallback_indices``), inherits that frame's label map -- across a batch boundary too, which is
-    the one thing this object carries from batch to batch -- and has zero conditioning landmarks."""
+    the one thing this object carries from batch to batch -- and has zero conditioning landmarks.  Over a video file
+    (``ClipInputs.from_video``) the clip hands out I420 rows: they are uploaded as they are and become the same RGB frames on the
+    device (``hip.yuv420_to_rgb``; matrix and chroma siting from ``--video_in_matrix``, ``--chroma_upsample`` and the file's header),
+    timed as stage ``video_in``."""
     frame_size_order = "width_height"   # (a clip is rarely square: paste_back.PasteBack)
     record_keys = ("frame_ids", "pasted_frames", "crops", "conditioning")
 
     def __init__(self, clip, opt, device):
         self.clip, self.device, self.F = clip, torch.device(device), opt.n_samples
         self._last_labels = {}      # batch id -> its last frame's label map, for the first frame of the batch after it
+        self.matrix, self.chroma_upsample = opt.video_in_matrix or "bt709", opt.chroma_upsample or "sited"
+        self._seconds = {}          # batch id -> wall seconds of what this provider did on the device for it (`own_seconds`)
 
     def _rows(self, k):
         return slice(k * self.F, (k + 1) * self.F)
@@ -167,7 +179,25 @@ class ClipRunInputs:
 
     def intake_frames(self, k):
         given = self.clip.batch(k, self.F)
-        return given["frames"].to(self.device), given["crop_frames"].to(self.device), given["quads"], None
+        if self.clip.video is None:
+            return given["frames"].to(self.device), given["crop_frames"].to(self.device), given["quads"], None
+        # a video file: the I420 rows cross to the device (1.5 bytes per pixel) and become RGB frames there
+        torch.cuda.synchronize(self.device)
+        t0 = time.time()
+        frames = self._rgb(given["frames"])
+        crop_frames = frames if given["crop_frames"] is given["frames"] else self._rgb(given["crop_frames"])
+        torch.cuda.synchronize(self.device)
+        self._seconds[k] = {"video_in": time.time() - t0}
+        return frames, crop_frames, given["quads"], None
+
+    def _rgb(self, i420):
+        from .. import hip
+        head = self.clip.video.header
+        return hip.yuv420_to_rgb(i420.to(self.device), head.W, head.H, matrix=self.matrix, full_range=head.full_range,
+                                 chroma="nearest" if self.chroma_upsample == "nearest" else head.siting)
+
+    def own_seconds(self, k):
+        return self._seconds.pop(k, {})
 
     def inherits(self, k):
         return [not bool(found) for found in self.clip.found[self._rows(k)]]

@@ -158,6 +158,7 @@ def prepare(run, inputs, batch_id) -> Batch:
     if b.uc is None:    # :423 uc = learnable_vector per frame
         b.uc = run.model.learnable_vector.detach().float().repeat(run.opt.n_samples, 1, 1)
     stage_latents(run, inputs, b)
+    b.timer.seconds.update(inputs.own_seconds(batch_id))       # (device work of the provider's own, under its own stage names)
     if run.opt.clip_cond:
         stage_conditioning(run, inputs, b)
     stage_flow(run, inputs, b)
