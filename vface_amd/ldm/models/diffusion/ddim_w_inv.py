@@ -108,7 +108,11 @@ class DDIMSampler(object):
                callback=None, normals_sequence=None, img_callback=None, quantize_x0=False, eta=0., mask=None, x0=None,
                temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None, verbose=True, flow=None,
                x_T=None, log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None,
-               src_im=None, tar=None, **kwargs):
+               src_im=None, tar=None, carry=None, boundary_flow=None, **kwargs):
+        """``carry`` / ``boundary_flow`` (this package's addition): the batch is one of a whole clip's (``parallel.ClipCarry``, already
+        moved to this batch with ``begin_batch``) and ``boundary_flow`` the field from the previous batch's last frame into this
+        batch's frame 0, at the resolution of ``flow`` -- ``flow_fix`` then smooths frame 0 with the previous batch's last frame, step
+        by step, as one batch of the whole clip would (``_sampling_plan``)."""
         if conditioning is not None and not isinstance(conditioning, dict) and conditioning.shape[0] != batch_size:
             print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
@@ -120,7 +124,8 @@ class DDIMSampler(object):
                                   score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, x_T=x_T,
                                   flow=flow, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, **kwargs)
+                                  unconditional_conditioning=unconditional_conditioning, carry=carry, boundary_flow=boundary_flow,
+                                  **kwargs)
 
     def _register_step_hooks(self, flow):
         """ddim_w_inv.py:303,305."""
@@ -140,13 +145,14 @@ class DDIMSampler(object):
                       ddim_use_original_steps=False, callback=None, timesteps=None, quantize_denoised=False, mask=None,
                       x0=None, img_callback=None, log_every_t=100, temperature=1., noise_dropout=0.,
                       score_corrector=None, flow=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, src_im=None, max_steps=None, **kwargs):
+                      unconditional_conditioning=None, src_im=None, max_steps=None, carry=None, boundary_flow=None, **kwargs):
         state, steps = self._sampling_plan(cond, shape, target_conditioning=target_conditioning, inverse_results_dir=inverse_results_dir,
                                            x_T=x_T, ddim_use_original_steps=ddim_use_original_steps, callback=callback,
                                            quantize_denoised=quantize_denoised, mask=mask, x0=x0, img_callback=img_callback,
                                            log_every_t=log_every_t, temperature=temperature, noise_dropout=noise_dropout,
                                            score_corrector=score_corrector, flow=flow, unconditional_guidance_scale=unconditional_guidance_scale,
-                                           unconditional_conditioning=unconditional_conditioning, max_steps=max_steps, **kwargs)
+                                           unconditional_conditioning=unconditional_conditioning, max_steps=max_steps, carry=carry,
+                                           boundary_flow=boundary_flow, **kwargs)
         for _ in steps:
             pass
         return state["img"], state["intermediates"]
@@ -154,10 +160,14 @@ class DDIMSampler(object):
     def _sampling_plan(self, cond, shape, target_conditioning=None, inverse_results_dir=None, x_T=None,
                        ddim_use_original_steps=False, callback=None, quantize_denoised=False, mask=None, x0=None,
                        img_callback=None, log_every_t=100, temperature=1., noise_dropout=0., score_corrector=None, flow=None,
-                       unconditional_guidance_scale=1., unconditional_conditioning=None, max_steps=None, **kwargs):
+                       unconditional_guidance_scale=1., unconditional_conditioning=None, max_steps=None, carry=None,
+                       boundary_flow=None, **kwargs):
         """The sampling loop (ddim_w_inv.py:254-355) as ``(state, generator)``: every ``next()`` enqueues ONE DDIM step (hook
         registration :303,305 included) and updates ``state["img"]``; ``ddim_sampling`` drives it to the end, and
-        ``sample_while_inverting`` interleaves it with the next batch's inversion loop."""
+        ``sample_while_inverting`` interleaves it with the next batch's inversion loop.
+        ``carry`` (``parallel.ClipCarry``) with a ``flow_fix`` hook plan: the loop installs it on the engine with ``boundary_flow``
+        (brought to the latent map like ``flow``) when it starts, states the step before every forward, and takes it off the engine
+        when it ends -- however it ends.  Other hook plans couple no frames across a boundary: the carry is left alone."""
         if ddim_use_original_steps or mask is not None or quantize_denoised or score_corrector is not None:
             raise NotImplementedError("original-step sampling / masks / quantisation / score correctors are not used "
                                       "by scripts/VFace_inference_batch.py")
@@ -171,23 +181,54 @@ class DDIMSampler(object):
         state = {"img": img, "intermediates": {'x_inter': [img], 'pred_x0': [img]}}
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
+
+        def on_latent_map(f, what):
+            if f is not None and tuple(f.shape[-2:]) != tuple(shape[-2:]) and self.flow_resample == "area":
+                fh, fw = f.shape[-2] // shape[-2], f.shape[-1] // shape[-1]
+                if fh == fw and fh >= 1 and (fh * shape[-2], fw * shape[-1]) == tuple(f.shape[-2:]):
+                    f = hip.flow_to_latent(f, fh)
+            if f is not None and tuple(f.shape[-2:]) != tuple(shape[-2:]):
+                # the shipped script feeds 512x512 RAFT flow to a 64x64 map and dies in warp_image
+                raise RuntimeError(f"The size of the {what} {tuple(f.shape[-2:])} must match the latent map "
+                                   f"{tuple(shape[-2:])} (temporal_flow.py:43: grid + flow)")
+            return f
+
+        coupled = carry is not None and self.hook_plan.enabled and self.hook_plan.fusion == "flow_fix" and carry.world > 1
         flow_dev = _dev_flow(flow, device)
-        if flow_dev is not None and tuple(flow_dev.shape[-2:]) != tuple(shape[-2:]) and self.flow_resample == "area":
-            fh, fw = flow_dev.shape[-2] // shape[-2], flow_dev.shape[-1] // shape[-1]
-            if fh == fw and fh >= 1 and (fh * shape[-2], fw * shape[-1]) == tuple(flow_dev.shape[-2:]):
-                flow_dev = hip.flow_to_latent(flow_dev, fh)
-        if flow_dev is not None and tuple(flow_dev.shape[-2:]) != tuple(shape[-2:]):
-            # the shipped script feeds 512x512 RAFT flow to a 64x64 map and dies in warp_image
-            raise RuntimeError(f"The size of the flow field {tuple(flow_dev.shape[-2:])} must match the latent map "
-                               f"{tuple(shape[-2:])} (temporal_flow.py:43: grid + flow)")
+        if coupled and flow_dev is not None and flow_dev.shape[0] == 0:
+            flow_dev = None                         # (a one-frame batch has no field of its own)
+        flow_dev = on_latent_map(flow_dev, "flow field")
+        bflow_dev = None
+        if coupled:
+            if b != carry.count:
+                raise ValueError(f"carry: the batch holds {b} frames, batch {carry.rank} of the clip's plan {carry.count}")
+            if carry.rank > 0:
+                bflow_dev = _dev_flow(boundary_flow, device)
+                if bflow_dev is None:
+                    raise ValueError(f"carry: batch {carry.rank} needs boundary_flow, the field from the previous batch's last frame")
+                bflow_dev = on_latent_map(bflow_dev.reshape(1, 2, bflow_dev.shape[-2], bflow_dev.shape[-1]), "boundary flow field")
         self._register_step_hooks(flow_dev)  # the pre-loop registrations (:289,291) are overwritten before any UNet call
 
+        eng = self.model.model.diffusion_model.engine
+
         def steps():
+            if not coupled:
+                yield from walk()
+                return
+            carry.install(eng, bflow_dev, tuple(shape[-2:]), device)
+            try:
+                yield from walk()
+            finally:
+                carry.uninstall(eng)
+
+        def walk():
             img = state["img"]
             for i, step in enumerate(time_range):
                 if max_steps is not None and i >= max_steps:
                     break
                 self._register_step_hooks(flow_dev)
+                if coupled:
+                    carry.set_step(i)
                 index = total_steps - i - 1
                 ts = torch.full((b,), int(step), device=device, dtype=torch.long)
                 img, pred_x0 = self.p_sample_ddim_with_inverse(
@@ -373,6 +414,9 @@ class DDIMSampler(object):
         inversion forward), results bit-identical to running the loops one after the other (tests).  Returns
         ``((samples, intermediates), (x_inverted, intermediates))``."""
         sk, ik = dict(sample_kwargs), dict(invert_kwargs)
+        if sk.get("carry") is not None:
+            raise NotImplementedError("sample_while_inverting: a clip carry is installed on the engine for one loop's forwards; two "
+                                      "concurrent loops on one engine are not built")
         S, eta = sk.pop("S"), sk.pop("eta", 0.)
         if ik.pop("S") != S or ik.pop("eta", 0.) != eta:
             raise ValueError("sample_while_inverting: both loops walk ONE schedule (the same S and eta)")

@@ -20,6 +20,9 @@ exchange step here, issued between the hooked ``attn1``'s projection and its edi
 
 ``finish_exchange`` completes any of the three (bounded: ``exchange_timeout_s``, ``ExchangeTimeout``).  Under gloo with device
 tensors every form runs through host staging (the rehearsal on a box without one GPU per rank).
+
+The same one-neighbour exchange also couples the BATCHES of a clip on one GPU (``--whole_clip``): ``clip_batches`` is the plan,
+``ClipCarry`` keeps batch k's last-frame slabs of every DDIM step for batch k + 1.
 """
 from __future__ import annotations
 
@@ -54,6 +57,17 @@ def frame_range(rank: int, world: int, total: int):
     return first, base + (1 if rank < extra else 0)
 
 
+def clip_batches(n_frames: int, n_samples: int):
+    """The batch plan of a whole clip: ``[(first, count), ...]`` -- frames ``[0, n_samples)``, ``[n_samples, 2 n_samples)`` .. and,
+    where ``n_frames`` is no multiple of ``n_samples``, a last, shorter batch (a one-frame tail is a batch; a clip shorter than
+    ``n_samples`` is one batch of ``n_frames``).  Every frame is in exactly one batch.  The loop over batches, the input providers
+    and ``ClipCarry`` all read the plan from here."""
+    n_frames, n_samples = int(n_frames), int(n_samples)
+    if n_frames < 0 or n_samples < 1:
+        raise ValueError(f"clip_batches: n_frames >= 0 and n_samples >= 1; got {n_frames}, {n_samples}")
+    return [(first, min(n_samples, n_frames - first)) for first in range(0, n_frames, n_samples)]
+
+
 class FrameShard:
     def __init__(self, rank: int, world: int, total_frames: int, dist=None, mode: str = "p2p"):
         self.rank, self.world, self.total = rank, world, total_frames
@@ -68,6 +82,16 @@ class FrameShard:
         states it before every ``start_exchange`` -- eagerly and from the host calls between hipGraph segments alike -- so that an
         exchange object that keeps per-layer state (``StreamShard``) never has to infer it from call counts."""
         self.index = int(k)
+
+    def graph_signature(self):
+        """What of this exchange a captured forward depends on: part of ``replay``'s graph key."""
+        return (id(self), self.rank, self.world, self.first, self.count)
+
+    def capture_pass(self, on: bool) -> None:
+        """``replay`` says when the capture pass of a hipGraph capture begins and ends.  In that pass the forward's kernels are
+        recorded, not run, so the slab a ``start_exchange`` is handed there holds no data yet; the call is still made, because
+        the ranks of a clip must pair their calls.  Nothing to do for an exchange whose slabs are consumed by the same forward;
+        one that KEEPS them (``ClipCarry``) must not keep these."""
 
     # ---- flow bookkeeping: global flow[i] maps frame i -> frame i+1 (temporal_flow.py:163-188, F-1 fields)
     def local_flow(self, global_flow: torch.Tensor) -> torch.Tensor:
@@ -338,6 +362,135 @@ class LoopbackShard(FrameShard):
 
     def agree(self, ok: bool, over_budget: bool = False):
         return bool(ok), bool(over_budget)      # one process: its own verdict is everybody's
+
+
+class ClipCarry(FrameShard):
+    """The batches of ONE clip walked one after another through one GPU, each through its whole DDIM loop, with ``flow_fix``
+    coupled across the batch boundaries: batch k keeps its last frame's fused q|k slab of EVERY step and hooked level-0 layer,
+    batch k + 1 reads them where the unbatched clip reads the frame before.  One object per clip; ``begin_batch(k)`` moves it to
+    batch k of the plan (``clip_batches``), which is what ``rank`` / ``first`` / ``count`` then say -- not ``frame_range``.
+
+    * The store is keyed by ``(step, ordinal)``: the sampler states the DDIM step before each UNet call (``set_step``), the engine
+      the ordinal of the exchange inside the forward (``set_index``), eagerly and from the host calls between hipGraph segments
+      alike.  A capturing call runs the forward up to three times -- warm-up, capture pass, first replay -- so a repeated
+      ``start_exchange`` for one key overwrites its slab; the capture pass's slabs hold no data (its kernels are recorded, not
+      run) and are not stored (``capture_pass``), so a capture that falls back to the warm-up forward's result -- it failed, or
+      its pool is over the byte budget -- leaves the warm-up's slabs in place; nothing is owed to another rank (``drain``).
+    * Two generations at most are alive: the one being read (batch k - 1's) and the one being written (batch k's); the slabs of
+      an older one are recycled as the buffers of the one being written.  One generation is steps x hooked layers x ``[n, 2d]``
+      16-bit (50 x 2 x 4096 x 640 x 2 B = 524 MB at 512 x 512).  The last batch keeps nothing, and ``end_batch`` after its loop
+      lets go of what it read.
+    * Reading a key the previous batch never wrote (it ran fewer steps, or another hook plan) raises, naming step and ordinal.
+    * ``temporal`` needs the NEXT batch's frames and ``adaIn`` every frame of the clip: both raise, as on a loop-back shard."""
+
+    def __init__(self, batches):
+        self.batches = [(int(f), int(c)) for f, c in batches]
+        if not self.batches:
+            raise ValueError("ClipCarry: a clip has at least one batch")
+        self.rank, self.world, self.total = 0, len(self.batches), sum(c for _, c in self.batches)
+        self.dist, self.mode = None, "carry"          # (one process: no collective backend)
+        self._capturing = False
+        self.generations: dict = {}     # batch -> {(step, ordinal): slab}
+        self._spare: list = []          # slabs of dropped generations, re-used as buffers
+        self.step: Optional[int] = None
+        self.index = 0
+        self.begin_batch(0)
+
+    def begin_batch(self, k: int) -> None:
+        """Move to batch ``k`` of the plan: it reads generation k - 1 and writes generation k (anew); every other one is dropped."""
+        if not 0 <= k < self.world:
+            raise IndexError(f"ClipCarry: batch {k} of a plan of {self.world}")
+        self.rank = int(k)
+        self.first, self.count = self.batches[k]
+        for g in [g for g in self.generations if g != k - 1]:
+            self._spare += list(self.generations.pop(g).values())
+        self.generations[k] = {}
+        if k + 1 == self.world:
+            self._spare = []        # (the last batch writes nothing: the buffers are let go)
+        self.step = None
+
+    def end_batch(self) -> None:
+        """After the batch's DDIM loop: the last batch of the clip lets go of the generation it read (nobody reads it again)."""
+        if self.rank + 1 == self.world:
+            self.generations.pop(self.rank - 1, None)
+
+    def capture_pass(self, on: bool) -> None:
+        self._capturing = bool(on)
+
+    def drain(self, pending, remaining) -> None:
+        """An aborted capture owes nobody an exchange here, and the warm-up forward's slabs are already stored."""
+
+    def set_step(self, step: int) -> None:
+        """The DDIM step of the NEXT UNet forward (the sampler's loop counter), stated before it."""
+        self.step = int(step)
+
+    def _key(self):
+        if self.step is None:
+            raise RuntimeError("ClipCarry: the sampler has to state the DDIM step (set_step) before a UNet forward that exchanges")
+        return (self.step, int(self.index))
+
+    def start_exchange(self, tail: torch.Tensor, recv=None):
+        if self.world == 1:
+            return None
+        key = self._key()
+        if self.rank + 1 < self.world and not self._capturing:
+            gen = self.generations[self.rank]
+            slot = gen.get(key)
+            if slot is None or slot.shape != tail.shape or slot.dtype != tail.dtype or slot.device != tail.device:
+                at = next((i for i, s in enumerate(self._spare)
+                           if s.shape == tail.shape and s.dtype == tail.dtype and s.device == tail.device), None)
+                slot = gen[key] = self._spare.pop(at) if at is not None else torch.empty_like(tail, memory_format=torch.contiguous_format)
+            slot.copy_(tail)        # (stream-ordered, on the stream of the forward; a second start for this key lands here again)
+        return ("carry", key, None)
+
+    def finish_exchange(self, handle):
+        if handle is None or self.rank == 0:
+            return None
+        step, ordinal = handle[1]
+        slab = self.generations.get(self.rank - 1, {}).get((step, ordinal))
+        if slab is None:
+            raise KeyError(f"ClipCarry: batch {self.rank} reads the slab of DDIM step {step}, exchange ordinal {ordinal}, which batch "
+                           f"{self.rank - 1} never wrote (it ran fewer steps, or with another hook plan)")
+        return slab
+
+    def start_temporal(self, edges, recv=None):
+        raise NotImplementedError("a clip carry runs the batches one after another: the temporal halo needs the NEXT batch's frames too")
+
+    def start_gather(self, part, recv=None):
+        raise NotImplementedError("a clip carry runs the batches one after another: the adaIn gather needs every frame of the clip")
+
+    def agree(self, ok: bool, over_budget: bool = False):
+        return bool(ok), bool(over_budget)      # one process: its own verdict is everybody's
+
+    def carry_bytes(self) -> int:
+        """Bytes of the generation being written: what this batch hands to the next one."""
+        return sum(s.numel() * s.element_size() for s in self.generations.get(self.rank, {}).values())
+
+    def graph_signature(self):
+        """What of this object a captured forward depends on (``replay``'s graph key): whether it reads a slab, and how many frames
+        it holds -- not which batch of the plan it is at, so that batches of one shape replay one capture."""
+        return (id(self), self.rank > 0, self.world, self.count)
+
+    def install(self, engine, boundary_flow: Optional[torch.Tensor] = None, hw=None, device=None) -> None:
+        """Hook the carry into a ``UNetEngine`` for the batch it is at.  ``boundary_flow`` ``[2, h, w]``: the field from the previous
+        batch's last frame into this batch's frame 0 (batch 0: None); ``hw``: the (h, w) of the clip's flow fields.  A clip of one
+        batch has no boundary: nothing is installed."""
+        if self.world == 1:
+            engine.halo_exchange, engine.halo_flow, engine.halo_hw = None, None, None
+            return
+        if self.rank > 0 and boundary_flow is None:
+            raise ValueError(f"ClipCarry: batch {self.rank} needs the flow field from the previous batch's last frame into its frame 0")
+        if self.rank == 0 or boundary_flow is None:
+            engine.halo_flow = None
+        else:
+            engine.halo_flow = boundary_flow.reshape(2, boundary_flow.shape[-2], boundary_flow.shape[-1]).to(
+                device=device, dtype=torch.float32).contiguous()
+        engine.halo_exchange = self
+        engine.halo_hw = (int(hw[0]), int(hw[1]))
+
+    @staticmethod
+    def uninstall(engine) -> None:
+        engine.halo_exchange, engine.halo_flow, engine.halo_hw = None, None, None
 
 
 class StreamShard(FrameShard):

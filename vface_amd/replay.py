@@ -484,8 +484,10 @@ class _StepReplay:
         self._ensure_packed()
         sig, flows = self._hook_signature()
         ex = self.halo_exchange
-        shard_sig = None if ex is None else (id(ex), ex.rank, ex.world, ex.first, ex.count, self.halo_hw,
-                                             None if self.halo_flow is None else tuple(self.halo_flow.shape))
+        # (an exchange object that is moved along the batches of a clip, parallel.ClipCarry, says itself what of its position a
+        #  captured forward depends on: batches of one shape then replay one capture)
+        shard_sig = None if ex is None else (ex.graph_signature() +
+                                             (self.halo_hw, None if self.halo_flow is None else tuple(self.halo_flow.shape)))
         key = (x.N, x.H, x.W, tuple(x.t.shape), x.t.dtype, self._version, *(getattr(self, a) for a in self._GRAPH_SWITCHES),
                hip._ws_domain, self.exchange_events is not None, sig,
                tuple(context.shape), torch.cuda.current_stream().cuda_stream, shard_sig)
@@ -569,6 +571,7 @@ class _StepReplay:
             seg = _GraphSegments(self, real_exchange)
             if real_exchange is not None:
                 self.halo_exchange = seg             # start_exchange / finish_exchange cut the capture (see _GraphSegments)
+                real_exchange.capture_pass(True)     # (the slabs this pass hands over hold no data: FrameShard.capture_pass)
             # No garbage collection inside the capture pass: a cycle collected there can release device objects of an earlier
             # configuration (its graphs, their pool, events), and releasing them while this thread captures is a fatal runtime
             # error, not a Python exception.  Collected above, as ``torch.cuda.graph`` does; the collector stays off until the end.
@@ -602,6 +605,8 @@ class _StepReplay:
                 real_exchange.drain(st.pop("h", None) if st else None, counting.tails[done:])
         finally:
             self.halo_exchange, self.halo_flow = real_exchange, real_halo_flow
+            if real_exchange is not None:
+                real_exchange.capture_pass(False)
             for c, f in zip(cfgs, saved_flows):
                 c.flow = f
             self._a2_cache = saved_cache

@@ -30,7 +30,7 @@ parts that meet at plain data:
 
     scripts/inputs.py       what a batch is fed: ``SeededInputs`` (``--synthetic``) or ``ClipRunInputs`` (a clip), one interface
     scripts/run_setup.py    everything a run owns, built once: model and weights, sampler, intake, parser, RAFT, paste-back, source
-    scripts/pipeline.py     the stages of a batch, their wall timing, the loop (``--pipeline_inversion`` included), the record
+    scripts/pipeline.py     the stages of a batch, their wall timing, the loop (``--pipeline_inversion``, ``--whole_clip``), the record
     scripts/outputs.py      the sinks: ``.pt`` / PNG of a seeded run, PNG / YUV4MPEG2 of a clip
     scripts/checkpoint.py   reading ``last.ckpt``
 """
@@ -171,6 +171,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--pipeline_inversion", action="store_true",
                    help="run the DDIM inversion of batch k + 1 beside the sampling of batch k, on two HIP streams (the batches are "
                         "independent: VFace_inference_batch.py:413, 529-553); frames bit-identical to the sequential order")
+    p.add_argument("--whole_clip", action="store_true",
+                   help="process EVERY frame (a last, shorter batch where --n_frames is no multiple of --n_samples) and make "
+                        "--n_samples a memory knob only: flow_fix is coupled across the batch boundaries (batch k keeps its last "
+                        "frame's q|k of every step, batch k + 1 smooths its first frame with them, parallel.ClipCarry) and every "
+                        "per-frame random draw is seeded by (--seed, frame, draw), so the frames written are the same for every "
+                        "--n_samples.  An extension of the reference, which drops the tail frames and leaves a seam at every batch")
     return p
 
 
@@ -262,6 +268,24 @@ def check_options(opt):
         raise SystemExit("--arcface computes the identity features of the conditioning mix: it needs --clip_cond")
     if opt.paste_back and not opt.with_vae:
         raise SystemExit("--paste_back pastes decoded pixels: it needs --with_vae")
+    check_whole_clip_options(opt)
+
+
+def check_whole_clip_options(opt):
+    """--whole_clip promises the same frames for every --n_samples: what cannot keep that promise is refused."""
+    opt = normalise_options(opt)
+    if not opt.whole_clip:
+        return
+    if opt.fusion in ("temporal", "adaIn"):
+        needs = "the NEXT batch's first two frames" if opt.fusion == "temporal" else "a standard deviation over every frame of the clip"
+        raise SystemExit(f"--whole_clip walks the batches one after another and --fusion {opt.fusion} needs {needs}: its frames would "
+                         "still depend on --n_samples (coupled across batches: flow_fix; uncoupled modes: none, fft, replace, mix ..)")
+    if opt.pipeline_inversion:
+        raise SystemExit("--whole_clip and --pipeline_inversion together are not built: the carry is installed on the engine for one "
+                         "loop's forwards, and --pipeline_inversion runs two loops on it at once")
+    if opt.ddim_eta != 0.0:
+        raise SystemExit(f"--whole_clip needs --ddim_eta 0: the sampler's noise is drawn per batch, so at --ddim_eta {opt.ddim_eta:g} "
+                         "the frames would depend on --n_samples")
 
 
 def _checked(opt, synthetic: bool) -> argparse.Namespace:

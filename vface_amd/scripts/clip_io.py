@@ -27,6 +27,8 @@ from typing import List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from ..parallel import clip_batches
+
 FRAME_NAME = re.compile(r"^(\d+)\.(png|jpg)$")
 
 
@@ -200,12 +202,14 @@ class ClipInputs:
                              f"are {self.size[1]} x {self.size[0]}: the frames of a clip must all be one size")
         return frames
 
-    def batch(self, batch_id: int, F: int) -> dict:
-        """Frames ``[batch_id * F, (batch_id + 1) * F)`` of the clip: ``frames`` uint8 [F, Hs, Ws, 3], each frame itself (pasted
+    def batch(self, batch_id: int, F: int, whole_clip: bool = False) -> dict:
+        """Frames ``[batch_id * F, (batch_id + 1) * F)`` of the clip -- ``whole_clip``: batch ``batch_id`` of the plan that covers
+        every frame (``parallel.clip_batches``: the last batch may be shorter than F) --: ``frames`` uint8 [F, Hs, Ws, 3], each frame itself (pasted
         into); ``crop_frames``: the frames the crops are cut from (a frame without landmarks: the one it takes, read again);
         ``quads`` [F, 4, 2], ``coeffs`` [F, 8], ``landmarks`` float32 [F, 136], ``found`` bool [F], ``frame_ids``.  Over a video file
         ``frames`` and ``crop_frames`` are I420 rows [F, frame_bytes] (``from_video``)."""
-        sl = slice(batch_id * F, (batch_id + 1) * F)
+        first, count = clip_batches(len(self.frame_ids), F)[batch_id] if whole_clip else (batch_id * F, F)
+        sl = slice(first, first + count)
         own = list(range(sl.start, sl.stop))
         frames = self._read(own)
         crop_frames = frames

@@ -19,7 +19,11 @@ The questions, for batch ``k`` of ``F = --n_samples`` frames (tensors on the pro
     learnable_vector()      a seeded value for the model's learnable_vector on seeded weights, or None = leave the module's own
 
 and, where a stage is off (seeded only): ``images`` ``latents`` ``latent_mask`` ``keep_mask`` ``id_feats`` ``flow``
-``inversion_cache`` ``inversion_latents`` ``paste_target`` ``source_clip_image``.
+``boundary_flow`` ``inversion_cache`` ``inversion_latents`` ``paste_target`` ``source_clip_image``.
+
+Which frames batch ``k`` holds is ``batch_plan(opt)[k]``, ``(first, count)``: ``--n_samples`` frames each and the tail dropped, or under
+``--whole_clip`` every frame (``parallel.clip_batches``: a last batch may be shorter).  Under ``--whole_clip`` the seeded stand-ins
+are drawn per CLIP and cut by frame, so that what a frame is fed does not depend on the batch that holds it.
 """
 from __future__ import annotations
 
@@ -28,7 +32,17 @@ import time
 import numpy as np
 import torch
 
+from ..parallel import clip_batches
 from ..utils import synth
+
+
+def batch_plan(opt):
+    """``[(first, count), ...]`` of a run: the reference's ``DataLoader(batch_size=n_samples, drop_last=True)`` (:376-382), or
+    under ``--whole_clip`` every frame of the clip (``parallel.clip_batches``).  The loop, the providers and ``clip_io`` read it
+    from here."""
+    if getattr(opt, "whole_clip", False):
+        return clip_batches(opt.n_frames, opt.n_samples)
+    return [(k * opt.n_samples, opt.n_samples) for k in range(opt.n_frames // opt.n_samples)]
 
 
 def _quad_coeffs(size, quad):
@@ -63,31 +77,63 @@ def synthetic_intake_inputs(F_: int, S_: int, H: int, W: int, seed: int):
 
 class SeededInputs:
     """The stand-ins of ``--synthetic``.  Every draw is a function of its tag (``cli.{name}.{k}``) or seed alone, so the order in
-    which a run asks is free."""
+    which a run asks is free.  A stand-in is drawn over a SCOPE and the batch takes its rows of it (``_scope``): the batch's own
+    ``--n_samples`` frames, tagged and seeded by the batch -- or, under ``--whole_clip``, the clip's ``--n_frames``, tagged ``clip``,
+    drawn once per provider and cut by frame."""
     frame_size_order = "reference"      # (PasteBack: :623 as written; the seeded frames are square)
     record_keys = ()                    # a batch's record carries no key beyond the common ones
 
     def __init__(self, opt, device):
         self.opt, self.device, self.F = opt, torch.device(device), opt.n_samples
         self.h, self.w = opt.H // opt.f, opt.W // opt.f
+        self.whole = bool(getattr(opt, "whole_clip", False))
+        self.plan = batch_plan(opt)
+        self._clip = {}                 # --whole_clip: what was drawn over the clip, by name
 
-    def _normal(self, k, name, shape):
-        return synth.synth_normal(f"cli.{name}.{k}", shape).to(self.device)
+    def _scope(self, k):
+        """``(tag, seed offset, frames, rows)`` of batch k's stand-ins: what they are drawn over, and the batch's rows of it."""
+        if self.whole:
+            first, count = self.plan[k]
+            return "clip", 0, self.opt.n_frames, slice(first, first + count)
+        return k, k, self.F, slice(0, self.F)
+
+    def _drawn(self, k, name, make):
+        """``make(tag, seed offset, frames)`` over batch k's scope; a clip-long draw is made once."""
+        tag, offset, n, _ = self._scope(k)
+        if not self.whole:
+            return make(tag, offset, n)
+        if name not in self._clip:
+            self._clip[name] = make(tag, offset, n)
+        return self._clip[name]
+
+    def count(self, k):
+        rows = self._scope(k)[3]
+        return rows.stop - rows.start
+
+    def _host(self, k, name, shape, groups=1):
+        """Batch k's rows of N(0, 1) ``[groups * frames, *shape]`` tagged ``cli.{name}.{scope}`` (``groups`` blocks of frames each)."""
+        rows = self._scope(k)[3]
+        full = self._drawn(k, name, lambda tag, _, n: synth.synth_normal(f"cli.{name}.{tag}", (groups * n,) + tuple(shape)))
+        return full.reshape((groups, -1) + tuple(shape))[:, rows].reshape((-1,) + tuple(shape))
+
+    def _normal(self, k, name, shape, groups=1):
+        return self._host(k, name, shape, groups).to(self.device)
 
     def frame_ids(self, k):
         return None
 
     def tokens(self, k):
-        return tuple(self._normal(k, name, (self.F, 1, 768)) for name in ("c", "uc", "tc"))
+        return tuple(self._normal(k, name, (1, 768)) for name in ("c", "uc", "tc"))
 
     def intake_frames(self, k):
-        o = self.opt
-        frames, quads, labels = synthetic_intake_inputs(self.F, o.frame_size, o.H, o.W, o.seed + 1000 + k)
+        o, rows = self.opt, self._scope(k)[3]
+        frames, quads, labels = (v[rows] for v in self._drawn(k, "intake", lambda _, offset, n: synthetic_intake_inputs(
+            n, o.frame_size, o.H, o.W, o.seed + 1000 + offset)))
         frames = frames.to(self.device)
         return frames, frames, quads, labels.to(self.device)
 
     def inherits(self, k):
-        return [False] * self.F
+        return [False] * self.count(k)
 
     def carry_labels(self, k, labels):
         return labels
@@ -96,7 +142,7 @@ class SeededInputs:
         return {}
 
     def landmarks(self, k):
-        return (synth.synth_normal(f"cli.landmarks.{k}", (self.F, 136)) * 0.1 + 0.5).to(self.device)
+        return (self._host(k, "landmarks", (136,)) * 0.1 + 0.5).to(self.device)
 
     def source(self):
         o = self.opt
@@ -110,43 +156,53 @@ class SeededInputs:
 
     # ---- stand-ins for the products of stages that are off
     def images(self, k):
-        o = self.opt
-        return torch.stack([synth.synth_normal(f"cli.img{f}.{k}", (3, o.H, o.W)).clamp(-1, 1) for f in range(self.F)]).to(self.device)
+        o, (tag, _, n, rows) = self.opt, self._scope(k)
+        return torch.stack([synth.synth_normal(f"cli.img{f}.{tag}", (3, o.H, o.W)).clamp(-1, 1) for f in range(n)[rows]]).to(self.device)
 
     def latents(self, k):
-        return (synth.synth_normal(f"cli.inp.{k}", (self.F, self.opt.C, self.h, self.w)) * 0.18215).to(self.device)
+        return (self._host(k, "inp", (self.opt.C, self.h, self.w)) * 0.18215).to(self.device)
 
     def latent_mask(self, k):
-        return synth.synth_mask(self.F, self.h, self.w).to(self.device)
+        return synth.synth_mask(self.count(k), self.h, self.w).to(self.device)
 
     def keep_mask(self, k):
-        return synth.synth_mask(self.F, self.opt.H, self.opt.W).to(self.device)
+        return synth.synth_mask(self.count(k), self.opt.H, self.opt.W).to(self.device)
 
     def id_feats(self, k):
-        return tuple(self._normal(k, name, (self.F, 512)) for name in ("id_feat", "id_feat_tar"))
+        return tuple(self._normal(k, name, (512,)) for name in ("id_feat", "id_feat_tar"))
 
-    def flow(self, k):
-        """A host field per frame pair; with ``--flow_pixels`` at pixel resolution, its latent resample a +-2-cell motion."""
+    def _fields(self, k):
+        """The scope's frames - 1 host fields; with ``--flow_pixels`` at pixel resolution, their latent resample a +-2-cell motion."""
         o = self.opt
         if o.flow_pixels:
-            return [f[None] * o.f for f in synth.synth_flow(self.F - 1, o.H, o.W, seed=o.seed + k)]
-        return [f[None] for f in synth.synth_flow(self.F - 1, self.h, self.w, seed=o.seed + k)]
+            return self._drawn(k, "flow", lambda _, offset, n: [f[None] * o.f for f in synth.synth_flow(n - 1, o.H, o.W, seed=o.seed + offset)])
+        return self._drawn(k, "flow", lambda _, offset, n: [f[None] for f in synth.synth_flow(n - 1, self.h, self.w, seed=o.seed + offset)])
+
+    def flow(self, k):
+        """The fields between the batch's own frames."""
+        rows = self._scope(k)[3]
+        return self._fields(k)[rows.start:rows.stop - 1]
+
+    def boundary_flow(self, k):
+        """``--whole_clip``: the field from the last frame of batch k - 1 into the first frame of batch k; None for batch 0."""
+        first = self._scope(k)[3].start
+        return self._fields(k)[first - 1] if first else None
 
     def inversion_cache(self, k, timesteps):
-        return {int(s): self._normal(k, f"inv{int(s)}", (self.F, self.opt.C, self.h, self.w)) for s in timesteps}
+        return {int(s): self._normal(k, f"inv{int(s)}", (self.opt.C, self.h, self.w)) for s in timesteps}
 
     def inversion_latents(self, k):
-        return self._normal(k, "z2", (2 * self.F, self.opt.C, self.h, self.w))
+        return self._normal(k, "z2", (self.opt.C, self.h, self.w), groups=2)       # [target ; source]
 
     def paste_target(self, k, canvas):
         """Original frames and ``inv_transforms_all`` rows (:625) where no intake made them: the ``canvas`` lands on the central
         half of the frame, slightly sheared."""
-        S_ = self.opt.frame_size
-        gen = torch.Generator().manual_seed(self.opt.seed + 1000 + k)
-        frames = torch.randint(0, 256, (self.F, S_, S_, 3), dtype=torch.uint8, generator=gen).to(self.device)
+        S_, (_, _, n, rows) = self.opt.frame_size, self._scope(k)
+        frames = self._drawn(k, "paste", lambda _, offset, n: torch.randint(
+            0, 256, (n, S_, S_, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(self.opt.seed + 1000 + offset)))
         q = S_ / 4.0
-        return frames, [_quad_coeffs(canvas, [(q + 3 * f, q), (3 * q, q + f), (3 * q - f, 3 * q), (q, 3 * q - 2 * f)])
-                        for f in range(self.F)]
+        return frames[rows].to(self.device), [_quad_coeffs(canvas, [(q + 3 * f, q), (3 * q, q + f), (3 * q - f, 3 * q), (q, 3 * q - 2 * f)])
+                                              for f in range(n)[rows]]
 
     def source_clip_image(self):
         return synth.synth_normal("cli.source224", (1, 3, 224, 224)).to(self.device)
@@ -164,12 +220,15 @@ class ClipRunInputs:
 
     def __init__(self, clip, opt, device):
         self.clip, self.device, self.F = clip, torch.device(device), opt.n_samples
+        self.whole = bool(getattr(opt, "whole_clip", False))
+        self.plan = batch_plan(opt)
         self._last_labels = {}      # batch id -> its last frame's label map, for the first frame of the batch after it
         self.matrix, self.chroma_upsample = opt.video_in_matrix or "bt709", opt.chroma_upsample or "sited"
         self._seconds = {}          # batch id -> wall seconds of what this provider did on the device for it (`own_seconds`)
 
     def _rows(self, k):
-        return slice(k * self.F, (k + 1) * self.F)
+        first, count = self.plan[k] if self.whole else (k * self.F, self.F)
+        return slice(first, first + count)
 
     def frame_ids(self, k):
         return list(self.clip.frame_ids[self._rows(k)])
@@ -178,7 +237,7 @@ class ClipRunInputs:
         return None, None, None     # :423 uc = learnable_vector; c and tc come from the conditioning stage
 
     def intake_frames(self, k):
-        given = self.clip.batch(k, self.F)
+        given = self.clip.batch(k, self.F, whole_clip=self.whole)
         if self.clip.video is None:
             return given["frames"].to(self.device), given["crop_frames"].to(self.device), given["quads"], None
         # a video file: the I420 rows cross to the device (1.5 bytes per pixel) and become RGB frames there
@@ -222,5 +281,5 @@ class ClipRunInputs:
     def _no_stand_in(self, *a):
         raise RuntimeError("a clip from disk runs every stage (CLIP_STAGES): there is no stand-in for a stage's product")
 
-    images = latents = latent_mask = keep_mask = id_feats = flow = _no_stand_in
+    images = latents = latent_mask = keep_mask = id_feats = flow = boundary_flow = _no_stand_in
     inversion_cache = inversion_latents = paste_target = source_clip_image = _no_stand_in

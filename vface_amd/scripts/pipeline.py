@@ -4,7 +4,12 @@ A stage is a function of ``(run, inputs, batch)``: ``run`` is what the run owns 
 provider it was handed (``scripts/inputs.py``), ``batch`` the state it reads and extends.  Which stages run is decided by what
 ``run`` holds and the options; none of them asks what kind of provider it has.  ``prepare`` is a batch up to, not including, its
 DDIM inversion; ``run_batches`` inverts, samples (beside the next batch's inversion under ``--pipeline_inversion``), decodes,
-pastes, hands the batch to the output sink and appends its record."""
+pastes, hands the batch to the output sink and appends its record.
+
+Which frames a batch holds is ``inputs.batch_plan(opt)``; a stage reads ``batch.first`` / ``batch.count``, never ``--n_samples``.
+Under ``--whole_clip`` (an extension of the reference) the plan covers every frame, ``flow_fix`` is coupled across the
+batch boundaries (``parallel.ClipCarry`` in ``run.carry``, the boundary field in ``batch.boundary_flow``) and every per-frame
+random draw is ``frame_noise``'s -- so the frames written do not depend on ``--n_samples``."""
 from __future__ import annotations
 
 import contextlib
@@ -14,6 +19,7 @@ from typing import Any, Optional
 
 import torch
 
+from .inputs import batch_plan
 from .intake import REMOVE_MASK_TAR_FFHQ, inv_transforms
 
 
@@ -42,6 +48,8 @@ class StageTimer:
 class Batch:
     id: int
     frame_ids: Optional[list]
+    first: int = 0                  # the batch's frames in the clip: [first, first + count) (inputs.batch_plan)
+    count: int = 0
     timer: StageTimer = field(default_factory=StageTimer)
     c: Any = None                   # conditioning tokens [F, 1, 768]; uc, tc: unconditional, and the inversion's
     uc: Any = None
@@ -55,6 +63,9 @@ class Batch:
     z_inp: Any = None               # inpaint latents, and their mask on the latent grid
     mask: Any = None
     flow: Any = None
+    boundary_flow: Any = None       # --whole_clip: the field from the previous batch's last frame into this batch's frame 0
+    coupled: bool = False           # ... and whether the sampler coupled flow_fix across that boundary; the bytes handed on
+    carry_bytes: int = 0
     inv_store: dict = field(default_factory=dict)      # timestep -> inverted latents
     invert_kw: Optional[dict] = None                    # arguments of ddim_invert; None: nothing to invert
     inverted: bool = False
@@ -64,8 +75,28 @@ class Batch:
     pasted: Any = None              # uint8 [F, Hs, Ws, 3]
 
 
-def encode(run, x):
-    return run.model.get_first_stage_encoding(run.model.encode_first_stage(x)).detach()         # :456-457
+DRAWS = ("inpaint", "z2_tar", "paste_back")     # the per-frame posterior draws of a batch (distributions.py:23-28)
+
+
+def frame_noise(seed: int, frames, draw: str, shape) -> torch.Tensor:
+    """``--whole_clip``: N(0, 1) ``[len(frames), *shape]`` on the host, row j from a ``torch.Generator`` seeded by ``(seed, frames[j],
+    draw)`` alone -- a frame's draw is the same whichever batch holds it and wherever it stands in that batch."""
+    rows = []
+    for f in frames:
+        gen = torch.Generator().manual_seed(((int(seed) * 1000003 + int(f)) * len(DRAWS) + DRAWS.index(draw)) % (1 << 63))
+        rows.append(torch.randn(tuple(shape), generator=gen))
+    return torch.stack(rows) if rows else torch.empty((0,) + tuple(shape))
+
+
+def batch_noise(run, b, draw):
+    """The posterior draw ``draw`` of batch ``b``: None = torch's global generator in batch order, as the reference draws."""
+    if not run.opt.whole_clip:
+        return None
+    return frame_noise(run.opt.seed, range(b.first, b.first + b.count), draw, (run.opt.C,) + tuple(run.latent))
+
+
+def encode(run, x, noise=None):
+    return run.model.get_first_stage_encoding(run.model.encode_first_stage(x), noise).detach()  # :456-457
 
 
 def target_images(inputs, b):
@@ -102,7 +133,7 @@ def stage_latents(run, inputs, b):
         return
     pixels = stage_intake(run, inputs, b) if run.intake is not None else target_images(inputs, b)
     with b.timer("vae_encode"):
-        b.z_inp = encode(run, pixels)
+        b.z_inp = encode(run, pixels, batch_noise(run, b, "inpaint"))
 
 
 def stage_conditioning(run, inputs, b):
@@ -122,26 +153,43 @@ def stage_conditioning(run, inputs, b):
 
 
 def stage_flow(run, inputs, b):
+    """The batch's own F - 1 fields and, under ``--whole_clip`` with a batch in front of it, the boundary field: RAFT on [the
+    previous batch's last image ; this batch's images] gives F fields, the first of which is the boundary's.  RAFT's fields are
+    not bit-invariant to how many pairs one call holds, so under ``--whole_clip`` every pair is a call of its own."""
+    whole = run.opt.whole_clip
+    if whole and run.opt.fusion != "flow_fix":
+        return                      # (no other hook mode reads a flow field: `sample_kwargs` hands none over)
     if run.raft is None:
         b.flow = inputs.flow(b.id)
+        if whole and b.first > 0:
+            with b.timer("boundary_flow"):
+                b.boundary_flow = inputs.boundary_flow(b.id)
         return
     from . import temporal_flow as tflow
     video = target_images(inputs, b)
-    with b.timer("flow"):       # :550-553 flow = return_flow(target frames), pixel resolution
-        b.flow = tflow.return_flow(video, run.raft)
+    if not whole:
+        with b.timer("flow"):       # :550-553 flow = return_flow(target frames), pixel resolution
+            b.flow = tflow.return_flow(video, run.raft)
+        return
+    if b.first > 0:
+        with b.timer("boundary_flow"):
+            b.boundary_flow = tflow.return_flow(torch.cat([run.last_image, video[:1]]), run.raft)[0]
+    with b.timer("flow"):
+        b.flow = [tflow.return_flow(video[i:i + 2], run.raft)[0] for i in range(video.shape[0] - 1)]
+    run.last_image = video[-1:].clone()
 
 
 def stage_inversion_operands(run, inputs, b):
     """:531-540: invert [target ; source] (2F), hooks off; the target half is cached per timestep.  ``--no_inversion``: a seeded
     cache instead."""
-    opt, F_, (h, w) = run.opt, run.opt.n_samples, run.latent
+    opt, F_, (h, w) = run.opt, b.count, run.latent
     if opt.no_inversion:
         run.sampler.make_schedule(opt.ddim_steps, ddim_eta=opt.ddim_eta, verbose=False)
         b.inv_store, b.inverted = inputs.inversion_cache(b.id, run.sampler.ddim_timesteps), True
         return
     if run.source_state is not None:    # :488-490, :509-525: z2_tar = encode(prior), prior = the batch's image; the source's own half
         with b.timer("vae_encode"):
-            z2_tar = encode(run, b.img)
+            z2_tar = encode(run, b.img, batch_noise(run, b, "z2_tar"))
         z2, cond2, kw2 = run.source_state.inversion_operands(z2_tar, b.tc, b.z_inp, b.mask, cond_src=None if opt.clip_cond else b.c)
     else:
         z2, cond2 = inputs.inversion_latents(b.id), torch.cat([b.tc, b.c])
@@ -153,10 +201,13 @@ def stage_inversion_operands(run, inputs, b):
 
 def prepare(run, inputs, batch_id) -> Batch:
     """Everything of a batch up to (not including) its DDIM inversion: intake, parsing, VAE encoding, conditioning, flow."""
-    b = Batch(batch_id, inputs.frame_ids(batch_id))
+    # (a run too short for one batch still prepares batch 0, as it always did, and then writes nothing)
+    plan = run.plan if run.plan is not None else batch_plan(run.opt)
+    first, count = plan[batch_id] if batch_id < len(plan) else (batch_id * run.opt.n_samples, run.opt.n_samples)
+    b = Batch(batch_id, inputs.frame_ids(batch_id), first, count)
     b.c, b.uc, b.tc = inputs.tokens(batch_id)
     if b.uc is None:    # :423 uc = learnable_vector per frame
-        b.uc = run.model.learnable_vector.detach().float().repeat(run.opt.n_samples, 1, 1)
+        b.uc = run.model.learnable_vector.detach().float().repeat(b.count, 1, 1)
     stage_latents(run, inputs, b)
     b.timer.seconds.update(inputs.own_seconds(batch_id))       # (device work of the provider's own, under its own stage names)
     if run.opt.clip_cond:
@@ -190,10 +241,13 @@ def sample_kwargs(run, b):
     if opt.max_steps is not None:  # smoke runs: the remaining cache entries are never read
         for s in ts:
             b.inv_store.setdefault(s, x_T)
-    return dict(S=opt.ddim_steps, conditioning=b.c, target_conditioning=b.tc, inverse_results_dir=b.inv_store, batch_size=opt.n_samples,
-                shape=[opt.C, h, w], verbose=False, unconditional_guidance_scale=opt.scale, unconditional_conditioning=b.uc,
-                eta=opt.ddim_eta, x_T=x_T, flow=b.flow if opt.fusion == "flow_fix" else None,
-                test_model_kwargs={"inpaint_image": b.z_inp, "inpaint_mask": b.mask}, max_steps=opt.max_steps)
+    kw = dict(S=opt.ddim_steps, conditioning=b.c, target_conditioning=b.tc, inverse_results_dir=b.inv_store, batch_size=b.count,
+              shape=[opt.C, h, w], verbose=False, unconditional_guidance_scale=opt.scale, unconditional_conditioning=b.uc,
+              eta=opt.ddim_eta, x_T=x_T, flow=b.flow if opt.fusion == "flow_fix" else None,
+              test_model_kwargs={"inpaint_image": b.z_inp, "inpaint_mask": b.mask}, max_steps=opt.max_steps)
+    if b.coupled:
+        kw.update(carry=run.carry, boundary_flow=b.boundary_flow)
+    return kw
 
 
 def stage_invert(run, b):
@@ -207,12 +261,18 @@ def stage_sample(run, b, nxt):
     """Sampling; with ``nxt`` (a prepared batch) its inversion runs beside it (DDIMSampler.sample_while_inverting).  Returns the
     stage's wall seconds."""
     name = "sampling" if nxt is None else "sampling_beside_next_inversion"
+    b.coupled = run.carry is not None and run.opt.fusion == "flow_fix" and run.carry.world > 1
+    if b.coupled:
+        run.carry.begin_batch(b.id)
     with b.timer(name):
         if nxt is None:
             b.samples, _ = run.sampler.sample(**sample_kwargs(run, b))
         else:
             (b.samples, _), _ = run.sampler.sample_while_inverting(sample_kwargs(run, b), nxt.invert_kw)
             nxt.inverted = True
+    if b.coupled:
+        b.carry_bytes = run.carry.carry_bytes()
+        run.carry.end_batch()       # (the last batch lets go of the generation it read)
     return b.timer.seconds[name]
 
 
@@ -226,6 +286,8 @@ def stage_paste_back(run, inputs, b):
     """:603-633, into the frames the crops were cut from with the inverse of that cut (:68-71, :625), or into stand-ins."""
     if b.frames is None:
         b.frames, b.inv_transforms = inputs.paste_target(b.id, run.paster.canvas)
+    if run.opt.whole_clip:
+        run.paste_noise = batch_noise(run, b, "paste_back")
     with b.timer("paste_back"):
         b.pasted = run.paster.paste(b.decoded, b.frames, b.inv_transforms)
     return b.timer.seconds["paste_back"]
@@ -233,7 +295,7 @@ def stage_paste_back(run, inputs, b):
 
 def record(run, inputs, b, sample_seconds, paste_seconds, wall_seconds) -> dict:
     keep = run.opt.return_samples
-    rec = {"batch": b.id, "frames": run.opt.n_samples, "sample_seconds": sample_seconds, "batch_wall_seconds": wall_seconds,
+    rec = {"batch": b.id, "frames": b.count, "sample_seconds": sample_seconds, "batch_wall_seconds": wall_seconds,
            "samples": b.samples if keep else None, "labels": b.labels if keep else None,
            "inversion_cache": dict(b.inv_store) if keep else None,
            "finite": bool(torch.isfinite(b.samples).all()) and (b.pixels is None or bool(torch.isfinite(b.pixels).all())),
@@ -243,12 +305,19 @@ def record(run, inputs, b, sample_seconds, paste_seconds, wall_seconds) -> dict:
     of_the_clip = {"frame_ids": b.frame_ids, "pasted_frames": b.pasted if keep else None, "crops": b.crops if keep else None,
                    "conditioning": b.c if keep else None}
     rec.update((key, of_the_clip[key]) for key in inputs.record_keys)
+    if run.opt.whole_clip:      # what the run did at this batch's front boundary, and what it keeps for the next one's
+        rec.update(coupled=b.coupled and b.first > 0, carry_bytes=b.carry_bytes)
     return rec
 
 
 def run_batches(run, inputs, sink) -> dict:
     opt = run.opt
-    nbatches = opt.n_frames // opt.n_samples       # DataLoader(batch_size=n_samples, drop_last=True) (:376-382)
+    run.plan = batch_plan(opt)      # DataLoader(batch_size=n_samples, drop_last=True) (:376-382), or every frame (--whole_clip)
+    nbatches = len(run.plan)
+    if opt.whole_clip:
+        from ..parallel import ClipCarry
+        if nbatches and (run.carry is None or run.carry.batches != run.plan):      # (kept across walks of one clip: its captures are too)
+            run.carry = ClipCarry(run.plan)
     # --pipeline_inversion: the DDIM inversion of batch k + 1 runs beside the sampling of batch k (the batches are independent,
     # :413, :529-553); batch 0's inversion runs alone, the last batch's sampling too
     pipelined = opt.pipeline_inversion and not opt.no_inversion and nbatches > 1
@@ -266,7 +335,7 @@ def run_batches(run, inputs, sink) -> dict:
         sink.write(cur)
         torch.cuda.synchronize()
         results.append(record(run, inputs, cur, sample_seconds, paste_seconds, time.time() - t_batch))
-        print(f"batch {batch_id}: {opt.n_samples} frames sampled in {sample_seconds:.2f} s")
+        print(f"batch {batch_id}: {cur.count} frames sampled in {sample_seconds:.2f} s")
         t_batch = time.time()
         if nxt is None and batch_id + 1 < nbatches:
             nxt = prepare(run, inputs, batch_id + 1)

@@ -32,6 +32,9 @@ class Run:
     id_source: Optional[torch.Tensor] = None    # its identity features (ddpm.py:1010)     --arcface
 
     paste_noise: Optional[torch.Tensor] = None  # the next background round trip's posterior draw, where it was taken ahead
+    plan: Any = None                            # [(first, count)] of the run's batches (inputs.batch_plan), set by the loop
+    carry: Any = None                           # parallel.ClipCarry                       --whole_clip
+    last_image: Optional[torch.Tensor] = None   # the previous batch's last target image, for the boundary flow field
 
     @property
     def latent(self):
