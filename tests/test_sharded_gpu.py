@@ -354,7 +354,7 @@ def _rccl_selfloop(port, outdir):
                 if slot is None or slot.shape != tail.shape:
                     slot = self.store[(self.rank, k)] = torch.empty_like(tail)
                 works += self._move(tail.contiguous(), slot)
-            return ("p2p", works, halo)
+            return self.handle(works, lambda: halo)
 
         def _move(self, src, dst):
             if self.mode == "allgather":

@@ -60,7 +60,7 @@ def main():
             else:
                 works = dist.batch_isend_irecv([dist.P2POp(dist.isend, tail.contiguous(), 0), dist.P2POp(dist.irecv, sink, 0),
                                                 dist.P2POp(dist.isend, self.halos[k], 0), dist.P2POp(dist.irecv, halo, 0)])
-            return ("p2p", works, halo)
+            return self.handle(works, lambda: halo)
 
     F_, h = a.frames, 64
     total = 2 * F_

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import hip, packing
-from .replay import _GraphSegments, _StepReplay
+from .replay import _StepReplay, _between_events
 
 
 @dataclass
@@ -234,7 +234,7 @@ class UNetEngine(_StepReplay):
         self._packed: Dict[str, dict] = {}
         self._maps: Dict[tuple, torch.Tensor] = {}
         self._version = None
-        # multi-GPU: a parallel.FrameShard (start_exchange / finish_exchange), installed by FrameShard.install
+        # the boundary exchange: a parallel.Exchange (ranks, batches of a clip or stream halves), set by parallel.set_boundary
         self.halo_exchange = None
         self.halo_flow: Optional[torch.Tensor] = None  # flow from the previous rank's last frame into our frame 0
         self.halo_hw = None                            # (h, w) of the clip's flow fields (set with halo_exchange)
@@ -781,25 +781,17 @@ class UNetEngine(_StepReplay):
 
     def _halo_start(self, tail: torch.Tensor, kind: str = "exchange"):
         """``halo_exchange.start_exchange`` (``kind`` "temporal" / "gather": ``start_temporal`` / ``start_gather``) with the
-        exchange's ordinal inside this forward stated first (FrameShard.set_index)."""
+        exchange's ordinal inside this forward stated first (Exchange.set_index)."""
         ex = self.halo_exchange
-        k = self._halo_k
-        self._halo_k = k + 1
-        if hasattr(ex, "set_index"):
-            ex.set_index(k)
+        ex.set_index(self._halo_k)
+        self._halo_k += 1
         return getattr(ex, "start_" + kind)(tail)
 
     def _halo_finish(self, handle):
-        """``halo_exchange.finish_exchange``, timed with HIP events when ``exchange_events`` asks for it."""
-        ev = self.exchange_events if not isinstance(self.halo_exchange, _GraphSegments) else None
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        got = self.halo_exchange.finish_exchange(handle)
-        if ev is not None:
-            e1.record()
-            ev.append((e0, e1))
-        return got
+        """``halo_exchange.finish_exchange``, timed with HIP events when ``exchange_events`` asks for it (an exchange that issues
+        its host calls itself, ``times_itself``, also times them)."""
+        ex = self.halo_exchange
+        return _between_events(None if ex.times_itself else self.exchange_events, lambda: ex.finish_exchange(handle))
 
     def _staged_edit(self, mode: str, qkv: torch.Tensor, F_: int, n: int, d: int, chunks: int):
         """The q|k edit of the staged hook modes in the projected ``qkv`` buffer ``[chunks F_ n, 3d]`` (pnp_utils.py:145-160): chunk

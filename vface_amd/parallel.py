@@ -1,4 +1,10 @@
-"""Frame sharding of a clip across the GPUs of one node (one process per GPU, RCCL over xGMI).
+"""The boundary exchange of the hooked ``attn1``: ONE protocol (``Exchange``) for the frames a forward does not hold itself.
+
+``Exchange`` is everything ``UNetEngine`` and ``replay`` call on ``engine.halo_exchange`` (set with ``set_boundary``).  It is implemented
+by ``FrameShard`` (the ranks of a clip over ``torch.distributed``: one process per GPU, RCCL over xGMI), by the in-process one-neighbour
+hand-overs of ``InProcessExchange`` -- ``LoopbackShard`` (ranks one after another), ``ClipCarry`` (the batches of a whole clip,
+``--whole_clip``, planned by ``clip_batches``), ``StreamShard`` (the two frame halves of a batch on two HIP streams) -- and by
+``replay``'s two wrappers around any of these while a hipGraph is captured.
 
 The hot path shards by frame: every rank runs the full 3-way batch for a contiguous range of frames.  FSAI and
 structure injection have no cross-frame dependency.  Three hook modes read other frames, and each has its
@@ -20,9 +26,6 @@ exchange step here, issued between the hooked ``attn1``'s projection and its edi
 
 ``finish_exchange`` completes any of the three (bounded: ``exchange_timeout_s``, ``ExchangeTimeout``).  Under gloo with device
 tensors every form runs through host staging (the rehearsal on a box without one GPU per rank).
-
-The same one-neighbour exchange also couples the BATCHES of a clip on one GPU (``--whole_clip``): ``clip_batches`` is the plan,
-``ClipCarry`` keeps batch k's last-frame slabs of every DDIM step for batch k + 1.
 """
 from __future__ import annotations
 
@@ -68,14 +71,40 @@ def clip_batches(n_frames: int, n_samples: int):
     return [(first, min(n_samples, n_frames - first)) for first in range(0, n_frames, n_samples)]
 
 
-class FrameShard:
-    def __init__(self, rank: int, world: int, total_frames: int, dist=None, mode: str = "p2p"):
+def set_boundary(engine, exchange=None, flow: Optional[torch.Tensor] = None, hw=None, device=None):
+    """Set the engine's three boundary attributes together: ``halo_exchange``, ``halo_flow`` (the field from the frame before
+    the forward's first one into it, made contiguous fp32 on ``device``) and ``halo_hw`` (the (h, w) of the clip's flow fields).
+    With nothing given all three are cleared.  Returns the triple that was there: ``set_boundary(engine, *previous)`` restores it."""
+    previous = (engine.halo_exchange, engine.halo_flow, engine.halo_hw)
+    engine.halo_exchange = exchange
+    engine.halo_flow = None if flow is None else flow.to(device=device, dtype=torch.float32).contiguous()
+    engine.halo_hw = None if hw is None else (int(hw[0]), int(hw[1]))
+    return previous
+
+
+class Exchange:
+    """What ``UNetEngine`` and ``replay`` may call on ``engine.halo_exchange``: the contract of every boundary exchange.
+
+    * Identity: ``rank`` of ``world`` holds frames ``[first, first + count)`` of ``total``.
+    * Position: ``set_index(k)`` before every start; ``capture_pass(on)`` around the capture pass of a hipGraph capture.
+    * The three exchanges, each started with the data to send (and, optionally, a persistent buffer ``recv`` to receive into where
+      the form allows it) and completed by ``finish_exchange(handle)``; handles are opaque to the caller, ``None`` is one:
+      ``start_exchange(tail)`` -> the predecessor's last-frame slab, or None on rank 0 / in a world of one;
+      ``start_temporal(edges)`` -> the two frames before and the two after the range; ``start_gather(part)`` -> every rank's rows, of
+      shape ``gather_shape(part)``.
+    * Capture bookkeeping: ``graph_signature()``, ``agree(ok, over_budget)``, ``drain(pending, remaining)``.
+    * ``times_itself``: the object puts ``engine.exchange_events`` around its own host-issued exchanges; the engine then does not."""
+
+    index = 0
+    times_itself = False
+
+    def __init__(self, rank: int = 0, world: int = 1, total_frames: int = 0):
         self.rank, self.world, self.total = rank, world, total_frames
         self.first, self.count = frame_range(rank, world, total_frames)
-        self.dist = dist
-        self.mode = mode
-        if world > 1 and dist is None:
-            raise ValueError("world_size > 1 needs torch.distributed")
+
+    def adopt_identity(self, inner: "Exchange") -> None:
+        """A wrapper shows the identity of what it wraps."""
+        self.rank, self.world, self.first, self.count, self.total = inner.rank, inner.world, inner.first, inner.count, inner.total
 
     def set_index(self, k: int) -> None:
         """Ordinal of the NEXT exchange inside its UNet forward (0 = the first hooked flow layer, 1 = the second ..): the engine
@@ -104,7 +133,70 @@ class FrameShard:
             return None
         return global_flow[self.first - 1]
 
-    # ---- the boundary exchange
+    def install(self, engine, global_flow: Optional[torch.Tensor] = None, device=None) -> None:
+        """Hook the exchange into a ``UNetEngine``: flow_fix layers use it with the clip's flow fields (``global_flow``
+        ``[total-1, 2, h, w]``), temporal / adaIn layers without any."""
+        flow, hw = (None, None) if global_flow is None else (self.halo_flow(global_flow), global_flow.shape[-2:])
+        set_boundary(engine, self if self.world > 1 else None, flow, hw, device)
+
+    # ---- the three exchanges: every implementation has all of them (one that cannot do a form says so: NotImplementedError)
+    def start_exchange(self, tail: torch.Tensor, recv: Optional[torch.Tensor] = None):
+        raise NotImplementedError
+
+    def start_temporal(self, edges: torch.Tensor, recv: Optional[torch.Tensor] = None):
+        raise NotImplementedError
+
+    def start_gather(self, part: torch.Tensor, recv: Optional[torch.Tensor] = None):
+        raise NotImplementedError
+
+    def gather_shape(self, part: torch.Tensor):
+        """Shape of what ``finish_exchange`` returns for ``start_gather(part)``."""
+        return (int(part.shape[0]), int(part.shape[1]) // self.count * self.total) + tuple(part.shape[2:])
+
+    def finish_exchange(self, handle) -> Optional[torch.Tensor]:
+        raise NotImplementedError
+
+    # ---- one decision for all ranks of a clip (hipGraph capture outcome, ADVICE r3)
+    def agree(self, ok: bool, over_budget: bool = False):
+        """``(every rank ok, any rank over budget)``.  A rank whose capture failed and a rank whose capture succeeded must take ONE
+        decision, or their exchange counts stop pairing.  Here: one process, whose own verdict is everybody's."""
+        return bool(ok), bool(over_budget)
+
+    def drain(self, pending, remaining) -> None:
+        """Finish the paired exchanges of an aborted forward so that the neighbours' calls still match: ``pending`` = a handle
+        that was started and not finished (or None), ``remaining`` = the slabs (tensors shaped like the tails the forward would
+        have sent; contents irrelevant) of the exchanges not yet started -- a ``(kind, tensor)`` pair for a temporal halo or an
+        adaIn gather (kind ``"temporal"`` / ``"gather"``)."""
+        if pending is not None:
+            self.finish_exchange(pending)
+        for tail in remaining:
+            kind, t = tail if isinstance(tail, tuple) else ("exchange", tail)
+            self.finish_exchange(getattr(self, "start_" + kind)(t))
+
+
+class FrameShard(Exchange):
+    """The ranks of a clip over ``torch.distributed``: rank r holds ``frame_range(r, world, total)``."""
+
+    def __init__(self, rank: int, world: int, total_frames: int, dist=None, mode: str = "p2p"):
+        super().__init__(rank, world, total_frames)
+        self.dist = dist
+        self.mode = mode
+        if world > 1 and dist is None:
+            raise ValueError("world_size > 1 needs torch.distributed")
+
+    def _staged(self, t: torch.Tensor):
+        """``(what the backend is handed, the device the result goes back to)``.  gloo cannot move device memory peer to peer: a
+        rehearsal on a box without one GPU per rank runs the same protocol through host staging (a CPU copy, and the device to return
+        to).  Production runs use backend "nccl" (RCCL over xGMI): the tensor itself, and None."""
+        if t.is_cuda and self.dist.get_backend() == "gloo":
+            return t.detach().to("cpu").contiguous(), t.device
+        return t.contiguous(), None
+
+    def handle(self, works, result, peers: Optional[str] = None):
+        """The handle of a started exchange: the works to wait for, ``result()`` -> what ``finish_exchange`` returns once they are
+        done, and whom to name when they are not done in time (default: the flow halo's peers)."""
+        return (works, result, peers)
+
     def start_exchange(self, tail: torch.Tensor, recv: Optional[torch.Tensor] = None):
         """Send this shard's last-frame slab to rank+1 and start receiving rank-1's.  Returns a handle.
         ``recv``: a persistent receive buffer shaped like ``tail`` (the hipGraph-segmented forward bakes its address into
@@ -112,31 +204,18 @@ class FrameShard:
         if self.world == 1:
             return None
         d = self.dist
-        if tail.is_cuda and d.get_backend() == "gloo":
-            # rehearsal on a box without one GPU per rank (gloo cannot move device memory peer to peer): the same
-            # protocol through host staging.  Production runs use backend "nccl" (RCCL over xGMI) below.
-            host = tail.detach().to("cpu").contiguous()
-            ops, halo = [], None
-            if self.rank + 1 < self.world:
-                ops.append(d.P2POp(d.isend, host, self.rank + 1))
-            if self.rank > 0:
-                halo = torch.empty_like(host)
-                ops.append(d.P2POp(d.irecv, halo, self.rank - 1))
-            works = d.batch_isend_irecv(ops) if ops else []
-            return ("host", works, (halo, tail.device))
-        if self.mode == "allgather":
-            t = tail.contiguous()
-            bufs = torch.empty((self.world * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-            work = d.all_gather_into_tensor(bufs, t, async_op=True)  # rank r's slab = rows [r*n, (r+1)*n)
-            return ("ag", work, bufs.view((self.world,) + tuple(t.shape)))
+        src, dev = self._staged(tail)
+        if self.mode == "allgather" and dev is None:
+            bufs = torch.empty((self.world * src.shape[0],) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+            work = d.all_gather_into_tensor(bufs, src, async_op=True)  # rank r's slab = rows [r*n, (r+1)*n)
+            return self.handle([work], lambda: bufs.view((self.world,) + tuple(src.shape))[self.rank - 1] if self.rank > 0 else None)
         ops, halo = [], None
         if self.rank + 1 < self.world:
-            ops.append(d.P2POp(d.isend, tail.contiguous(), self.rank + 1))
+            ops.append(d.P2POp(d.isend, src, self.rank + 1))
         if self.rank > 0:
-            halo = recv if recv is not None else torch.empty_like(tail)
+            halo = recv if (recv is not None and dev is None) else torch.empty_like(src)
             ops.append(d.P2POp(d.irecv, halo, self.rank - 1))
-        works = d.batch_isend_irecv(ops) if ops else []
-        return ("p2p", works, halo)
+        return self.handle(d.batch_isend_irecv(ops), lambda: halo.to(dev) if (halo is not None and dev is not None) else halo)
 
     # ---- the two-directional halo of fusion="temporal" (+-2 frames) and the row-partial gather of fusion="adaIn"
     def temporal_form(self) -> str:
@@ -168,8 +247,7 @@ class FrameShard:
         if self.world == 1:
             return None
         d = self.dist
-        dev = edges.device if (edges.is_cuda and d.get_backend() == "gloo") else None      # host staging (see start_exchange)
-        src = edges.detach().to("cpu").contiguous() if dev is not None else edges.contiguous()
+        src, dev = self._staged(edges)
         if self.temporal_form() == "p2p":
             halo = recv if (recv is not None and dev is None) else torch.empty_like(src)
             ops = []
@@ -178,10 +256,18 @@ class FrameShard:
             if self.rank + 1 < self.world:
                 ops += [d.P2POp(d.isend, src[2:4], self.rank + 1), d.P2POp(d.irecv, halo[2:4], self.rank + 1)]
             peers = " and ".join(f"rank {q}" for q in (self.rank - 1, self.rank + 1) if 0 <= q < self.world) + " (their edge frames)"
-            return ("temporal", d.batch_isend_irecv(ops), (halo, None, dev, peers))
+            return self.handle(d.batch_isend_irecv(ops), lambda: halo.to(dev) if dev is not None else halo, peers)
         bufs = torch.empty((self.world * 4,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
         work = d.all_gather_into_tensor(bufs, src, async_op=True)       # rank q's edge slots = rows [4q, 4q + 4)
-        return ("temporal", [work], (None, bufs, dev, f"all {self.world} ranks (all-gather of edge frames)"))
+
+        def pick():
+            halo = torch.empty((4,) + tuple(bufs.shape[1:]), dtype=bufs.dtype, device=bufs.device)
+            for s, g in enumerate(self.halo_frames()):
+                if g is not None:
+                    q, slot = self._edge_slot(g)
+                    halo[s].copy_(bufs[4 * q + slot])
+            return halo.to(dev) if dev is not None else halo
+        return self.handle([work], pick, f"all {self.world} ranks (all-gather of edge frames)")
 
     def start_gather(self, part: torch.Tensor, recv: Optional[torch.Tensor] = None):
         """Start the gather of adaIn row partials: ``part`` ``[P, count * n, 2]`` fp64 (P arrays of this shard's rows).
@@ -193,19 +279,20 @@ class FrameShard:
         P, rows = int(part.shape[0]), int(part.shape[1])
         n = rows // self.count
         most = frame_range(0, self.world, self.total)[1] * n
-        dev = part.device if (part.is_cuda and d.get_backend() == "gloo") else None
-        src = part.detach().to("cpu") if dev is not None else part
+        src, dev = self._staged(part)
         if rows < most:
             src = torch.cat([src, torch.zeros((P, most - rows) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)], 1)
-        src = src.contiguous()
-        bufs = torch.empty((self.world * P,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
-        work = d.all_gather_into_tensor(bufs, src, async_op=True)       # rank q's arrays = rows [qP, (q + 1)P)
-        return ("gather", [work], (bufs.view((self.world, P) + tuple(src.shape[1:])), n, dev,
-                                   f"all {self.world} ranks (all-gather of adaIn row partials)"))
+        flat = torch.empty((self.world * P,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+        work = d.all_gather_into_tensor(flat, src, async_op=True)       # rank q's arrays = rows [qP, (q + 1)P)
+        bufs = flat.view((self.world, P) + tuple(src.shape[1:]))
 
-    def gather_shape(self, part: torch.Tensor):
-        """Shape of what ``finish_exchange`` returns for ``start_gather(part)``."""
-        return (int(part.shape[0]), int(part.shape[1]) // self.count * self.total) + tuple(part.shape[2:])
+        def assemble():
+            out = torch.empty((P, self.total * n) + tuple(bufs.shape[3:]), dtype=bufs.dtype, device=bufs.device)
+            for q in range(self.world):
+                f, c = frame_range(q, self.world, self.total)
+                out[:, f * n:(f + c) * n].copy_(bufs[q, :, :c * n])
+            return out.to(dev) if dev is not None else out
+        return self.handle([work], assemble, f"all {self.world} ranks (all-gather of adaIn row partials)")
 
     def _peers(self) -> str:
         peers = ([f"rank {self.rank - 1} (its last-frame slab)"] if self.rank > 0 else []) + \
@@ -218,7 +305,7 @@ class FrameShard:
         unless ``VFACE_EXCHANGE_BLOCKING=1`` asks for host polling.  ``peers``: whom the exchange waits for, named in the
         ``ExchangeTimeout`` message (default: the flow halo's peers)."""
         limit = exchange_timeout_s()
-        backend = self.dist.get_backend() if hasattr(self.dist, "get_backend") else "gloo"
+        backend = self.dist.get_backend()
         poll = backend != "gloo" and os.environ.get("VFACE_EXCHANGE_BLOCKING") == "1"
         import time
         t0 = time.monotonic()
@@ -248,39 +335,12 @@ class FrameShard:
         the peer when it does not arrive."""
         if handle is None:
             return None
-        kind, work, buf = handle
-        if kind == "temporal":
-            halo, bufs, dev, peers = buf
-            self._wait(work, peers)
-            if bufs is not None:
-                halo = torch.empty((4,) + tuple(bufs.shape[1:]), dtype=bufs.dtype, device=bufs.device)
-                for s, g in enumerate(self.halo_frames()):
-                    if g is not None:
-                        q, slot = self._edge_slot(g)
-                        halo[s].copy_(bufs[4 * q + slot])
-            return halo.to(dev) if dev is not None else halo
-        if kind == "gather":
-            bufs, n, dev, peers = buf
-            self._wait(work, peers)
-            out = torch.empty((bufs.shape[1], self.total * n) + tuple(bufs.shape[3:]), dtype=bufs.dtype, device=bufs.device)
-            for q in range(self.world):
-                f, c = frame_range(q, self.world, self.total)
-                out[:, f * n:(f + c) * n].copy_(bufs[q, :, :c * n])
-            return out.to(dev) if dev is not None else out
-        if kind == "host":
-            self._wait(work)
-            halo, dev = buf
-            return halo.to(dev) if halo is not None else None
-        if kind == "ag":
-            self._wait([work])
-            return buf[self.rank - 1] if self.rank > 0 else None
-        self._wait(work)
-        return buf
+        works, result, peers = handle
+        self._wait(works, peers)
+        return result()
 
-    # ---- one decision for all ranks of a clip (hipGraph capture outcome, ADVICE r3)
     def agree(self, ok: bool, over_budget: bool = False):
-        """All-reduce two flags over the ranks of the clip: returns ``(every rank ok, any rank over budget)``.  A rank whose
-        capture failed and a rank whose capture succeeded must take ONE decision, or their exchange counts stop pairing."""
+        """All-reduce the two flags over the ranks of the clip."""
         if self.world == 1:
             return bool(ok), bool(over_budget)
         d = self.dist
@@ -290,46 +350,50 @@ class FrameShard:
         bad, over = (int(v) for v in t.cpu())
         return bad == 0, over != 0
 
-    def drain(self, pending, remaining) -> None:
-        """Finish the paired exchanges of an aborted forward so that the neighbours' calls still match: ``pending`` = a handle
-        that was started and not finished (or None), ``remaining`` = the slabs (tensors shaped like the tails the forward would
-        have sent; contents irrelevant) of the exchanges not yet started -- a ``(kind, tensor)`` pair for a temporal halo or an
-        adaIn gather (kind ``"temporal"`` / ``"gather"``)."""
-        if pending is not None:
-            self.finish_exchange(pending)
-        for tail in remaining:
-            if isinstance(tail, tuple):
-                kind, t = tail
-                self.finish_exchange(getattr(self, "start_" + kind)(t))
-            else:
-                self.finish_exchange(self.start_exchange(tail))
-
     def slab_bytes_per_step(self, n: int, d: int, layers: int = 2, elem: int = 2) -> int:
         """Bytes this rank SENDS per DDIM step: one ``[n, 2d]`` slab per hooked level-0 layer (none from the last rank)."""
         return 0 if self.rank + 1 >= self.world else layers * n * 2 * d * elem
 
-    def install(self, engine, global_flow: Optional[torch.Tensor] = None, device=None) -> None:
-        """Hook the exchange into a ``UNetEngine``: flow_fix layers use it with the clip's flow fields (``global_flow``
-        ``[total-1, 2, h, w]``), temporal / adaIn layers without any."""
-        if global_flow is None:
-            engine.halo_flow, engine.halo_hw = None, None
-            engine.halo_exchange = self if self.world > 1 else None
-            return
-        hf = self.halo_flow(global_flow)
-        engine.halo_flow = hf.to(device=device, dtype=torch.float32).contiguous() if hf is not None else None
-        engine.halo_exchange = self if self.world > 1 else None
-        engine.halo_hw = (int(global_flow.shape[-2]), int(global_flow.shape[-1]))
+
+class InProcessExchange(Exchange):
+    """A one-neighbour hand-over inside ONE process: whoever is at ``rank`` leaves its last-frame slab under a key, its successor
+    fetches the slab its predecessor left under the same key.  The chain has no cycle (rank 0 needs nothing).  A subclass says what
+    the key is (``_key``), where a slab is put (``_put``) and where the predecessor's is fetched (``_fetch``), and why nothing
+    but the one neighbour behind can be served (``one_neighbour_only``: the temporal halo and the adaIn gather are refused)."""
+
+    last_stores = False         # whether the last rank's slabs, which nobody reads, are put too
+
+    def start_exchange(self, tail: torch.Tensor, recv=None):
+        if self.world == 1:
+            return None
+        key = self._key()
+        if self.rank + 1 < self.world or self.last_stores:
+            self._put(key, tail)
+        return (key,)
+
+    def finish_exchange(self, handle):
+        if handle is None or self.rank == 0:
+            return None
+        return self._fetch(handle[0])
+
+    def start_temporal(self, edges, recv=None):
+        raise NotImplementedError(self.one_neighbour_only)
+
+    start_gather = start_temporal
 
 
-class LoopbackShard(FrameShard):
+class LoopbackShard(InProcessExchange):
     """All shards of a clip run ONE AFTER ANOTHER in one process on one GPU: rank r's boundary slabs are kept in memory
-    (in call order -- one per hooked level-0 layer and UNet call) and handed to rank r+1 when it runs.  The chain has
-    no cycle (rank 0 needs nothing), so running the ranks in order needs no concurrency.  Same engine code path as the
-    RCCL exchange (``UNetEngine._attn1_att``), which makes it the strict bit-for-bit test of that path
-    (tests/test_sharded_gpu.py) and a way to walk a clip that does not fit one batch through one GPU."""
+    (in call order -- one per hooked level-0 layer and UNet call) and handed to rank r+1 when it runs, so running the ranks in
+    order needs no concurrency.  Same engine code path as the RCCL exchange (``UNetEngine._attn1_att``), which makes it the strict
+    bit-for-bit test of that path (tests/test_sharded_gpu.py) and a way to walk a clip that does not fit one batch through one GPU."""
+
+    one_neighbour_only = ("a loop-back shard runs the ranks one after another: the temporal halo needs the NEXT rank's frames too, "
+                          "the adaIn gather every rank's rows (run the shards as processes: FrameShard)")
+    last_stores = True          # (every rank's list then counts the exchanges of its forward)
 
     def __init__(self, rank: int, world: int, total_frames: int, store: dict):
-        super().__init__(rank, world, total_frames, dist=object() if world > 1 else None)
+        super().__init__(rank, world, total_frames)
         self.store = store          # {rank: [slab, ...]} shared by the shards of one clip
         self.store.setdefault(rank, [])
         self._next = 0
@@ -339,32 +403,18 @@ class LoopbackShard(FrameShard):
         self.store[self.rank] = []
         self._next = 0
 
-    def start_exchange(self, tail: torch.Tensor, recv=None):
-        if self.world == 1:
-            return None
+    def _key(self):
+        return self._next           # call order
+
+    def _put(self, key, tail):
         self.store[self.rank].append(tail.detach().clone())
-        i = self._next
         self._next += 1
-        return ("loop", i, None)
 
-    def finish_exchange(self, handle):
-        if handle is None or self.rank == 0:
-            return None
-        return self.store[self.rank - 1][handle[1]]
-
-    def start_temporal(self, edges, recv=None):
-        raise NotImplementedError("a loop-back shard runs the ranks one after another: the temporal halo needs the NEXT rank's "
-                                  "frames too (run the shards as processes: FrameShard)")
-
-    def start_gather(self, part, recv=None):
-        raise NotImplementedError("a loop-back shard runs the ranks one after another: the adaIn gather needs every rank's rows "
-                                  "(run the shards as processes: FrameShard)")
-
-    def agree(self, ok: bool, over_budget: bool = False):
-        return bool(ok), bool(over_budget)      # one process: its own verdict is everybody's
+    def _fetch(self, key):
+        return self.store[self.rank - 1][key]
 
 
-class ClipCarry(FrameShard):
+class ClipCarry(InProcessExchange):
     """The batches of ONE clip walked one after another through one GPU, each through its whole DDIM loop, with ``flow_fix``
     coupled across the batch boundaries: batch k keeps its last frame's fused q|k slab of EVERY step and hooked level-0 layer,
     batch k + 1 reads them where the unbatched clip reads the frame before.  One object per clip; ``begin_batch(k)`` moves it to
@@ -383,17 +433,18 @@ class ClipCarry(FrameShard):
     * Reading a key the previous batch never wrote (it ran fewer steps, or another hook plan) raises, naming step and ordinal.
     * ``temporal`` needs the NEXT batch's frames and ``adaIn`` every frame of the clip: both raise, as on a loop-back shard."""
 
+    one_neighbour_only = ("a clip carry runs the batches one after another: the temporal halo needs the NEXT batch's frames too, "
+                          "the adaIn gather every frame of the clip")
+
     def __init__(self, batches):
         self.batches = [(int(f), int(c)) for f, c in batches]
         if not self.batches:
             raise ValueError("ClipCarry: a clip has at least one batch")
-        self.rank, self.world, self.total = 0, len(self.batches), sum(c for _, c in self.batches)
-        self.dist, self.mode = None, "carry"          # (one process: no collective backend)
+        super().__init__(0, len(self.batches), sum(c for _, c in self.batches))      # (first / count: begin_batch)
         self._capturing = False
         self.generations: dict = {}     # batch -> {(step, ordinal): slab}
         self._spare: list = []          # slabs of dropped generations, re-used as buffers
         self.step: Optional[int] = None
-        self.index = 0
         self.begin_batch(0)
 
     def begin_batch(self, k: int) -> None:
@@ -429,38 +480,23 @@ class ClipCarry(FrameShard):
             raise RuntimeError("ClipCarry: the sampler has to state the DDIM step (set_step) before a UNet forward that exchanges")
         return (self.step, int(self.index))
 
-    def start_exchange(self, tail: torch.Tensor, recv=None):
-        if self.world == 1:
-            return None
-        key = self._key()
-        if self.rank + 1 < self.world and not self._capturing:
-            gen = self.generations[self.rank]
-            slot = gen.get(key)
-            if slot is None or slot.shape != tail.shape or slot.dtype != tail.dtype or slot.device != tail.device:
-                at = next((i for i, s in enumerate(self._spare)
-                           if s.shape == tail.shape and s.dtype == tail.dtype and s.device == tail.device), None)
-                slot = gen[key] = self._spare.pop(at) if at is not None else torch.empty_like(tail, memory_format=torch.contiguous_format)
-            slot.copy_(tail)        # (stream-ordered, on the stream of the forward; a second start for this key lands here again)
-        return ("carry", key, None)
+    def _put(self, key, tail):
+        if self._capturing:
+            return
+        gen = self.generations[self.rank]
+        slot = gen.get(key)
+        if slot is None or slot.shape != tail.shape or slot.dtype != tail.dtype or slot.device != tail.device:
+            at = next((i for i, s in enumerate(self._spare)
+                       if s.shape == tail.shape and s.dtype == tail.dtype and s.device == tail.device), None)
+            slot = gen[key] = self._spare.pop(at) if at is not None else torch.empty_like(tail, memory_format=torch.contiguous_format)
+        slot.copy_(tail)        # (stream-ordered, on the stream of the forward; a second start for this key lands here again)
 
-    def finish_exchange(self, handle):
-        if handle is None or self.rank == 0:
-            return None
-        step, ordinal = handle[1]
-        slab = self.generations.get(self.rank - 1, {}).get((step, ordinal))
+    def _fetch(self, key):
+        slab = self.generations.get(self.rank - 1, {}).get(key)
         if slab is None:
-            raise KeyError(f"ClipCarry: batch {self.rank} reads the slab of DDIM step {step}, exchange ordinal {ordinal}, which batch "
+            raise KeyError(f"ClipCarry: batch {self.rank} reads the slab of DDIM step {key[0]}, exchange ordinal {key[1]}, which batch "
                            f"{self.rank - 1} never wrote (it ran fewer steps, or with another hook plan)")
         return slab
-
-    def start_temporal(self, edges, recv=None):
-        raise NotImplementedError("a clip carry runs the batches one after another: the temporal halo needs the NEXT batch's frames too")
-
-    def start_gather(self, part, recv=None):
-        raise NotImplementedError("a clip carry runs the batches one after another: the adaIn gather needs every frame of the clip")
-
-    def agree(self, ok: bool, over_budget: bool = False):
-        return bool(ok), bool(over_budget)      # one process: its own verdict is everybody's
 
     def carry_bytes(self) -> int:
         """Bytes of the generation being written: what this batch hands to the next one."""
@@ -476,24 +512,19 @@ class ClipCarry(FrameShard):
         batch's last frame into this batch's frame 0 (batch 0: None); ``hw``: the (h, w) of the clip's flow fields.  A clip of one
         batch has no boundary: nothing is installed."""
         if self.world == 1:
-            engine.halo_exchange, engine.halo_flow, engine.halo_hw = None, None, None
+            set_boundary(engine)
             return
         if self.rank > 0 and boundary_flow is None:
             raise ValueError(f"ClipCarry: batch {self.rank} needs the flow field from the previous batch's last frame into its frame 0")
-        if self.rank == 0 or boundary_flow is None:
-            engine.halo_flow = None
-        else:
-            engine.halo_flow = boundary_flow.reshape(2, boundary_flow.shape[-2], boundary_flow.shape[-1]).to(
-                device=device, dtype=torch.float32).contiguous()
-        engine.halo_exchange = self
-        engine.halo_hw = (int(hw[0]), int(hw[1]))
+        flow = boundary_flow.reshape(2, boundary_flow.shape[-2], boundary_flow.shape[-1]) if self.rank > 0 else None
+        set_boundary(engine, self, flow, hw, device)
 
     @staticmethod
     def uninstall(engine) -> None:
-        engine.halo_exchange, engine.halo_flow, engine.halo_hw = None, None, None
+        set_boundary(engine)
 
 
-class StreamShard(FrameShard):
+class StreamShard(InProcessExchange):
     """The two frame halves of ONE batch on one GPU as two shards that run AT THE SAME TIME on two HIP streams (the engine's two
     launch streams under ``flow_fix``, whose warp reads the previous frame: UNetEngine._step_forward_split).  Half 0 hands the
     fused q|k of its last frame to half 1 at every hooked flow layer, through device memory and an event:
@@ -515,39 +546,34 @@ class StreamShard(FrameShard):
     * every stream-ordered call here goes to ``torch.cuda.current_stream()``: the warm-up forward of a capture runs on a side
       stream, the capture pass's real exchanges on the capturing stream, replays on the half's launch stream."""
 
+    one_neighbour_only = ("the halves of a batch on two streams hand one frame forward: the temporal halo needs the NEXT half's frames "
+                          "too, the adaIn gather every frame's rows (such a batch runs whole)")
+
     def __init__(self, rank: int, world: int, total_frames: int, shared: dict):
-        super().__init__(rank, world, total_frames, dist=object() if world > 1 else None)
+        super().__init__(rank, world, total_frames)
         self.shared = shared            # {"slots": {(rank, k): tensor}, "events": {(rank, k): Event}} of the batch's shards
         self.shared.setdefault("slots", {})
         self.shared.setdefault("events", {})
-        self.index = 0
 
-    def start_exchange(self, tail: torch.Tensor, recv=None):
-        if self.world == 1:
-            return None
-        k = self.index
-        if self.rank + 1 < self.world:
-            key = (self.rank, k)
-            slot = self.shared["slots"].get(key)
-            if slot is None or slot.shape != tail.shape or slot.dtype != tail.dtype:
-                slot = self.shared["slots"][key] = torch.empty(tail.shape, dtype=tail.dtype, device=tail.device)
-            slot.copy_(tail)
-            ev = self.shared["events"].get(key)
-            if ev is None:
-                ev = self.shared["events"][key] = torch.cuda.Event()
-            ev.record()                                   # on the current stream, behind the copy
-        return ("stream", k, None)
+    def _key(self):
+        return self.index               # the ordinal, as stated
 
-    def finish_exchange(self, handle):
-        if handle is None or self.rank == 0:
-            return None
-        key = (self.rank - 1, handle[1])
+    def _put(self, k, tail):
+        key = (self.rank, k)
+        slot = self.shared["slots"].get(key)
+        if slot is None or slot.shape != tail.shape or slot.dtype != tail.dtype:
+            slot = self.shared["slots"][key] = torch.empty(tail.shape, dtype=tail.dtype, device=tail.device)
+        slot.copy_(tail)
         ev = self.shared["events"].get(key)
         if ev is None:
-            raise RuntimeError(f"StreamShard: half {self.rank} reached exchange {handle[1]} before half {self.rank - 1} issued it "
+            ev = self.shared["events"][key] = torch.cuda.Event()
+        ev.record()                                   # on the current stream, behind the copy
+
+    def _fetch(self, k):
+        key = (self.rank - 1, k)
+        ev = self.shared["events"].get(key)
+        if ev is None:
+            raise RuntimeError(f"StreamShard: half {self.rank} reached exchange {k} before half {self.rank - 1} issued it "
                                "(the halves must be enqueued in order)")
         torch.cuda.current_stream().wait_event(ev)
         return self.shared["slots"][key]
-
-    def agree(self, ok: bool, over_budget: bool = False):
-        return bool(ok), bool(over_budget)      # one process; a half that runs eagerly still makes the same exchange calls

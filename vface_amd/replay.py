@@ -1,7 +1,11 @@
 """How the UNet forward of a DDIM step reaches the device: kernel by kernel, as a captured hipGraph (in segments cut where a
 frame-sharded forward exchanges with its neighbours), or as two frame halves on two HIP streams at once -- with the overlap probe,
 the bit self-check and the both-ways timing that decide whether an engine keeps that form.  ``UNetEngine`` (engine.py), which
-inherits from ``_StepReplay``, says what one forward computes; no kernel is called from this file."""
+inherits from ``_StepReplay``, says what one forward computes; no kernel is called from this file.
+
+The boundary exchange is spoken to through ``parallel.Exchange`` alone.  Two implementations of it live here, both wrappers around
+the engine's own exchange while a hipGraph is captured: ``_CountingExchange`` (the warm-up forward) and ``_GraphSegments`` (the
+capture pass, and the host calls of every replay)."""
 from __future__ import annotations
 
 import gc
@@ -12,6 +16,7 @@ from typing import Dict, Optional
 import torch
 
 from . import hip
+from .parallel import Exchange, StreamShard, set_boundary
 
 
 def _timed(cur, fn):
@@ -24,7 +29,20 @@ def _timed(cur, fn):
     return e0.elapsed_time(e1), out
 
 
-class _GraphSegments:
+def _between_events(events, fn):
+    """``fn()`` -- one ``finish_exchange`` -- with a (start, end) pair of HIP events around what it enqueues on the current stream,
+    appended to ``events`` (the engine's ``exchange_events``: a list, or None: not timed)."""
+    if events is None:
+        return fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    events.append((e0, e1))
+    return out
+
+
+class _GraphSegments(Exchange):
     """Capture of one UNet forward as a chain of hipGraphs sharing ONE memory pool, cut wherever the forward calls the
     frame-shard exchange (``start_exchange`` / ``finish_exchange``): those two calls are host-issued RCCL operations and run
     BETWEEN segment replays, on the same stream, in the captured order.  Installed as the engine's ``halo_exchange`` while
@@ -33,6 +51,8 @@ class _GraphSegments:
     receives straight into it where it can -- RCCL p2p -- otherwise its result is copied there).
     An unsharded forward is the degenerate case: one segment, no host call."""
 
+    times_itself = True           # (its host calls run at every replay, where the engine's own timing is not on the path)
+
     def __init__(self, engine, inner):
         self.engine, self.inner = engine, inner
         self.stream = torch.cuda.Stream()
@@ -40,13 +60,10 @@ class _GraphSegments:
         self.segments: list = []      # [(CUDAGraph, host_op | None)]
         self.keep: list = []          # tensors the host ops refer to
         self.cur = None
-        self.index = 0                # ordinal of the next exchange inside the forward (stated by the engine: FrameShard.set_index)
         self.n_started = 0            # exchanges the capture pass has started for real ..
         self.pending = None           # .. and the state dict of one that was started and not yet finished
-        # what the engine reads from its exchange object
         if inner is not None:
-            self.rank, self.world, self.first, self.count = inner.rank, inner.world, inner.first, inner.count
-            self.total = getattr(inner, "total", None)
+            self.adopt_identity(inner)
 
     def begin(self):
         self.cur = torch.cuda.CUDAGraph()
@@ -80,19 +97,17 @@ class _GraphSegments:
                 pass
             self.cur = None
 
-    # ---- the exchange interface (parallel.FrameShard), as seen by UNetEngine._attn1_att while capturing
-    def set_index(self, k: int) -> None:
-        self.index = int(k)
-
-    def start_exchange(self, tail: torch.Tensor):
+    # ---- the exchange interface (parallel.Exchange), as seen by UNetEngine._attn1_att while capturing: the ordinal the engine
+    # states (set_index) is baked into the host call; ``recv`` is this object's to choose
+    def start_exchange(self, tail: torch.Tensor, recv=None):
         recv = torch.empty_like(tail) if self.inner.rank > 0 else None      # (allocated in the shared pool: lives with the graphs)
         return self._start("start_exchange", tail, recv)
 
-    def start_temporal(self, edges: torch.Tensor):
+    def start_temporal(self, edges: torch.Tensor, recv=None):
         """The temporal halo (``FrameShard.start_temporal``): every rank receives (frames on both sides)."""
         return self._start("start_temporal", edges, torch.empty_like(edges))
 
-    def start_gather(self, part: torch.Tensor):
+    def start_gather(self, part: torch.Tensor, recv=None):
         """The adaIn row-partial gather (``FrameShard.start_gather``): the gathered array lands in a persistent buffer."""
         return self._start("start_gather", part, torch.empty(self.inner.gather_shape(part), dtype=part.dtype, device=part.device))
 
@@ -101,8 +116,7 @@ class _GraphSegments:
         self.keep += [tail, recv, state]
 
         def op():
-            if hasattr(inner, "set_index"):
-                inner.set_index(k)                 # (the replayed host call states the same ordinal as the captured forward did)
+            inner.set_index(k)                     # (the replayed host call states the same ordinal as the captured forward did)
             state["h"] = getattr(inner, method)(tail, recv=recv)
         self.end(op)
         op()                       # the capture pass exchanges for real too (garbage slabs): the ranks' calls stay paired
@@ -117,17 +131,11 @@ class _GraphSegments:
         if os.environ.get("VFACE_TEST_FAIL_CAPTURE") == "mid":      # (test hook: die with one exchange started, not finished)
             raise RuntimeError("injected capture failure (VFACE_TEST_FAIL_CAPTURE)")
 
-        def op():
-            ev = eng.exchange_events
-            if ev is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
+        def finish():
             halo = inner.finish_exchange(state.pop("h"))
             if halo is not None and recv is not None and halo.data_ptr() != recv.data_ptr():
                 recv.copy_(halo)
-            if ev is not None:
-                e1.record()
-                ev.append((e0, e1))
+        op = lambda: _between_events(eng.exchange_events, finish)
         self.end(op)
         op()
         self.pending = None
@@ -135,22 +143,20 @@ class _GraphSegments:
         return recv
 
 
-class _CountingExchange:
+class _CountingExchange(Exchange):
     """The frame-shard exchange seen by the warm-up forward of a capture: passes every call through and records the slabs a
-    forward sends (shapes only), so that a capture pass that dies half-way can finish its paired exchanges (``FrameShard.drain``)."""
+    forward sends (shapes only), so that a capture pass that dies half-way can finish its paired exchanges (``Exchange.drain``)."""
 
     def __init__(self, inner):
         self.inner, self.tails = inner, []
-        self.rank, self.world, self.first, self.count = inner.rank, inner.world, inner.first, inner.count
-        self.total = getattr(inner, "total", None)
+        self.adopt_identity(inner)
 
     def set_index(self, k: int) -> None:
-        if hasattr(self.inner, "set_index"):
-            self.inner.set_index(k)
+        self.inner.set_index(k)
 
     def start_exchange(self, tail, recv=None):
         self.tails.append(tail)
-        return self.inner.start_exchange(tail, recv=recv) if recv is not None else self.inner.start_exchange(tail)
+        return self.inner.start_exchange(tail, recv=recv)
 
     def start_temporal(self, edges, recv=None):
         self.tails.append(("temporal", edges))
@@ -366,7 +372,6 @@ class _StepReplay:
         """flow_fix: the halves as two in-process frame shards (parallel.StreamShard).  Per half: its own exchange object, the flow
         fields between ITS frames, and -- half 1 -- the field from half 0's last frame into its first.  The slices are kept
         (one object per flow tensor and half): the graphs' private flow copies are refreshed by tensor identity."""
-        from .parallel import StreamShard
         fl = coupled[0].flow
         F_all = fl.shape[0] + 1
         fkey = (id(fl), fl._version)
@@ -385,16 +390,16 @@ class _StepReplay:
         the engine's exchange attributes and the cfgs' flow restored afterwards); join on ``cur``.  ``ev``: the overlap probe's events, or None."""
         from .engine import Act
         outs = []
-        saved = (self.halo_exchange, self.halo_flow, self.halo_hw, [(c, c.flow) for c in (coupled or [])])
+        flows = [(c, c.flow) for c in (coupled or [])]
+        saved = set_boundary(self)      # (no exchange is installed on an engine that splits: _split_decide)
         try:
             for h, idx in enumerate(plan):
                 s = st["streams"][h]
                 s.wait_stream(cur)
                 if halves is not None:
                     shard, lflow, hflow = halves[h]
-                    self.halo_exchange, self.halo_flow = shard, hflow
-                    self.halo_hw = (int(saved[3][0][1].shape[-2]), int(saved[3][0][1].shape[-1]))
-                    for c, _ in saved[3]:
+                    set_boundary(self, shard, hflow, flows[0][1].shape[-2:])
+                    for c, _ in flows:
                         c.flow = lflow
                 with torch.cuda.stream(s), hip.workspace_domain(h + 1):
                     if ev is not None:
@@ -403,8 +408,8 @@ class _StepReplay:
                     if ev is not None:
                         ev[2 + 2 * h].record(s)
         finally:
-            self.halo_exchange, self.halo_flow, self.halo_hw = saved[0], saved[1], saved[2]
-            for c, f in saved[3]:
+            set_boundary(self, *saved)
+            for c, f in flows:
                 c.flow = f
         for s in st["streams"]:
             cur.wait_stream(s)
@@ -477,8 +482,8 @@ class _StepReplay:
         [warp, attention, .. next hooked layer ..] -- with the two ``isend/irecv`` + ``wait`` pairs issued from the host between
         segment replays (5 segments and 4 host calls per step instead of ~1200 launches).  A capture failure (or a pool
         over the byte budget) runs the eager path for that configuration -- decided ONCE for all ranks of a sharded clip
-        (``FrameShard.agree``), the failing rank first completing the exchanges its aborted pass owed its neighbours
-        (``FrameShard.drain``), and the capturing call returns the warm-up forward's eps instead of running a further forward."""
+        (``Exchange.agree``), the failing rank first completing the exchanges its aborted pass owed its neighbours
+        (``Exchange.drain``), and the capturing call returns the warm-up forward's eps instead of running a further forward."""
         if not self.use_graph or x.t32 is not None:
             return self.forward_nhwc(x, timesteps, context)
         self._ensure_packed()
@@ -542,9 +547,8 @@ class _StepReplay:
         real_exchange, real_halo_flow = self.halo_exchange, self.halo_flow
         own_halo_flow = real_halo_flow.clone() if (real_exchange is not None and real_halo_flow is not None) else None
         seg, eps_warm, counting, ok, pool_bytes = None, None, None, True, 0
+        saved = set_boundary(self, real_exchange, real_halo_flow if own_halo_flow is None else own_halo_flow, self.halo_hw)
         try:
-            if own_halo_flow is not None:
-                self.halo_flow = own_halo_flow
             a2 = self.context_projections(context, x.N).clone()
             self._a2_cache = (context, context._version, self._packed, a2)
             for c in cfgs:
@@ -571,7 +575,7 @@ class _StepReplay:
             seg = _GraphSegments(self, real_exchange)
             if real_exchange is not None:
                 self.halo_exchange = seg             # start_exchange / finish_exchange cut the capture (see _GraphSegments)
-                real_exchange.capture_pass(True)     # (the slabs this pass hands over hold no data: FrameShard.capture_pass)
+                real_exchange.capture_pass(True)     # (the slabs this pass hands over hold no data: Exchange.capture_pass)
             # No garbage collection inside the capture pass: a cycle collected there can release device objects of an earlier
             # configuration (its graphs, their pool, events), and releasing them while this thread captures is a fatal runtime
             # error, not a Python exception.  Collected above, as ``torch.cuda.graph`` does; the collector stays off until the end.
@@ -604,14 +608,14 @@ class _StepReplay:
                 done = seg.n_started if seg is not None else 0
                 real_exchange.drain(st.pop("h", None) if st else None, counting.tails[done:])
         finally:
-            self.halo_exchange, self.halo_flow = real_exchange, real_halo_flow
+            set_boundary(self, *saved)
             if real_exchange is not None:
                 real_exchange.capture_pass(False)
             for c, f in zip(cfgs, saved_flows):
                 c.flow = f
             self._a2_cache = saved_cache
         over = ok and pool_bytes > self.graph_budget_bytes      # one forward larger than the whole budget: do not pin it
-        if real_exchange is not None and hasattr(real_exchange, "agree"):
+        if real_exchange is not None:
             # ONE decision for the ranks of a clip (pool_bytes follows each rank's own frame count): a rank that replays
             # segments and a rank that launches eagerly would still pair, but a rank that RE-RUNS the forward would not
             all_ok, any_over = real_exchange.agree(ok, over)
