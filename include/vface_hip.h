@@ -306,7 +306,7 @@ int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out,
 /* ---- video mux, colour half (REFace/scripts/VFace_inference_batch.py:646-654) ------------------------------------------------
  * The reference writes the pasted frames as PNG (:636) and asks ffmpeg for `-pix_fmt yuv420p -colorspace bt709 -color_range tv`
  * at 10 fps (:646-654); swscale converts on the host.  vface_rgb_to_yuv420 makes that conversion on the device, so the host
- * receives 1.5 bytes per pixel instead of 3 (vface_amd/scripts/mux.py writes them as YUV4MPEG2; H.264 and audio are not built).
+ * receives 1.5 bytes per pixel instead of 3 (vface_amd/scripts/mux.py writes them as YUV4MPEG2; H.264 and audio are not built; Motion-JPEG: below).
  *   rgb [frames][H][W][3], the layout the paste-back returns -> out: one I420 frame per frame, frame f at out + f * frame_stride:
  *   Y [H][W], Cb [ch][cw], Cr [ch][cw], cw = (W + 1) / 2, ch = (H + 1) / 2.  Bytes between frames are not written.
  *   Integer arithmetic, stated once in tests/mux_model.py and equal to it bit for bit: 16-bit BT.709 limited-range coefficients,
@@ -314,6 +314,37 @@ int vface_frame_normalise_resize(const uint8_t* frame, int W, int H, float* out,
  *   may be odd; no alignment is required of either pointer or of frame_stride.
  *   NULL pointer, W, H or frames <= 0: VFACE_ERR_ARG; frame_stride < W * H + 2 * cw * ch: VFACE_ERR_SHAPE -- before the first HIP call. */
 int vface_rgb_to_yuv420(const uint8_t* rgb, int W, int H, uint8_t* out, int64_t frame_stride, int frames, void* stream);
+
+/* ---- video mux, compressed: baseline JPEG per frame (REFace/scripts/VFace_inference_batch.py:646-654) -----------------------
+ * The reference ends in a compressed, playable file (:646-654, mp4; :656-658, gif).  H.264 is not built; these two entry points
+ * make the entropy-coded scan of a baseline 4:2:0 JPEG of every frame on the device, vface_amd/scripts/mjpeg.py adds the headers and
+ * writes the frames as Motion-JPEG into an AVI, and the host receives the compressed bytes only.  csrc/mjpeg.hip.
+ *
+ * vface_jpeg_coefficients: rgb [frames][H][W][3] -> quantised DCT coefficients, frame f at out + f * frame_stride (int16
+ *   elements): [mcu_rows][mcu_cols][6][64], mcu_rows = (H + 15) / 16, mcu_cols = (W + 15) / 16, the six blocks of a 16 x 16 MCU in
+ *   the order Y00 Y01 Y10 Y11 Cb Cr, 64 coefficients each in zigzag order.  A frame is extended to whole MCUs by replicating its last
+ *   column and row.  One fused pass: RGB -> JFIF Y'CbCr, **full-range BT.601** (what every MJPEG decoder assumes; NOT the BT.709
+ *   limited range of vface_rgb_to_yuv420) -> 2 x 2 chroma mean -> level shift -> 8 x 8 forward DCT -> quantise -> zigzag.  qluma,
+ *   qchroma: device tables of 64 bytes, row-major, 1..255.  Integer arithmetic, stated once in tests/jpeg_model.py and equal to
+ *   it bit for bit; |DC| <= 1024, |AC| <= 1023.  Elements between frames are not written.
+ *   NULL pointer, W, H or frames <= 0: VFACE_ERR_ARG; W or H > 65535, frame_stride < mcu_rows * mcu_cols * 384: VFACE_ERR_SHAPE.
+ *
+ * vface_jpeg_entropy: coefficient frames as above (`mcus` = mcu_rows * mcu_cols per frame, frame f at coef + f * frame_stride) ->
+ *   the scan of every frame, baseline Huffman coding with the four typical tables of T.81 Annex K, restart intervals of `restart`
+ *   MCUs (the DRI value; a frame's last interval may be shorter): every interval starts with zero DC predictors and ends
+ *   1-padded to a whole byte, FF bytes inside it are followed by a stuffed 00, and RSTm, m = index mod 8, stands between the
+ *   intervals of a frame.  No EOI.  The scans are packed back to back into out (frame 0 first); lengths [frames] takes each
+ *   frame's byte count.  Bytes past out_bytes are dropped, never written: out_bytes >= frames * (intervals * restart * 6 * 416 +
+ *   2 * (intervals - 1)) always suffices (416 = twice the 64 * (16 + 10) bits of a block, for the stuffing), and a caller that
+ *   gives less compares the sum of lengths with it.  workspace: vface_jpeg_entropy_workspace_bytes(mcus, frames, restart) bytes,
+ *   16-byte aligned.  Three launches, no allocation, no host synchronisation.
+ *   NULL pointer, mcus, frames, restart or out_bytes <= 0: VFACE_ERR_ARG; restart > 65535, frame_stride < mcus * 384, a workspace
+ *   too small: VFACE_ERR_SHAPE; a workspace off 16 bytes: VFACE_ERR_ALIGN. */
+int vface_jpeg_coefficients(const uint8_t* rgb, int W, int H, int frames, const uint8_t* qluma, const uint8_t* qchroma, int16_t* out,
+                            int64_t frame_stride, void* stream);
+size_t vface_jpeg_entropy_workspace_bytes(int mcus, int frames, int restart);
+int vface_jpeg_entropy(const int16_t* coef, int64_t frame_stride, int mcus, int frames, int restart, uint8_t* out, int64_t out_bytes,
+                       int32_t* lengths, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- video in, colour half (REFace/scripts/VFace_inference_batch.py:240-285) --------------------------------------------------
  * The reference decodes the target video on the host (cv2.VideoCapture, BGR -> RGB, PNG per frame, :240-285).  The H.264 decoder

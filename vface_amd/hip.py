@@ -83,6 +83,9 @@ SIGNATURES = {
     "vface_perspective_paste": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_frame_normalise_resize": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_rgb_to_yuv420": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _i32, _vp]),
+    "vface_jpeg_coefficients": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "vface_jpeg_entropy_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "vface_jpeg_entropy": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
@@ -546,6 +549,84 @@ def rgb_to_yuv420(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -
     stride = out.stride(0) if F_ > 1 else max(out.stride(0), n)
     _check(load().vface_rgb_to_yuv420(_p(frames_u8), W, H, _p(out), stride, F_, _stream()), "vface_rgb_to_yuv420")
     return out
+
+
+JPEG_MCU_COEFS = 6 * 64            # int16 elements of one 16 x 16 MCU: Y00 Y01 Y10 Y11 Cb Cr
+JPEG_BLOCK_BYTES_BOUND = 416       # worst case of one coded block: 64 x (16 + 10) bits, doubled for the stuffing (csrc/mjpeg.hip)
+_jpeg_ws = {}
+
+
+def jpeg_mcu_grid(W: int, H: int) -> Tuple[int, int]:
+    """(mcu_rows, mcu_cols) of a W x H frame: 16 x 16 pixels per MCU, the last column and row replicated."""
+    return (int(H) + 15) // 16, (int(W) + 15) // 16
+
+
+def jpeg_scan_bytes_bound(mcus: int, restart: int) -> int:
+    """Bytes that always hold one frame's scan (``vface_jpeg_entropy`` in the header): every block at its worst, RST markers."""
+    nint = -(-int(mcus) // int(restart))
+    return nint * min(int(restart), int(mcus)) * 6 * JPEG_BLOCK_BYTES_BOUND + 2 * (nint - 1)
+
+
+def jpeg_coefficients(frames_u8: torch.Tensor, qluma: torch.Tensor, qchroma: torch.Tensor,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 frames [F, H, W, 3] -> the quantised DCT coefficients of a baseline 4:2:0 JPEG, int16 [F, mcu_rows, mcu_cols, 6, 64]:
+    the blocks Y00 Y01 Y10 Y11 Cb Cr of every 16 x 16 MCU, zigzag order; a frame is extended to whole MCUs by replicating its last
+    column and row.  The colour matrix is **full-range BT.601 (JFIF)**, what every MJPEG decoder assumes -- not the BT.709 ``tv``
+    range of ``rgb_to_yuv420``.  ``qluma``, ``qchroma``: device uint8 [64], row-major, 1..255 (``scripts/mjpeg.quant_tables``).
+    The integer arithmetic of ``tests/jpeg_model.py``, bit for bit (csrc/mjpeg.hip).  ``out``: an int16 view of that shape whose
+    frames are contiguous, frame stride at least one frame; the elements between frames are not written."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise VFaceHipError("jpeg_coefficients: frames must be contiguous uint8 [F, H, W, 3]")
+    F_, H, W, _ = frames_u8.shape
+    if min(F_, H, W) <= 0:
+        raise VFaceHipError("jpeg_coefficients: F, H and W must be positive")
+    for q in (qluma, qchroma):
+        if q.dtype != torch.uint8 or tuple(q.shape) != (64,) or not q.is_contiguous() or q.device != frames_u8.device:
+            raise VFaceHipError("jpeg_coefficients: a quantisation table is a contiguous uint8 [64] tensor on the frames' device")
+    mr, mc = jpeg_mcu_grid(W, H)
+    shape, n = (F_, mr, mc, 6, 64), mr * mc * JPEG_MCU_COEFS
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=frames_u8.device)
+    elif (out.dtype != torch.int16 or tuple(out.shape) != shape or not out[0].is_contiguous() or (F_ > 1 and out.stride(0) < n)
+          or out.device != frames_u8.device):
+        raise VFaceHipError(f"jpeg_coefficients: out must be an int16 {list(shape)} view on the frames' device, frames contiguous, "
+                            f"frame stride >= {n}")
+    stride = out.stride(0) if F_ > 1 else max(out.stride(0), n)
+    _check(load().vface_jpeg_coefficients(_p(frames_u8), W, H, F_, _p(qluma), _p(qchroma), _p(out), stride, _stream()),
+           "vface_jpeg_coefficients")
+    return out
+
+
+def jpeg_entropy(coef: torch.Tensor, restart: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Coefficient frames, device int16 [F, mcu_rows, mcu_cols, 6, 64] (or [F, mcus, 6, 64]; what ``jpeg_coefficients`` returns, a
+    frame stride is fine) -> ``(out, lengths)``: the entropy-coded scans of the frames packed back to back in the uint8 buffer
+    ``out`` and int32 ``lengths`` [F], so the host copies ``out[:lengths.sum()]`` and nothing else.  Baseline Huffman coding, the
+    Annex-K tables, restart intervals of ``restart`` MCUs with RSTm between them, no EOI (csrc/mjpeg.hip; equal to
+    ``tests/jpeg_model.scan_bytes`` byte for byte).  ``out``: a contiguous uint8 buffer; by default one of the worst-case size
+    (``jpeg_scan_bytes_bound``).  Bytes that a smaller ``out`` cannot hold are dropped, and the caller sees it from the lengths."""
+    if (not isinstance(coef, torch.Tensor) or coef.dtype != torch.int16 or coef.dim() not in (4, 5) or tuple(coef.shape[-2:]) != (6, 64)
+            or not coef[0].is_contiguous()):
+        raise VFaceHipError("jpeg_entropy: coefficients must be int16 [F, mcu_rows, mcu_cols, 6, 64] with contiguous frames")
+    F_, mcus, restart = coef.shape[0], coef[0].numel() // JPEG_MCU_COEFS, int(restart)
+    if min(F_, mcus) <= 0 or not 1 <= restart <= 65535:
+        raise VFaceHipError(f"jpeg_entropy: F and the MCUs per frame must be positive, restart in 1..65535; got {F_}, {mcus}, {restart}")
+    n = mcus * JPEG_MCU_COEFS
+    if F_ > 1 and coef.stride(0) < n:
+        raise VFaceHipError(f"jpeg_entropy: frame stride >= {n}")
+    if out is None:
+        out = torch.empty(F_ * jpeg_scan_bytes_bound(mcus, restart), dtype=torch.uint8, device=coef.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != coef.device or out.numel() == 0:
+        raise VFaceHipError("jpeg_entropy: out must be a contiguous uint8 buffer on the coefficients' device")
+    lib = load()
+    need = int(lib.vface_jpeg_entropy_workspace_bytes(mcus, F_, restart))
+    ws = _jpeg_ws.get(str(coef.device))
+    if ws is None or ws.numel() < need:
+        ws = _jpeg_ws[str(coef.device)] = torch.empty(need, dtype=torch.uint8, device=coef.device)
+    lengths = torch.empty(F_, dtype=torch.int32, device=coef.device)
+    stride = coef.stride(0) if F_ > 1 else max(coef.stride(0), n)
+    _check(lib.vface_jpeg_entropy(_p(coef), stride, mcus, F_, restart, _p(out), out.numel(), _p(lengths), _p(ws), ws.numel(),
+                                  _stream()), "vface_jpeg_entropy")
+    return out, lengths
 
 
 YUV_MATRICES = {"bt709": 0, "bt601": 1}

@@ -15,7 +15,8 @@ landmarks file from disk (``scripts/clip_io.py``; dlib and the H.264 decoder sta
 are inputs: the ``{index}.png`` frames the reference writes at ``:285``, or -- ``--target_video`` -- the YUV4MPEG2 file any decoder
 writes, whose I420 planes are uploaded and converted to RGB on the GPU, ``scripts/demux.py``, csrc/demux.hip), the pasted frames out
 as PNG (``:636``) and, with ``--video_out``, as a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps
-(``:646-654``; ``scripts/mux.py``).  H.264 and audio are not built.
+(``:646-654``; ``scripts/mux.py``) or, with ``--video_codec mjpeg``, as Motion-JPEG in an AVI: a baseline JPEG encoder on the GPU
+(``scripts/mjpeg.py``, csrc/mjpeg.hip), a compressed file every player opens.  H.264 and audio are not built.
 
     python -m vface_amd.scripts.VFace_inference_batch --target_frames clip/ --src_image src.png --landmarks clip.npz \\
         --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.y4m
@@ -24,6 +25,9 @@ as PNG (``:636``) and, with ``--video_out``, as a YUV4MPEG2 file in the referenc
     python -m vface_amd.scripts.VFace_inference_batch --target_video clip.y4m --src_image src.png --landmarks clip.npz \\
         --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.y4m
 
+    python -m vface_amd.scripts.VFace_inference_batch --target_video clip.y4m --src_image src.png --landmarks clip.npz \\
+        --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.avi --video_codec mjpeg
+
 This module is the command line and nothing else: the flags (``build_parser``), their normalisation and every dependency between
 them (``normalise_options``, ``check_options``), and ``run_synthetic`` / ``run_clip`` / ``main``, which put a run together from
 parts that meet at plain data:
@@ -31,7 +35,7 @@ parts that meet at plain data:
     scripts/inputs.py       what a batch is fed: ``SeededInputs`` (``--synthetic``) or ``ClipRunInputs`` (a clip), one interface
     scripts/run_setup.py    everything a run owns, built once: model and weights, sampler, intake, parser, RAFT, paste-back, source
     scripts/pipeline.py     the stages of a batch, their wall timing, the loop (``--pipeline_inversion``, ``--whole_clip``), the record
-    scripts/outputs.py      the sinks: ``.pt`` / PNG of a seeded run, PNG / YUV4MPEG2 of a clip
+    scripts/outputs.py      the sinks: ``.pt`` / PNG of a seeded run, PNG / YUV4MPEG2 / Motion-JPEG of a clip
     scripts/checkpoint.py   reading ``last.ckpt``
 """
 from __future__ import annotations
@@ -103,7 +107,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "no face found), source [68, 2], optionally crops [N, 68, 2] and source_crop [68, 2] (scripts/clip_io.py)")
     p.add_argument("--video_out", type=str, default=None,
                    help="real-clip run: write the pasted frames as a YUV4MPEG2 file (yuv420p, BT.709, tv range, 10 fps: :646-654; "
-                        "scripts/mux.py) -- the hand-off to an encoder; H.264 and audio are not built")
+                        "scripts/mux.py) -- the hand-off to an encoder; H.264 and audio are not built -- or, with --video_codec "
+                        "mjpeg, as Motion-JPEG in an AVI")
+    p.add_argument("--video_codec", choices=["y4m", "mjpeg"], default=None,
+                   help="with --video_out: y4m (default) = raw YUV4MPEG2; mjpeg = one baseline 4:2:0 JPEG per frame, encoded on the GPU "
+                        "(csrc/mjpeg.hip), in a RIFF AVI with an index (scripts/mjpeg.py): full-range BT.601 as every MJPEG decoder "
+                        "assumes, 10 fps, no audio")
+    p.add_argument("--video_quality", type=int, default=None,
+                   help="with --video_codec mjpeg: libjpeg's quality scale, 1..100 (default 90): the tables Pillow's quality= yields")
     p.add_argument("--synthetic_weights", action="store_true",
                    help="real-clip run on seeded weights for every model (the seeds of --synthetic) instead of --ckpt, "
                         "--faceParsing_ckpt and --raft_ckpt: for tests and smoke runs")
@@ -254,10 +265,24 @@ def check_video_in_options(opt):
             raise SystemExit(f"--{flag} says how --target_video is converted: it needs --target_video FILE.y4m")
 
 
+def check_video_out_options(opt):
+    """--video_codec says how --video_out is written and --video_quality how the mjpeg codec quantises: alone they would be
+    ignored, so they are refused."""
+    opt = normalise_options(opt)
+    if opt.video_codec is not None and not opt.video_out:
+        raise SystemExit("--video_codec says how --video_out is written: it needs --video_out FILE")
+    if opt.video_quality is not None:
+        if opt.video_codec != "mjpeg":
+            raise SystemExit("--video_quality is the quantiser of the JPEG encoder: it needs --video_codec mjpeg (y4m is lossless)")
+        if not 1 <= opt.video_quality <= 100:
+            raise SystemExit(f"--video_quality is libjpeg's scale, 1..100; got {opt.video_quality}")
+
+
 def check_options(opt):
     """Every dependency between flags, on normalised options, before anything is built.  Without ``--synthetic`` the run is a
     clip's: its files and checkpoints are asked for and every stage is switched on."""
     check_video_in_options(opt)
+    check_video_out_options(opt)
     if not opt.synthetic:
         check_clip_options(opt)
     if opt.intake and not opt.with_vae:
@@ -332,7 +357,7 @@ def run_clip(opt) -> dict:
     conditioning landmarks and ``uc = learnable_vector`` (:423).  A frame without landmarks takes the crop, label map and inverse
     transform of the frame before it and zero conditioning landmarks, and is pasted into its own frame (:297-303).  Pasted
     frames go to ``Base_dir/results/{index}.png`` (:636) unless ``--skip_save``, and to ``--video_out`` as YUV4MPEG2
-    (scripts/mux.py).  Where the landmarks file has no ``crops``, the conditioning landmarks are derived from the frame points;
+    (scripts/mux.py) or, with ``--video_codec mjpeg``, as Motion-JPEG in an AVI (scripts/mjpeg.py).  Where the landmarks file has no ``crops``, the conditioning landmarks are derived from the frame points;
     that stands in for the reference's second detection on the crop and is not equal to it (scripts/clip_io.py).
     Returns the record of ``run_synthetic``; every batch also carries ``frame_ids`` and, with ``opt.return_samples``,
     ``pasted_frames``, ``crops`` and ``conditioning``."""

@@ -12,7 +12,9 @@ on the pasted frames where they are, and the host receives 1.5 bytes per pixel i
 
       ffmpeg -i out.y4m -c:v libx264 -pix_fmt yuv420p -colorspace bt709 -color_range tv out.mp4
 
-- **Audio and H.264 are not built**: there is no encoder in this project.  The ``.y4m`` file is the lossless hand-off to one.
+- **Audio and H.264 are not built.**  The ``.y4m`` file is the lossless hand-off to an H.264 encoder; the compressed file this
+  project writes itself is Motion-JPEG in an AVI (``scripts/mjpeg.py``, ``--video_codec mjpeg``), a different product: full-range
+  BT.601, lossy, playable as it is.
 """
 from __future__ import annotations
 

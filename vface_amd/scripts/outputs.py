@@ -37,17 +37,24 @@ class SeededOutputs:
 class ClipOutputs:
     """A clip from disk: the pasted frames as ``Base_dir/results/{index}.png`` (:636) unless ``--skip_save`` and, with
     ``--video_out``, as YUV4MPEG2 in frame order (:646-654: yuv420p, BT.709, tv range, 10 fps; scripts/mux.py), the batch's
-    ``video_out`` stage.  The file is opened by the first batch, whose frames give its size."""
+    ``video_out`` stage -- or, with ``--video_codec mjpeg``, as Motion-JPEG in an AVI at ``--video_quality`` (default 90;
+    scripts/mjpeg.py), the same stage.  The file is opened by the first batch, whose frames give its size."""
 
     def __init__(self, opt):
         self.dir, self.save, self.video_out, self.writer = opt.Base_dir, not opt.skip_save, opt.video_out, None
+        self.codec, self.quality = opt.video_codec or "y4m", opt.video_quality
         os.makedirs(self.dir, exist_ok=True)
 
     def write(self, b):
         if self.video_out:
             if self.writer is None:
-                from .mux import Y4MWriter
-                self.writer = Y4MWriter(self.video_out, b.pasted.shape[2], b.pasted.shape[1])
+                W, H = b.pasted.shape[2], b.pasted.shape[1]
+                if self.codec == "mjpeg":
+                    from .mjpeg import DEFAULT_QUALITY, MJPEGWriter
+                    self.writer = MJPEGWriter(self.video_out, W, H, quality=DEFAULT_QUALITY if self.quality is None else self.quality)
+                else:
+                    from .mux import Y4MWriter
+                    self.writer = Y4MWriter(self.video_out, W, H)
             with b.timer("video_out"):
                 self.writer.write(b.pasted)
         if self.save:
