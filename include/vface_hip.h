@@ -364,6 +364,55 @@ int vface_jpeg_entropy(const int16_t* coef, int64_t frame_stride, int mcus, int 
 int vface_yuv420_to_rgb(const uint8_t* i420, int64_t frame_stride, int W, int H, int frames, uint8_t* rgb, int matrix,
                         int full_range, int chroma, void* stream);
 
+/* ---- video in, compressed: baseline JPEG per frame (REFace/scripts/VFace_inference_batch.py:240-285) --------------------------
+ * The reference hands the target video to cv2.VideoCapture (:240-285).  Of the codecs that decodes, baseline JPEG is built here:
+ * vface_amd/scripts/mjpeg_in.py walks an AVI with an MJPG stream and parses each frame's headers on the host (8-bit, three
+ * components, Y 2 x 2, Cb and Cr 1 x 1, one scan), the SCANS cross to the device -- about a tenth of the I420 bytes at quality 90 --
+ * and these three entry points turn them into the I420 rows vface_yuv420_to_rgb reads (matrix 1, full_range 1, chroma 1: JFIF).
+ * csrc/mjpeg_in.hip; the interval decoder is csrc/jpeg_interval.hpp, which a host program runs under sanitizers.
+ *
+ * Common to the three: `mcus` = mcu_rows * mcu_cols per frame, the same for every frame of a call; restart [frames] = the DRI
+ *   value of each frame, 0 = none; a frame has ceil(mcus / restart) intervals (1 without restart, or where restart >= mcus);
+ *   max_intervals >= the largest of those counts is the row length of `ranges`.  status [frames]: 0 = decoded, 1 = the scan does
+ *   not hold the RST markers its header promises, 2 = they do not run RST0, RST1, .. mod 8, 3 = the bytes of an interval ran
+ *   out before its blocks, 4 = bits that are no code of the table, 5 = DC category above 11, 6 = AC size above 10, 7 = a zero run
+ *   past coefficient 63, 8 = a DC value outside int16.
+ *
+ * vface_jpeg_scan_index: scans = the frames' entropy-coded segments in one buffer of scan_bytes bytes, frame f at offsets[f],
+ *   lengths[f] bytes (after SOS, up to EOI) -> ranges [frames][max_intervals][2] int32: (begin, end) of every restart interval in
+ *   bytes of `scans`, the RST marker between two intervals in neither; entries past a frame's count are 0.  Writes status[f] =
+ *   0, 1 or 2 for every frame; a refused frame's row of ranges is 0.  A frame whose bytes do not lie inside the buffer is refused (1).
+ *   NULL pointer, mcus, frames, max_intervals or scan_bytes <= 0: VFACE_ERR_ARG; scan_bytes >= 2^31, max_intervals > mcus: VFACE_ERR_SHAPE.
+ *
+ * vface_jpeg_decode_entropy: ranges and status as vface_jpeg_scan_index left them -> out: quantised coefficients, frame f at
+ *   out + f * frame_stride (int16 elements): [mcus][6][64], blocks Y00 Y01 Y10 Y11 Cb Cr, zigzag order -- the layout
+ *   vface_jpeg_coefficients writes, so that vface_jpeg_entropy followed by these two calls is the identity.  tables: 2304 bytes per
+ *   frame, 4-byte aligned: DC tables of Y, Cb, Cr, then their AC tables, each int32 maxcode[16], int32 valoff[16], uint8 vals[256]
+ *   (csrc/jpeg_interval.hpp; mjpeg_in.huffman_block builds them).  Canonical Huffman decoding, stuffed 00 bytes skipped, DC
+ *   prediction per component reset at every interval, ZRL, EOB, EXTEND of T.81 F.2.2.1.  Every frame's mcus * 384 elements are
+ *   cleared first: what a refused frame or a failed interval did not reach is 0.  Elements between frames are not written.  A
+ *   frame's status becomes the largest code of its intervals (3..8); frames with status 1 or 2 are not decoded.  No byte outside
+ *   [begin, end) of an interval is read and no element outside its MCUs is written, whatever the bytes are.
+ *   NULL pointer, mcus, frames, max_intervals or scan_bytes <= 0: VFACE_ERR_ARG; scan_bytes >= 2^31, max_intervals > mcus,
+ *   frame_stride < mcus * 384: VFACE_ERR_SHAPE; tables off 4 bytes: VFACE_ERR_ALIGN.
+ *
+ * vface_jpeg_planes: coefficient frames as above (frame f at coef + f * coef_stride) and quant [frames][3][64], the quantisation
+ *   table of Y, Cb, Cr of every frame, row-major -> out: one I420 frame per frame, frame f at out + f * row_stride: Y [H][W], Cb
+ *   [ch][cw], Cr [ch][cw], cw = (W + 1) / 2, ch = (H + 1) / 2, cropped out of the whole MCUs.  Dequantisation, an integer 8 x 8
+ *   inverse DCT in two passes, + 128, clamp to 0..255; stated once in tests/jpeg_decode_model.py and equal to it bit for bit.  Within
+ *   0.5 + 0.15 of a level of the fp64 definition for coefficients an encoder can produce; every sum fits int32 for every int16
+ *   coefficient.  Bytes between frames are not written.
+ *   NULL pointer, W, H or frames <= 0: VFACE_ERR_ARG; W or H > 65535, coef_stride < mcus * 384, row_stride < W * H + 2 * cw * ch:
+ *   VFACE_ERR_SHAPE. */
+int vface_jpeg_scan_index(const uint8_t* scans, int64_t scan_bytes, const int64_t* offsets, const int32_t* lengths,
+                          const int32_t* restart, int mcus, int frames, int max_intervals, int32_t* ranges, int32_t* status,
+                          void* stream);
+int vface_jpeg_decode_entropy(const uint8_t* scans, int64_t scan_bytes, const int32_t* ranges, const int32_t* restart,
+                              const uint8_t* tables, int mcus, int frames, int max_intervals, int16_t* out, int64_t frame_stride,
+                              int32_t* status, void* stream);
+int vface_jpeg_planes(const int16_t* coef, int64_t coef_stride, const uint8_t* quant, int W, int H, int frames, uint8_t* out,
+                      int64_t row_stride, void* stream);
+
 /* ---- frame intake: decoded frame -> aligned crop -> the sampler's tensors (the mirror image of the paste-back) ---------------
  * The reference runs these steps per frame on the host with Pillow and numpy.  The Lanczos shrink of a large face
  * (alignmengt.py:108-114) and the bicubic resize to 512 x 512 (video_swap_dataset.py:139) are vface_resample_u8 with the tap

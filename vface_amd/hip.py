@@ -87,6 +87,9 @@ SIGNATURES = {
     "vface_jpeg_entropy_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "vface_jpeg_entropy": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vface_jpeg_scan_index": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "vface_jpeg_decode_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "vface_jpeg_planes": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vface_source_tensors": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp,
@@ -661,6 +664,121 @@ def yuv420_to_rgb(i420: torch.Tensor, W: int, H: int, matrix: str = "bt709", ful
     stride = i420.stride(0) if F_ > 1 else max(i420.stride(0), n)
     _check(load().vface_yuv420_to_rgb(_p(i420), stride, W, H, F_, _p(out), YUV_MATRICES[matrix], int(bool(full_range)),
                                       YUV_CHROMA[chroma], _stream()), "vface_yuv420_to_rgb")
+    return out
+
+
+JPEG_TABLE_BYTES = 6 * (16 * 4 + 16 * 4 + 256)      # a frame's Huffman tables as the decoder reads them (csrc/jpeg_interval.hpp)
+JPEG_STATUS = {0: "decoded", 1: "the scan does not hold the RST markers its DRI promises", 2: "the RST markers are out of order",
+               3: "the bytes of a restart interval ran out before its blocks", 4: "bits that are no code of the frame's Huffman table",
+               5: "a DC difference category above 11", 6: "an AC coefficient size above 10", 7: "a zero run past coefficient 63",
+               8: "a DC value outside 16 bits"}
+
+
+def jpeg_interval_count(mcus: int, restart: int) -> int:
+    """Restart intervals of a frame of ``mcus`` MCUs whose DRI says ``restart`` (0 = none)."""
+    mcus, restart = int(mcus), int(restart)
+    return 1 if restart <= 0 or restart >= mcus else -(-mcus // restart)
+
+
+def _jpeg_in_frames(what, scans, restart, mcus, max_intervals):
+    if not isinstance(scans, torch.Tensor) or scans.dtype != torch.uint8 or scans.dim() != 1 or not scans.is_contiguous() or scans.numel() == 0:
+        raise VFaceHipError(f"{what}: scans must be a contiguous, non-empty uint8 buffer")
+    if (not isinstance(restart, torch.Tensor) or restart.dtype != torch.int32 or restart.dim() != 1 or not restart.is_contiguous()
+            or restart.device != scans.device or restart.numel() == 0):
+        raise VFaceHipError(f"{what}: restart must be a contiguous int32 [F] tensor on the scans' device, F > 0")
+    mcus, max_intervals = int(mcus), int(max_intervals)
+    if mcus <= 0 or not 1 <= max_intervals <= mcus:
+        raise VFaceHipError(f"{what}: mcus must be positive and max_intervals in 1..mcus; got {mcus}, {max_intervals}")
+    if scans.numel() >= 2 ** 31:
+        raise VFaceHipError(f"{what}: the scans of one call must stay under 2 GiB; got {scans.numel()} bytes")
+    return restart.numel(), mcus, max_intervals
+
+
+def jpeg_scan_index(scans: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, restart: torch.Tensor, mcus: int,
+                    max_intervals: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The restart intervals of every frame's scan.  ``scans``: device uint8, the entropy-coded segments of F frames in one
+    buffer; ``offsets`` int64 [F], ``lengths`` int32 [F]: where each lies; ``restart`` int32 [F]: each frame's DRI value, 0 = none;
+    ``mcus``: MCUs per frame; ``max_intervals`` >= every frame's ``jpeg_interval_count``.  -> ``(ranges, status)``: int32
+    [F, max_intervals, 2] (begin, end) in bytes of ``scans``, the RST markers in neither, zeros past a frame's count; int32 [F],
+    0 or 1 = wrong marker count, 2 = wrong marker order (``JPEG_STATUS``), and such a frame's ranges are zeros.  csrc/mjpeg_in.hip."""
+    F_, mcus, max_intervals = _jpeg_in_frames("jpeg_scan_index", scans, restart, mcus, max_intervals)
+    for name, t, dt in (("offsets", offsets, torch.int64), ("lengths", lengths, torch.int32)):
+        if (not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (F_,) or not t.is_contiguous()
+                or t.device != scans.device):
+            raise VFaceHipError(f"jpeg_scan_index: {name} must be a contiguous {dt} [{F_}] tensor on the scans' device")
+    if out is None:
+        out = torch.empty(F_, max_intervals, 2, dtype=torch.int32, device=scans.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (F_, max_intervals, 2) or not out.is_contiguous() or out.device != scans.device:
+        raise VFaceHipError(f"jpeg_scan_index: out must be a contiguous int32 {[F_, max_intervals, 2]} tensor on the scans' device")
+    status = torch.empty(F_, dtype=torch.int32, device=scans.device)
+    _check(load().vface_jpeg_scan_index(_p(scans), scans.numel(), _p(offsets), _p(lengths), _p(restart), mcus, F_, max_intervals,
+                                        _p(out), _p(status), _stream()), "vface_jpeg_scan_index")
+    return out, status
+
+
+def jpeg_decode_entropy(scans: torch.Tensor, ranges: torch.Tensor, status: torch.Tensor, restart: torch.Tensor,
+                        tables: torch.Tensor, mcus: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ranges`` and ``status`` of ``jpeg_scan_index`` -> ``(coefficients, status)``: int16 [F, mcus, 6, 64], the layout
+    ``jpeg_coefficients`` writes (blocks Y00 Y01 Y10 Y11 Cb Cr, zigzag order), so ``jpeg_entropy`` followed by this is the identity;
+    ``status`` is updated in place: the largest code of a frame's intervals (``JPEG_STATUS``).  ``tables``: device uint8
+    [F, JPEG_TABLE_BYTES], every frame's Huffman tables by component (``scripts/mjpeg_in.huffman_block``).  One lane decodes one
+    interval with the routine of csrc/jpeg_interval.hpp: no byte outside an interval is read and no element outside its MCUs is
+    written, whatever the bytes are.  Every frame is cleared first; a refused frame stays zero.  ``out``: an int16 view
+    [F, mcus, 6, 64] with contiguous frames, frame stride at least one frame; elements between frames are not written."""
+    if not isinstance(ranges, torch.Tensor) or ranges.dim() != 3:
+        raise VFaceHipError("jpeg_decode_entropy: ranges must be int32 [F, max_intervals, 2]")
+    F_, mcus, max_intervals = _jpeg_in_frames("jpeg_decode_entropy", scans, restart, mcus, ranges.shape[1])
+    if ranges.dtype != torch.int32 or tuple(ranges.shape) != (F_, max_intervals, 2) or not ranges.is_contiguous() or ranges.device != scans.device:
+        raise VFaceHipError(f"jpeg_decode_entropy: ranges must be a contiguous int32 {[F_, max_intervals, 2]} tensor on the scans' device")
+    if (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (F_,) or not status.is_contiguous()
+            or status.device != scans.device):
+        raise VFaceHipError(f"jpeg_decode_entropy: status must be a contiguous int32 [{F_}] tensor on the scans' device")
+    if (not isinstance(tables, torch.Tensor) or tables.dtype != torch.uint8 or tuple(tables.shape) != (F_, JPEG_TABLE_BYTES)
+            or not tables.is_contiguous() or tables.device != scans.device):
+        raise VFaceHipError(f"jpeg_decode_entropy: tables must be a contiguous uint8 {[F_, JPEG_TABLE_BYTES]} tensor on the scans' device")
+    shape, n = (F_, mcus, 6, 64), mcus * JPEG_MCU_COEFS
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=scans.device)
+    elif (out.dtype != torch.int16 or tuple(out.shape) != shape or not out[0].is_contiguous() or (F_ > 1 and out.stride(0) < n)
+          or out.device != scans.device):
+        raise VFaceHipError(f"jpeg_decode_entropy: out must be an int16 {list(shape)} view on the scans' device, frames contiguous, "
+                            f"frame stride >= {n}")
+    stride = out.stride(0) if F_ > 1 else max(out.stride(0), n)
+    _check(load().vface_jpeg_decode_entropy(_p(scans), scans.numel(), _p(ranges), _p(restart), _p(tables), mcus, F_, max_intervals,
+                                            _p(out), stride, _p(status), _stream()), "vface_jpeg_decode_entropy")
+    return out, status
+
+
+def jpeg_planes(coef: torch.Tensor, quant: torch.Tensor, W: int, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Coefficient frames, device int16 [F, mcus, 6, 64] (or [F, mcu_rows, mcu_cols, 6, 64]; a frame stride is fine) and ``quant``,
+    device uint8 [F, 3, 64]: every frame's quantisation tables of Y, Cb, Cr, row-major -> uint8 [F, frame_bytes] I420 rows of
+    the W x H frames (Y [H][W], Cb [ch][cw], Cr [ch][cw]), what ``yuv420_to_rgb`` reads.  Dequantisation, integer inverse DCT,
+    + 128, clamp, crop: the arithmetic of ``tests/jpeg_decode_model.py``, bit for bit (csrc/mjpeg_in.hip).  ``out``: a uint8 view
+    [F, n >= frame_bytes] with unit column stride; bytes past frame_bytes of a row are not written."""
+    if (not isinstance(coef, torch.Tensor) or coef.dtype != torch.int16 or coef.dim() not in (4, 5) or tuple(coef.shape[-2:]) != (6, 64)
+            or coef.shape[0] == 0 or not coef[0].is_contiguous()):
+        raise VFaceHipError("jpeg_planes: coefficients must be int16 [F, mcus, 6, 64] with contiguous frames, F > 0")
+    W, H = int(W), int(H)
+    F_, mcus = coef.shape[0], coef[0].numel() // JPEG_MCU_COEFS
+    mr, mc = jpeg_mcu_grid(W, H)
+    if min(W, H) <= 0 or mcus != mr * mc:
+        raise VFaceHipError(f"jpeg_planes: a {W} x {H} frame is {mr} x {mc} MCUs; the coefficients hold {mcus} per frame")
+    n = mcus * JPEG_MCU_COEFS
+    if F_ > 1 and coef.stride(0) < n:
+        raise VFaceHipError(f"jpeg_planes: frame stride >= {n}")
+    if (not isinstance(quant, torch.Tensor) or quant.dtype != torch.uint8 or tuple(quant.shape) != (F_, 3, 64) or not quant.is_contiguous()
+            or quant.device != coef.device):
+        raise VFaceHipError(f"jpeg_planes: quant must be a contiguous uint8 {[F_, 3, 64]} tensor on the coefficients' device")
+    nb = i420_frame_bytes(W, H)
+    if out is None:
+        out = torch.empty(F_, nb, dtype=torch.uint8, device=coef.device)
+    elif (out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != F_ or out.shape[1] < nb or out.stride(1) != 1
+          or (F_ > 1 and out.stride(0) < nb) or out.device != coef.device):
+        raise VFaceHipError(f"jpeg_planes: out must be uint8 [{F_}, >= {nb}] rows on the coefficients' device, unit column stride, "
+                            f"row stride >= {nb}")
+    cstride = coef.stride(0) if F_ > 1 else max(coef.stride(0), n)
+    ostride = out.stride(0) if F_ > 1 else max(out.stride(0), nb)
+    _check(load().vface_jpeg_planes(_p(coef), cstride, _p(quant), W, H, F_, _p(out), ostride, _stream()), "vface_jpeg_planes")
     return out
 
 

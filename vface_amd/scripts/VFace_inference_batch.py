@@ -28,6 +28,10 @@ as PNG (``:636``) and, with ``--video_out``, as a YUV4MPEG2 file in the referenc
     python -m vface_amd.scripts.VFace_inference_batch --target_video clip.y4m --src_image src.png --landmarks clip.npz \\
         --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.avi --video_codec mjpeg
 
+    ffmpeg -i in.mp4 -c:v mjpeg -pix_fmt yuvj420p clip.avi
+    python -m vface_amd.scripts.VFace_inference_batch --target_video clip.avi --src_image src.png --landmarks clip.npz \\
+        --ckpt last.ckpt --faceParsing_ckpt 79999_iter.pth --raft_ckpt raft_large.pth --video_out out.avi --video_codec mjpeg
+
 This module is the command line and nothing else: the flags (``build_parser``), their normalisation and every dependency between
 them (``normalise_options``, ``check_options``), and ``run_synthetic`` / ``run_clip`` / ``main``, which put a run together from
 parts that meet at plain data:
@@ -94,10 +98,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--target_video", type=str, default=None,
                    help="real-clip run: the target clip as a YUV4MPEG2 file instead of --target_frames (`ffmpeg -i in.mp4 -pix_fmt yuv420p "
                         "clip.y4m`; 8-bit progressive 4:2:0, scripts/demux.py): the I420 planes are uploaded, 1.5 bytes per pixel, and "
-                        "converted to RGB on the GPU (csrc/demux.hip); frame ids 0 .. --n_frames - 1")
+                        "converted to RGB on the GPU (csrc/demux.hip); or as Motion-JPEG in an AVI (`ffmpeg -i in.mp4 -c:v mjpeg -pix_fmt "
+                        "yuvj420p clip.avi`, or what --video_codec mjpeg wrote; baseline 4:2:0, scripts/mjpeg_in.py): the compressed scans "
+                        "are uploaded and decoded on the GPU (csrc/mjpeg_in.hip).  The file's first bytes say which, not its name; frame "
+                        "ids 0 .. --n_frames - 1")
     p.add_argument("--video_in_matrix", choices=["bt709", "bt601"], default=None,
-                   help="with --target_video: the matrix of the file, which Y4M cannot tag.  Default bt709: what --video_out writes and "
-                        "HD material carries; bt601 is what an untagged swscale conversion uses")
+                   help="with --target_video FILE.y4m: the matrix of the file, which Y4M cannot tag.  Default bt709: what --video_out writes "
+                        "and HD material carries; bt601 is what an untagged swscale conversion uses.  Refused with an AVI: JFIF fixes "
+                        "full-range BT.601")
     p.add_argument("--chroma_upsample", choices=["sited", "nearest"], default=None,
                    help="with --target_video: sited (default) = interpolate the chroma where the header says its samples sit "
                         "(C420jpeg: centre; C420mpeg2: left); nearest = repeat each sample over its 2 x 2 block")
@@ -331,8 +339,12 @@ def _run(opt) -> dict:
     else:
         from .clip_io import ClipInputs
         if opt.target_video:
-            from .demux import Y4MReader
-            clip = ClipInputs.from_video(Y4MReader(opt.target_video), opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
+            from .mjpeg_in import open_video
+            video = open_video(opt.target_video)            # by the file's first bytes: a YUV4MPEG2 file, or an AVI with an MJPG stream
+            if video.fixed_matrix and opt.video_in_matrix:
+                raise SystemExit(f"--video_in_matrix names the matrix of a file that cannot tag it; {opt.target_video} is Motion-JPEG, and "
+                                 f"JFIF fixes full-range BT.601: leave the flag out")
+            clip = ClipInputs.from_video(video, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         else:
             clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         inputs, sink_type = providers.ClipRunInputs(clip, opt, dev), outputs.ClipOutputs

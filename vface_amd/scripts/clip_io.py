@@ -165,9 +165,10 @@ class ClipInputs:
 
     @classmethod
     def from_video(cls, video, src_image: str, landmarks: str, n_frames: int, H: int, W: int, image_size: int = 1024):
-        """The same inputs over a ``scripts/demux.Y4MReader`` instead of a folder: frame ids 0 .. n_frames - 1, and ``batch`` hands
-        out the I420 rows of the file, uint8 [F, frame_bytes], where the folder form hands out RGB frames (the conversion is the
-        device's: ``inputs.ClipRunInputs``).  One frame size by construction."""
+        """The same inputs over a ``scripts/demux.Y4MReader`` or a ``scripts/mjpeg_in.MJPEGReader`` instead of a folder: frame ids
+        0 .. n_frames - 1, and ``batch`` hands out what the reader's ``read`` returns -- the I420 rows of the file, uint8
+        [F, frame_bytes], or an ``MJPEGFrames`` of compressed scans -- where the folder form hands out RGB frames (the conversion
+        is the device's: the reader's ``to_rgb``, called by ``inputs.ClipRunInputs``).  One frame size by construction."""
         if len(video) < n_frames:
             raise SystemExit(f"--target_video {video.path}: {len(video)} frame(s), --n_frames asks for {n_frames}")
         self = cls.__new__(cls)

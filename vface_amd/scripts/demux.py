@@ -91,7 +91,9 @@ def parse_y4m_header(line, path: str = "<y4m>") -> Y4MHeader:
 class Y4MReader:
     """``Y4MReader(path)``: the header (``.header``, ``.W``, ``.H``), ``len()`` = the frame count, ``read(indices)`` = host uint8
     ``[F, frame_bytes]`` in the order asked for.  The frames are indexed on open from their ``FRAME...\\n`` lines alone (parameters
-    after ``FRAME`` are allowed, so offsets are found, not computed); the planes are only ever read by ``read``."""
+    after ``FRAME`` are allowed, so offsets are found, not computed); the planes are only ever read by ``read``.
+    ``to_rgb`` is the surface it shares with ``mjpeg_in.MJPEGReader``: what ``read`` returned -> RGB frames on the device."""
+    fixed_matrix = None             # Y4M cannot tag the matrix: --video_in_matrix says it
 
     def __init__(self, path: str):
         self.path = path
@@ -144,6 +146,14 @@ class Y4MReader:
             if self._f.readinto(memoryview(out[row])) != self.frame_bytes:
                 raise SystemExit(f"{self.path}: frame {i} is truncated (the file changed while it was read)")
         return torch.from_numpy(out)
+
+    def to_rgb(self, i420: torch.Tensor, device, matrix: str = "bt709", chroma_upsample: str = "sited") -> torch.Tensor:
+        """I420 rows as ``read`` returns them -> device uint8 [F, H, W, 3]: the rows are uploaded as they are (1.5 bytes per pixel)
+        and ``hip.yuv420_to_rgb`` converts them there; range and chroma siting from the file's header."""
+        from .. import hip
+        head = self.header
+        return hip.yuv420_to_rgb(i420.to(device), head.W, head.H, matrix=matrix, full_range=head.full_range,
+                                 chroma="nearest" if chroma_upsample == "nearest" else head.siting)
 
     def close(self):
         if self._f is not None:

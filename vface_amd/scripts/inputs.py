@@ -212,9 +212,10 @@ class ClipRunInputs:
     """A ``clip_io.ClipInputs`` behind the same questions.  A frame without landmarks is cut with the quad, and from the pixels, of
     the frame it takes (``clip_io.fallback_indices``), inherits that frame's label map -- across a batch boundary too, which is
     the one thing this object carries from batch to batch -- and has zero conditioning landmarks.  Over a video file
-    (``ClipInputs.from_video``) the clip hands out I420 rows: they are uploaded as they are and become the same RGB frames on the
-    device (``hip.yuv420_to_rgb``; matrix and chroma siting from ``--video_in_matrix``, ``--chroma_upsample`` and the file's header),
-    timed as stage ``video_in``."""
+    (``ClipInputs.from_video``) the clip hands out what the file's reader read -- I420 rows of a Y4M file, the compressed scans of
+    an AVI's JPEG frames -- and the reader's ``to_rgb`` makes the RGB frames on the device (``hip.yuv420_to_rgb``; matrix and chroma
+    siting from ``--video_in_matrix``, ``--chroma_upsample`` and the file's header; for an AVI the decoder of ``scripts/mjpeg_in.py``
+    in front of it), timed as stage ``video_in``."""
     frame_size_order = "width_height"   # (a clip is rarely square: paste_back.PasteBack)
     record_keys = ("frame_ids", "pasted_frames", "crops", "conditioning")
 
@@ -240,7 +241,7 @@ class ClipRunInputs:
         given = self.clip.batch(k, self.F, whole_clip=self.whole)
         if self.clip.video is None:
             return given["frames"].to(self.device), given["crop_frames"].to(self.device), given["quads"], None
-        # a video file: the I420 rows cross to the device (1.5 bytes per pixel) and become RGB frames there
+        # a video file: what its reader hands out crosses to the device (I420 rows, or JPEG scans) and becomes RGB frames there
         torch.cuda.synchronize(self.device)
         t0 = time.time()
         frames = self._rgb(given["frames"])
@@ -249,11 +250,9 @@ class ClipRunInputs:
         self._seconds[k] = {"video_in": time.time() - t0}
         return frames, crop_frames, given["quads"], None
 
-    def _rgb(self, i420):
-        from .. import hip
-        head = self.clip.video.header
-        return hip.yuv420_to_rgb(i420.to(self.device), head.W, head.H, matrix=self.matrix, full_range=head.full_range,
-                                 chroma="nearest" if self.chroma_upsample == "nearest" else head.siting)
+    def _rgb(self, read):
+        """What the clip's reader handed out (I420 rows of a Y4M file, the scans of an AVI's JPEG frames) -> device RGB frames."""
+        return self.clip.video.to_rgb(read, self.device, self.matrix, self.chroma_upsample)
 
     def own_seconds(self, k):
         return self._seconds.pop(k, {})
