@@ -8,7 +8,7 @@ under ``/root/reference`` and NOT installed in this image, and its pretrained we
     **PARITY UNPINNED.**  This file restates the published RAFT-large architecture of torchvision 0.14
     (``torchvision/models/optical_flow/raft.py``: FeatureEncoder / ResidualBlock / CorrBlock / MotionEncoder / ConvGRU /
     RecurrentBlock / FlowHead / MaskPredictor / ``upsample_flow``, and ``_utils.py``: ``grid_sample``, ``make_coords_grid``)
-    from its paper (Teed & Deng, ECCV 2020) and the library's documented structure, in plain fp32 torch.  Neither the module
+    from its paper (Teed & Deng, ECCV 2020) and the library's documented structure, in plain torch (fp32, or fp64 when given doubles).  Neither the module
     code nor a golden vector of it could be checked here; the state-dict key names are the ones that architecture defines and
     are equally unverified.  The HIP path is tested against THIS restatement on synthetic weights.
 
@@ -17,7 +17,7 @@ Nothing here is imported by the product path.
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -92,24 +92,40 @@ def _norm(sd, name, x, kind):
                         training=False, eps=1e-5)
 
 
-def encoder(sd, enc: str, x: torch.Tensor) -> torch.Tensor:
+def _tap(taps, name, v):
+    """Record a named intermediate (tests); changes no arithmetic."""
+    if taps is not None:
+        taps[name] = v
+    return v
+
+
+def _cna(sd, name, x, kind, taps, stride=1, relu=True):
+    """Conv2dNormActivation ``name`` = (``.0`` conv, ``.1`` norm, ReLU): taps ``name.0``, ``name.1`` and, with ``relu``, ``name.2``."""
+    y = _tap(taps, f"{name}.0", _conv(sd, f"{name}.0", x, stride=stride))
+    y = _tap(taps, f"{name}.1", _norm(sd, f"{name}.1", y, kind))
+    return _tap(taps, f"{name}.2", F.relu(y)) if relu else y
+
+
+def encoder(sd, enc: str, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    """``taps`` (optional dict): every convolution (``<layer>.0``), norm (``.1``) and activation (``.2``), each block's output
+    (``<block>.out``) and the head (``<enc>.conv``)."""
     kind = "instance" if enc == "feature_encoder" else "batch"
-    x = F.relu(_norm(sd, f"{enc}.convnormrelu.1", _conv(sd, f"{enc}.convnormrelu.0", x, stride=ENC_STRIDES[0]), kind))
+    x = _cna(sd, f"{enc}.convnormrelu", x, kind, taps, stride=ENC_STRIDES[0])
     for li, stride in enumerate(ENC_STRIDES[1:], start=1):
         for bi in range(2):
             b = f"{enc}.layer{li}.{bi}"
             st = stride if bi == 0 else 1
-            y = F.relu(_norm(sd, f"{b}.convnormrelu1.1", _conv(sd, f"{b}.convnormrelu1.0", x, stride=st), kind))
-            y = F.relu(_norm(sd, f"{b}.convnormrelu2.1", _conv(sd, f"{b}.convnormrelu2.0", y), kind))
+            y = _cna(sd, f"{b}.convnormrelu1", x, kind, taps, stride=st)
+            y = _cna(sd, f"{b}.convnormrelu2", y, kind, taps)
             if st != 1:
-                x = _norm(sd, f"{b}.downsample.1", _conv(sd, f"{b}.downsample.0", x, stride=st), kind)
-            x = F.relu(x + y)
-    return _conv(sd, f"{enc}.conv", x)
+                x = _cna(sd, f"{b}.downsample", x, kind, taps, stride=st, relu=False)
+            x = _tap(taps, f"{b}.out", F.relu(x + y))
+    return _tap(taps, f"{enc}.conv", _conv(sd, f"{enc}.conv", x))
 
 
-def coords_grid(B: int, h: int, w: int, device=None) -> torch.Tensor:
+def coords_grid(B: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     ys, xs = torch.meshgrid(torch.arange(h, device=device), torch.arange(w, device=device), indexing="ij")
-    return torch.stack([xs, ys], 0).float()[None].repeat(B, 1, 1, 1)      # channel 0 = x, channel 1 = y
+    return torch.stack([xs, ys], 0).to(dtype)[None].repeat(B, 1, 1, 1)      # channel 0 = x, channel 1 = y
 
 
 def corr_pyramid(fmap1: torch.Tensor, fmap2: torch.Tensor) -> List[torch.Tensor]:
@@ -137,7 +153,7 @@ def corr_lookup(pyr: List[torch.Tensor], coords: torch.Tensor) -> torch.Tensor:
     ``stack(meshgrid(d, d, indexing='ij'), -1)`` ADDED to (x, y): entry (i, j) samples at (x + d_i, y + d_j)."""
     r = CORR_RADIUS
     side = 2 * r + 1
-    d = torch.linspace(-r, r, side, device=coords.device)
+    d = torch.linspace(-r, r, side, device=coords.device, dtype=coords.dtype)
     delta = torch.stack(torch.meshgrid(d, d, indexing="ij"), -1).view(1, side, side, 2)
     B, _, h, w = coords.shape
     cen = coords.permute(0, 2, 3, 1).reshape(B * h * w, 1, 1, 2)
@@ -148,27 +164,38 @@ def corr_lookup(pyr: List[torch.Tensor], coords: torch.Tensor) -> torch.Tensor:
     return torch.cat(out, -1).permute(0, 3, 1, 2).contiguous()
 
 
-def update_block(sd, hidden, context, corr_features, flow):
+def update_block(sd, hidden, context, corr_features, flow, taps: Optional[dict] = None):
+    """``taps`` (optional dict): each convolution (``<name>.0``; ``convz`` / ``convr`` / ``convq`` / ``conv1`` / ``conv2`` under
+    their own names) and its activation (``.act``), ``motion`` (the 126 features), per ConvGRU ``<g>.z``, ``.r``, ``.rh`` (r *
+    hidden), ``.q`` and ``.hidden``, and ``delta``."""
     m = "update_block.motion_encoder"
-    corr = F.relu(_conv(sd, f"{m}.convcorr1.0", corr_features))
-    corr = F.relu(_conv(sd, f"{m}.convcorr2.0", corr))
-    fl = F.relu(_conv(sd, f"{m}.convflow1.0", flow))
-    fl = F.relu(_conv(sd, f"{m}.convflow2.0", fl))
-    mo = F.relu(_conv(sd, f"{m}.conv.0", torch.cat([corr, fl], 1)))
+
+    def cr(name, x):
+        return _tap(taps, f"{name}.act", F.relu(_tap(taps, f"{name}.0", _conv(sd, f"{name}.0", x))))
+
+    corr = cr(f"{m}.convcorr1", corr_features)
+    corr = cr(f"{m}.convcorr2", corr)
+    fl = cr(f"{m}.convflow1", flow)
+    fl = cr(f"{m}.convflow2", fl)
+    mo = _tap(taps, "motion", cr(f"{m}.conv", torch.cat([corr, fl], 1)))
     x = torch.cat([context, mo, flow], 1)
     for g in ("convgru1", "convgru2"):
         p = f"update_block.recurrent_block.{g}"
         hx = torch.cat([hidden, x], 1)
-        z = torch.sigmoid(_conv(sd, f"{p}.convz", hx))
-        r = torch.sigmoid(_conv(sd, f"{p}.convr", hx))
-        q = torch.tanh(_conv(sd, f"{p}.convq", torch.cat([r * hidden, x], 1)))
-        hidden = (1 - z) * hidden + z * q
-    delta = _conv(sd, "update_block.flow_head.conv2", F.relu(_conv(sd, "update_block.flow_head.conv1", hidden)))
+        z = _tap(taps, f"{g}.z", torch.sigmoid(_tap(taps, f"{p}.convz", _conv(sd, f"{p}.convz", hx))))
+        r = _tap(taps, f"{g}.r", torch.sigmoid(_tap(taps, f"{p}.convr", _conv(sd, f"{p}.convr", hx))))
+        rh = _tap(taps, f"{g}.rh", r * hidden)
+        q = _tap(taps, f"{g}.q", torch.tanh(_tap(taps, f"{p}.convq", _conv(sd, f"{p}.convq", torch.cat([rh, x], 1)))))
+        hidden = _tap(taps, f"{g}.hidden", (1 - z) * hidden + z * q)
+    fh = _tap(taps, "update_block.flow_head.conv1", _conv(sd, "update_block.flow_head.conv1", hidden))
+    delta = _tap(taps, "delta", _conv(sd, "update_block.flow_head.conv2", _tap(taps, "update_block.flow_head.conv1.act", F.relu(fh))))
     return hidden, delta
 
 
-def upsample_flow(sd, hidden, flow, factor: int = 8):
-    mask = 0.25 * _conv(sd, "mask_predictor.conv", F.relu(_conv(sd, "mask_predictor.convrelu.0", hidden)))
+def upsample_flow(sd, hidden, flow, factor: int = 8, taps: Optional[dict] = None):
+    """``taps`` (optional dict): ``mask_predictor.convrelu.0``, its ``.act``, and ``mask`` (0.25 x the 576 logits)."""
+    mr = _tap(taps, "mask_predictor.convrelu.0", _conv(sd, "mask_predictor.convrelu.0", hidden))
+    mask = _tap(taps, "mask", 0.25 * _conv(sd, "mask_predictor.conv", _tap(taps, "mask_predictor.convrelu.0.act", F.relu(mr))))
     B, _, h, w = flow.shape
     mask = torch.softmax(mask.view(B, 1, 9, factor, factor, h, w), dim=2)
     up = F.unfold(factor * flow, kernel_size=3, padding=1).view(B, 2, 9, 1, 1, h, w)
@@ -179,14 +206,14 @@ def upsample_flow(sd, hidden, flow, factor: int = 8):
 @torch.no_grad()
 def raft_forward(sd, image1: torch.Tensor, image2: torch.Tensor, num_flow_updates: int = 20, all_low_res: bool = False):
     """Last flow prediction [B, 2, H, W] (what ``compute_flow`` returns); ``all_low_res`` also returns the 1/8-resolution flow
-    after every update (for tests)."""
+    after every update (for tests).  Runs in the dtype of its inputs (fp32, or fp64 with a double ``sd`` and double images)."""
     B = image1.shape[0]
     fmaps = encoder(sd, "feature_encoder", torch.cat([image1, image2], 0))
     pyr = corr_pyramid(fmaps[:B], fmaps[B:])
     ctx = encoder(sd, "context_encoder", image1)
     hidden, context = torch.tanh(ctx[:, :HIDDEN]), F.relu(ctx[:, HIDDEN:])
     h, w = fmaps.shape[-2:]
-    coords0 = coords_grid(B, h, w, image1.device)
+    coords0 = coords_grid(B, h, w, image1.device, image1.dtype)
     coords1 = coords0.clone()
     lows = []
     for _ in range(num_flow_updates):

@@ -780,3 +780,179 @@ def timestep_embedding_ref_and_bound(t, dim, dt):
     if dim % 2:
         ref, e = torch.cat([ref, torch.zeros_like(ref[:, :1])], -1), torch.cat([e, torch.zeros_like(e[:, :1])], -1)
     return ref, as_16bit(ref, e, dt)
+
+
+# ------------------------------------------------------------------------------------------------ the flow producer's glue kernels (csrc/raft.hip)
+# Used by test_glue_kernels_gpu.py (synthetic operands, one kernel at a time) and by raft_stages.check_stage (the engine's own
+# operands, stage by stage).  Transcendental steps take their allowance from ``cpu_fp32_rel_error`` on the case's own arguments.
+def chan_stats_slices(hw):
+    """The pixel slices of the statistics launch (vf_chan_stats_slices): what fixes the length of one lane's sum."""
+    return 16 if hw >= 16384 else (4 if hw >= 2048 else 1)
+
+
+def channel_stats_ref_and_bound(x64, eps):
+    """nn.InstanceNorm2d's (mean, 1 / sqrt(var + eps)) per image and channel of ``x64 [nimg, hw, C]`` (fp64 of the stored 16-bit
+    values), biased variance.  Returns ``(ref [nimg, C, 2], bound [nimg, C, 2])``.
+    Bound, u = 2^-24, in moments about the pivot p = the channel's first pixel of the image (any value of the data serves; it
+    is within the spread of the channel, so nothing below grows with mean^2).  d = x - p, A1 = mean|d|, A2 = mean d^2,
+    delta = mean - p.  A lane sums n = ceil(ceil(hw / S) / 32) values in order, 32 lanes are folded in order, the slices in fp64:
+    each fp32 sum is off by at most L u (sum of |terms|), L = n + 32 + 2 (the subtraction d and the square round once each).
+      mean = p + sum d / hw            off by  L u A1 + u |mean|        (the second term: the fp32 store)
+      var  = sum d^2 / hw - delta^2    off by  dV = L u A2 + 2 |delta| L u A1
+      rstd = 1 / sqrt(var + eps)       off by  rstd (dV / (2 (var + eps)) + 2 u)
+    A constant channel has d = 0 exactly: mean exact, var = 0, rstd = fp32(1 / sqrt(eps))."""
+    hw = x64.shape[1]
+    mean, var = x64.mean(1), x64.var(1, unbiased=False)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    d = x64 - x64[:, :1]
+    A1, A2, delta = d.abs().mean(1), (d * d).mean(1), d.mean(1)
+    L = -(-(-(-hw // chan_stats_slices(hw))) // 32) + 34
+    d_mean = L * U32 * A1 + U32 * mean.abs()
+    d_var = L * U32 * A2 + 2 * delta.abs() * L * U32 * A1
+    d_rstd = rstd * (d_var / (2 * (var + eps)) + 2 * U32)
+    return torch.stack([mean, rstd], -1), torch.stack([d_mean, d_rstd], -1)
+
+
+def channel_norm_ref_and_bound(x64, stats64, dstats, dt):
+    """o = (x - mean) rstd of ``x64 [nimg, hw, C]`` from the fp64 statistics of ``channel_stats_ref_and_bound`` and their bounds,
+    rounded to ``dt``: 0.5 ulp(o) + rstd dMean + |x - mean| dRstd + 3 u |o|."""
+    mean, rstd, d_mean, d_rstd = stats64[..., 0], stats64[..., 1], dstats[..., 0], dstats[..., 1]
+    ref = (x64 - mean[:, None]) * rstd[:, None]
+    return ref, 0.5 * ulp(ref, dt) + rstd[:, None] * d_mean[:, None] + (x64 - mean[:, None]).abs() * d_rstd[:, None] + 3 * U32 * ref.abs()
+
+
+ACT_FN = {"none": lambda v: v, "relu": torch.relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
+ACT_LIP = {"none": 1.0, "relu": 1.0, "tanh": 1.0, "sigmoid": 0.25}            # Lipschitz constants
+
+
+def norm_act_pre_ref_and_bound(x64, st64, r64, hw):
+    """v = (x - mean) rstd + res in fp64 FROM GIVEN fp32 STATISTICS ``st64 [nimg, C, 2]`` (read back from the device or handed to
+    the kernel; None: no normalisation) and the bound dv of its fp32 evaluation: the subtraction and the product round once each
+    (2 u |(x - mean) rstd|), the sum with the residual once (u |v|)."""
+    v, dv = x64, torch.zeros_like(x64)
+    if st64 is not None:
+        m = st64[:, :, 0].repeat_interleave(hw, 0)
+        s = st64[:, :, 1].repeat_interleave(hw, 0)
+        v = (x64 - m) * s
+        dv = 2 * U32 * v.abs()
+    if r64 is not None:
+        v = v + r64
+        dv = dv + U32 * v.abs()
+    return v, dv
+
+
+def act_ref_and_bound(v, dv, act, out_dt):
+    """Reference act(v) and its bound: the activation's Lipschitz constant times dv, the transcendental allowance relative to the
+    result plus 2^-126, one fp32 rounding of the result, and 0.5 ulp of a 16-bit output."""
+    ref = ACT_FN[act](v)
+    b = ACT_LIP[act] * dv + U32 * ref.abs()
+    if act in ("tanh", "sigmoid"):
+        b = b + cpu_fp32_rel_error(ACT_FN[act], v.float()) * ref.abs() + TINY32
+    if out_dt != torch.float32:
+        b = b + 0.5 * ulp(ref, out_dt)
+    return ref, b
+
+
+def gru_gate_ref_and_bound(zr, h32, dt, h_err=None):
+    """``vface_gru_gate``: z = sigmoid(zr[:, :Hd]) and r h = sigmoid(zr[:, Hd:]) h32 in fp64 on the 16-bit ``zr [M, 2 Hd]`` and
+    the fp32 ``h32`` (or an fp64 reference state off by at most ``h_err``).  Returns ``(z, z_bound, rh, rh_bound)``.  z: the sigmoid
+    allowance E z + 2^-126 + 0.5 ulp; r h: (E + u) |r h| [+ r h_err] + 2^-126 (1 + |h|) + 0.5 ulp (one product; a flushed sigmoid
+    is multiplied by h)."""
+    Hd = zr.shape[1] // 2
+    E = cpu_fp32_rel_error(torch.sigmoid, zr.float())
+    h64 = h32.double()
+    zref = torch.sigmoid(zr[:, :Hd].double())
+    r = torch.sigmoid(zr[:, Hd:].double())
+    rref = r * h64
+    rb = (E + U32) * rref.abs()
+    if h_err is not None:
+        rb = rb + r * h_err
+    return zref, E * zref + TINY32 + 0.5 * ulp(zref, dt), rref, rb + TINY32 * (1 + h64.abs()) + 0.5 * ulp(rref, dt)
+
+
+def gru_update_ref_and_bound(q, z, h64, dt):
+    """h' = (1 - z) h + z tanh(q) in fp64 on the 16-bit q, z and the bound of its fp32 evaluation: 1 - z, its product with h and
+    the final sum round the first term three times, the tanh allowance E, the product with z and the sum the second."""
+    E = cpu_fp32_rel_error(torch.tanh, q.float())
+    a, b = (1 - z.double()) * h64, z.double() * torch.tanh(q.double())
+    return a + b, 3 * U32 * a.abs() + (E + 2 * U32) * b.abs() + TINY32
+
+
+def corr_lookup_ref_and_bound(vols, flow32, B, hh, ww, scale, dt):
+    """``vface_corr_lookup``: the 9 x 9 bilinear window per level around (x + fx) / 2^l, (y + fy) / 2^l, zero outside the map,
+    feature index l 81 + i 9 + j with i the x offset and j the y offset; ``vols``: fp32 [M, h_l, w_l] per level, ``flow32 [M, 2]``
+    fp32.  Returns ``(ref [M, levels 81], bound)``.
+
+    The sample point is the kernel's own fp32 value restated in torch fp32, ``((px + f) * 2^-l) + (i - 4)``: two IEEE roundings
+    (the sum px + f and the sum with the offset).  The scaling by a power of two is exact, so a fused multiply-add of the last two
+    steps gives the same bits; the one exception, a product in the subnormal range (px = 0 and |f| < 2^-123), moves the point by
+    less than 2^-149 cells when the offset is 0 and not at all otherwise (an integer plus less than half its last place), which is
+    far below every term of the bound.  Everything after it -- floor, the two weights a = s - floor(s) (exact in fp32: Sterbenz /
+    same binade or below), the taps -- is fp64 of those fp32 numbers.  For flows that are multiples of 1/64 (test_corr_lookup)
+    every step above is exact and this is the plain fp64 point.
+    Bound: each of the four terms passes two products and two sums, and the scale one more: 5 u S with S = scale sum_k w_k |v_k|,
+    plus 0.5 ulp of the type."""
+    M = B * hh * ww
+    m = torch.arange(M)
+    px, py = (m % ww).float(), ((m // ww) % hh).float()
+    f32 = flow32.float()
+    off = torch.arange(9, dtype=torch.float32) - 4
+    refs, sizes = [], []
+    for l, vol in enumerate(vols):
+        hl, wl = vol.shape[-2:]
+        inv = torch.tensor(1.0 / (1 << l), dtype=torch.float32)
+        sx = (((px + f32[:, 0]) * inv)[:, None, None] + off[None, :, None]).double()           # [M, 9 (i), 1]
+        sy = (((py + f32[:, 1]) * inv)[:, None, None] + off[None, None, :]).double()           # [M, 1, 9 (j)]
+        x0, y0 = torch.floor(sx), torch.floor(sy)
+        ax, ay = sx - x0, sy - y0
+        flat = vol.reshape(M, hl * wl)
+        val, size = torch.zeros(M, 9, 9, dtype=torch.float64), torch.zeros(M, 9, 9, dtype=torch.float64)
+        for dy, wy in ((0, 1 - ay), (1, ay)):
+            for dx, wx in ((0, 1 - ax), (1, ax)):
+                xx, yy = (x0 + dx).expand(M, 9, 9), (y0 + dy).expand(M, 9, 9)
+                inside = (xx >= 0) & (xx < wl) & (yy >= 0) & (yy < hl)
+                idx = (yy.clamp(0, hl - 1) * wl + xx.clamp(0, wl - 1)).long().reshape(M, 81)
+                v = torch.gather(flat, 1, idx).double().reshape(M, 9, 9) * inside
+                val += wy * wx * v
+                size += wy * wx * v.abs()
+        refs.append(val.reshape(M, 81) * scale)
+        sizes.append(size.reshape(M, 81) * scale)
+    ref, size = torch.cat(refs, 1), torch.cat(sizes, 1)
+    return ref, 5 * U32 * size + 0.5 * ulp(ref, dt)
+
+
+def convex_upsample_ref_and_bound(mask, flow, B, hh, ww, mult=0.25):
+    """``vface_convex_upsample``: out[b, :, 8 y + fy, 8 x + fx] = sum_k softmax_k(mult mask[m, k, fy, fx]) 8 flow[neighbour k of m]
+    in fp64 (F.unfold's zero padding: a neighbour outside the map adds 0 to the sum and its weight stays in the softmax).
+    ``mask [M, >= 576]`` fp32 (index k 64 + fy 8 + fx), ``flow [M, 2]`` fp32.  Returns ``(ref, bound) [B, 2, 8 hh, 8 ww]``.
+    Bound.  Weight k carries a relative error eps_k = E + 3 u |d_k|, d_k = its logit minus the row's largest (E: the softmax
+    allowance, measured on these logits; the subtraction and the scaling by log2 e inside __expf round in proportion to |d_k|).
+    Numerator and denominator are 9 sums each, every term one product, then one division:
+    sum_k w_k (eps_k + 10 u) |8 f_k| + |out| (sum_k w_k eps_k + 10 u), and 2^-126 (sum_k |8 f_k| + 1): an exponential below the
+    normal range may be flushed, and it is multiplied by 8 f_k."""
+    M = B * hh * ww
+    lg = mult * mask[:, :576].reshape(M, 9, 64)
+    w = torch.softmax(lg.double(), 1)
+    E = cpu_fp32_rel_error(torch.softmax, lg, dim=1)
+    eps = E + 3 * U32 * (lg.double().amax(1, keepdim=True) - lg.double())
+    f8 = 8 * flow.double().reshape(B, hh, ww, 2).permute(0, 3, 1, 2)
+    nb = F.unfold(f8, 3, padding=1).reshape(B, 2, 9, hh * ww).permute(0, 3, 1, 2).reshape(M, 2, 9, 1)       # [M, 2, 9 (k), 1]
+    ref = (w[:, None] * nb).sum(2)                                                                         # [M, 2, 64]
+    bound = ((w * (eps + 10 * U32))[:, None] * nb.abs()).sum(2) + ref.abs() * ((w * eps).sum(1)[:, None] + 10 * U32) \
+        + TINY32 * (nb.abs().sum(2) + 1)
+    pix = lambda t: t.reshape(B, hh, ww, 2, 8, 8).permute(0, 3, 1, 4, 2, 5).reshape(B, 2, 8 * hh, 8 * ww)
+    return pix(ref), pix(bound)
+
+
+def avgpool2_ref(x):
+    """``vface_avgpool2_f32`` of fp32 ``x [R, h, w]``: ((a + b) + c + d) * 0.25 in fp32 in the kernel's order -- three correctly
+    rounded adds and an exact scale, so equality is derived.  Odd sizes drop the last row / column."""
+    oh_, ow_ = x.shape[1] // 2, x.shape[2] // 2
+    c = x[:, :2 * oh_, :2 * ow_]
+    return (((c[:, 0::2, 0::2] + c[:, 0::2, 1::2]) + c[:, 1::2, 0::2]) + c[:, 1::2, 1::2]) * 0.25
+
+
+def flow_update_ref(flow, delta=None):
+    """``vface_flow_update``: flow32 + delta32[:, :2], one IEEE fp32 sum (``delta`` None: the flow itself); the 16-bit copies are
+    its rounding."""
+    return flow + delta[:, :2] if delta is not None else flow
