@@ -42,10 +42,14 @@ extern "C" {
 #define VFACE_F16 0
 #define VFACE_BF16 1
 
-/* epilogue flags of vface_gemm / vface_conv3x3 */
+/* The flags word of vface_gemm / vface_conv3x3*: every bit the library reads is defined here (csrc/dispatch.hpp and vface_amd/hip.py name the same values) */
 #define VFACE_EPI_GEGLU 1   /* out[m][c] = (acc_val + b) * gelu(acc_gate + b); Wt rows packed by vface layout */
 #define VFACE_EPI_OUT_F32 2 /* store fp32 instead of the 16-bit type */
-#define VFACE_TUNE_VARIANT(v) ((v) << 8) /* bits 8..11: force GEMM schedule variant v (1..8); 0 = automatic */
+#define VFACE_TUNE_VARIANT(v) ((v) << 8) /* bits 8..11: force GEMM schedule variant v of csrc/gemm.hip: 5 | 6 = 128 | 160 channels per tile, two LDS stages; 7 | 8 = the same, one stage; 11..15 = 8 without column statistics (15: no K split either).  0 = automatic; 1..4, 9, 10 are refused (VFACE_ERR_SHAPE) */
+#define VFACE_TUNE_NO_XCD_REMAP 0x1000     /* A/B: csrc/gemm.hip's plain GEMM walks its tiles in launch order, not in the XCD-aware order */
+#define VFACE_TUNE_NO_SETPRIO 0x2000       /* A/B: csrc/gemm.hip: no raised wave priority around the MFMAs; csrc/conv.hip: the late waves issue their half of a K tile's loads apart */
+#define VFACE_TUNE_STAMPS 0x4000           /* diagnostic (tools/stamp_gemm.py, tools/stamp_conv.py): run the stamped instantiation; colstats receives cycle counts per workgroup and wave, not statistics.  Built for the fp16 plain GEMM of variants 5 and 6 with the wide 16-bit epilogue and no residual, and for the patch-staged 3x3 convolution with Cout % 160 == 0; VFACE_ERR_SHAPE elsewhere */
+#define VFACE_TUNE_NARROW_EPILOGUE 0x8000  /* A/B: csrc/gemm.hip stores straight from the accumulator layout (8 bytes per lane), without the LDS transpose */
 #define VFACE_CONV_PAD_TRAILING 0x40000 /* vface_conv3x3: zero padding (left 0, right 1, top 0, bottom 1) instead of 1 all round */
 #define VFACE_TUNE_NO_PERSISTENT 0x10000 /* one workgroup per output tile even where the persistent form would run */
 #define VFACE_TUNE_PERSISTENT 0x20000    /* persistent form for a plain GEMM too (default: implicit convolutions only) */

@@ -101,3 +101,31 @@ def test_every_planned_split_fits_the_workspace_the_wrappers_ask_for(probe):
             splits += 1
             assert int(p["split_k"]) * f["M"] * f["N"] * 4 <= int(p["workspace_needed"]), (f, p)
     assert splits >= 20
+
+
+GEMM_OUT_F32, GEMM_STAMPS, GEMM_NARROW_EPILOGUE, GEMM_NO_PATCH, GEMM_PATCH = 2, 0x4000, 0x8000, 0x80000, 0x100000      # (dispatch.hpp; pinned against the header in test_host_cpu.py)
+VFACE_ERR_SHAPE = -3
+
+
+def test_stamped_launches_plan_onto_the_built_stamped_forms_or_are_refused(probe):
+    """GEMM_STAMPS has three instantiations behind it: gemm.hip's plain two-stage kernel at both tile widths (form 3), and the patch-staged 3x3
+    convolution 160 channels wide (form 3 there too).  Every other stamped launch is refused with VFACE_ERR_SHAPE, never run without stamps."""
+    ptrs = dict(A=0x10000, Wt=0x20000, C=0x30000, zeros=0x40000, bias=0x50000, colstats=0x60000)
+    plain = dict(ptrs, lda=192, ldw=192, Kw=192, M=200, N=320, K=192, rows_per_sample=1, ldc=320, ld_colstats=320)
+    conv = dict(ptrs, mode=1, lda=64, ldw=576, Kw=576, M=256, N=160, K=576, H=16, W=16, OH=16, OW=16, Cin=64, stride=1, pad=1,
+                rows_per_sample=256, ldc=160, ld_colstats=160)
+    launches = [dict(plain, flags=GEMM_STAMPS | (5 << 8)), dict(plain, flags=GEMM_STAMPS | (6 << 8)),
+                dict(plain, flags=GEMM_STAMPS | (5 << 8) | GEMM_OUT_F32), dict(plain, flags=GEMM_STAMPS | (5 << 8) | GEMM_NARROW_EPILOGUE),
+                dict(plain, flags=GEMM_STAMPS | (7 << 8)), dict(conv, flags=GEMM_STAMPS | GEMM_NO_PATCH),
+                dict(conv, flags=GEMM_STAMPS | GEMM_PATCH)]
+    w128, w160, f32, narrow, one_stage, im2col, patch = probe(launches)
+    for plan, bn in ((w128, 128), (w160, 160)):
+        assert (plan["rc"], plan["kernel"], plan["stages"], plan["mode"], plan["form"]) == ("0", "gemm", "2", "0", "3"), plan
+        assert (int(plan["bn"]), plan["persistent"], plan["split_k"], plan["reduce"]) == (bn, "0", "1", "0"), plan
+        assert plan["grid"] == f"{2 * ((320 + bn - 1) // bn)},1", plan
+    for refused in (f32, narrow, one_stage, im2col):
+        assert int(refused["rc"]) == VFACE_ERR_SHAPE and "kernel" not in refused, refused
+    assert (patch["rc"], patch["kernel"], patch["bn"], patch["mode"], patch["form"], patch["grid"]) == ("0", "conv_patch", "160", "3", "3", "1,1"), patch
+    # the same launches without the flag plan as before: form 0, and the refused forms run
+    for launch, plan in zip(launches, probe([dict(l, flags=l["flags"] & ~GEMM_STAMPS, colstats=0) for l in launches])):
+        assert plan["rc"] == "0" and plan["form"] == "0", (launch, plan)

@@ -478,3 +478,82 @@ def test_conv_refusals_launch_nothing():
         with pytest.raises(h.VFaceHipError, match=rf"\(code {ERR_SHAPE}\)"):
             h.conv3x3(xd, wd, out.view, **base, **kw)
     out.result("refused", rows=torch.arange(0))
+
+
+# ================================================================================================ 2.3 the stamped instantiations
+class StampBuffer:
+    """The ``colstats`` argument of a VFACE_TUNE_STAMPS launch: ``count`` floats behind a 16-byte-aligned offset into a flat sentinel
+    buffer, shaped ``[rows, n, 2]`` as the wrappers expect it (they pass its address and ``n`` on)."""
+
+    def __init__(self, count, n):
+        from kernel_bounds import sentinel
+        self.count, self.lead = count, 20
+        rows = -(-count // (2 * n))
+        self.keep = sentinel(1, self.lead + rows * 2 * n + 64, torch.float32).reshape(-1)
+        self.dev = self.keep.to(DEV)
+        self.arg = self.dev[self.lead:self.lead + rows * 2 * n].view(rows, n, 2)
+
+    def result(self, what, written=True):
+        """The ``count`` floats of the layout, after the check that every float before and behind them is still the sentinel."""
+        torch.cuda.synchronize()
+        allv = self.dev.cpu()
+        expect = self.keep.clone()
+        if written:
+            expect[self.lead:self.lead + self.count] = allv[self.lead:self.lead + self.count]
+        assert same_bits(allv, expect), f"{what}: a stamp outside the layout"
+        return allv[self.lead:self.lead + self.count].clone()
+
+
+def assert_counts(c, what):
+    assert torch.isfinite(c).all() and (c > 0).all() and (c < 2.0 ** 32).all(), (what, c)
+
+
+@pytest.mark.parametrize("variant", [5, 6])
+def test_gemm_stamped_instantiation(variant):
+    """M 200 x N 320 x K 192 (a row tail in the second m-tile, a column tail at width 128, three K tiles: prologue, steady state and last
+    tile): the stamped launch stores the bits of the plain one, and every wave of every workgroup files its counts inside
+    ``2 x [workgroup][wave][4]`` floats."""
+    h = hip()
+    dt, M, N, K = torch.float16, 200, 320, 192
+    a, w, b = strided(rnd((M, K), 31, dt), 8), rnd((N, K), 32, dt, 1 / math.sqrt(K)).to(DEV), rnd((N,), 33, torch.float32).to(DEV)
+    nwg = -(-M // 128) * -(-N // (128 if variant == 5 else 160))
+    plain, stamped, st = Framed(M, N, dt), Framed(M, N, dt), StampBuffer(2 * nwg * 16, N)
+    h.gemm(a, w, plain.view, M=M, N=N, K=K, lda=K + 16, ldc=plain.ld, bias=b, flags=variant << 8, split_k=False)
+    h.gemm(a, w, stamped.view, M=M, N=N, K=K, lda=K + 16, ldc=stamped.ld, bias=b, flags=(variant << 8) | h.TUNE_STAMPS, colstats=st.arg,
+           split_k=False)
+    want, got = plain.result(f"plain v{variant}"), stamped.result(f"stamped v{variant}")
+    assert want.abs().max() > 0.5 and torch.equal(got, want)
+    d = st.result(f"stamps v{variant}").view(2, nwg, 4, 4)
+    assert_counts(d[0, :, :, :3], f"v{variant}: prologue, K loop, epilogue")
+    assert torch.isfinite(d).all() and (d >= 0).all()
+
+
+def test_conv_patch_stamped_instantiation():
+    """64 -> 160 channels on one 16 x 16 image: one workgroup of eight waves, ``[workgroup][wave][8]`` floats."""
+    h = hip()
+    from vface_amd.packing import pack_conv3x3
+    dt, nimg, cin, cout, H = torch.float16, 1, 64, 160, 16
+    x, w = conv_inputs(dt, nimg, cin, cout, H, H)
+    xd, wd, b = nhwc(x), pack_conv3x3(w).to(DEV), rnd((cout,), 34, torch.float32).to(DEV)
+    plain, stamped, st = Framed(H * H, cout, dt), Framed(H * H, cout, dt), StampBuffer(8 * 8, cout)
+    base = dict(nimg=nimg, H=H, W=H, cin=cin, cout=cout, ldx=cin + 16, bias=b)
+    assert h.conv_uses_patch_kernel(H, H, cin, cout, 3, 1, False, h.TUNE_PATCH) == 1      # (the stamped plan is pinned in test_dispatch_cpu.py)
+    h.conv3x3(xd, wd, plain.view, ldy=plain.ld, flags=h.TUNE_PATCH, **base)
+    h.conv3x3(xd, wd, stamped.view, ldy=stamped.ld, flags=h.TUNE_PATCH | h.TUNE_STAMPS, colstats=st.arg, **base)
+    want, got = plain.result("plain patch"), stamped.result("stamped patch")
+    assert want.abs().max() > 0.5 and torch.equal(got, want)
+    d = st.result("patch stamps").view(8, 8)
+    assert_counts(d[:, :3], "patch: prologue, K loop, epilogue")
+    assert torch.isfinite(d).all() and (d >= 0).all()
+
+
+def test_stamped_launch_of_a_form_without_stamps_is_refused():
+    """The fp32 output has no stamped instantiation: VFACE_ERR_SHAPE, neither the output nor the stamp buffer written."""
+    h = hip()
+    dt, M, N, K = torch.float16, 200, 320, 192
+    a, w = rnd((M, K), 31, dt).to(DEV), rnd((N, K), 32, dt, 1 / math.sqrt(K)).to(DEV)
+    out, st = Framed(M, N, torch.float32), StampBuffer(2 * 6 * 16, N)
+    with pytest.raises(h.VFaceHipError, match=rf"\(code {ERR_SHAPE}\)"):
+        h.gemm(a, w, out.view, M=M, N=N, K=K, lda=K, ldc=out.ld, flags=(5 << 8) | h.TUNE_STAMPS | h.EPI_OUT_F32, colstats=st.arg, split_k=False)
+    out.result("refused", rows=torch.arange(0))
+    st.result("refused", written=False)

@@ -82,6 +82,31 @@ def test_ctypes_table_matches_header_type_for_type():
     assert checked >= 74
 
 
+def test_flags_word_is_stated_alike_in_header_enum_and_binding():
+    """The flags word of the GEMM-family calls is defined three times: the #defines of the header (the ABI), the GEMM_* enum the
+    kernels and dispatch.cpp read, and hip.py's constants.  Every bit must be in all three with one value, each a single bit of
+    its own outside the variant field (bits 8..11)."""
+    from vface_amd import hip
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    header = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define\s+VFACE_((?:EPI|TUNE|CONV)_\w+)\s+(0x[0-9a-fA-F]+|\d+)\s*$", src, flags=re.M)}
+    assert len(header) >= 19 and {"EPI_GEGLU", "TUNE_STAMPS", "TUNE_NO_XCD_REMAP", "TUNE_NO_SETPRIO", "TUNE_NARROW_EPILOGUE", "CONV_PAD_TRAILING"} <= set(header)
+    hpp = open(os.path.join(ROOT, "vface_amd", "csrc", "dispatch.hpp")).read()
+    enum = re.sub(r"/\*.*?\*/", "", hpp[hpp.index("enum {"):hpp.index("};", hpp.index("enum {"))], flags=re.S)
+    gemm = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"\bGEMM_(\w+)\s*=\s*(0x[0-9a-fA-F]+|\d+)", enum)}
+    # the enum's name of a header flag, where it is not the header's own without its EPI_ / TUNE_ prefix
+    other = {"TUNE_NO_PERSISTENT": "NO_PERSIST", "TUNE_PERSISTENT": "PERSIST", "TUNE_BIG_TILE": "BIG", "TUNE_NO_BIG_TILE": "NO_BIG"}
+    # (VFACE_CONV_PAD_TRAILING is consumed by the entry point: it becomes GemmParams::pad and no kernel reads the bit)
+    want = {other.get(name, name.split("_", 1)[1]): v for name, v in header.items() if name != "CONV_PAD_TRAILING"}
+    assert gemm == want
+    for name, v in header.items():
+        assert getattr(hip, name) == v, name
+    assert {n for n in vars(hip) if re.match(r"(EPI|TUNE|CONV)_[A-Z0-9_]+$", n)} == set(header)
+    assert len(set(header.values())) == len(header)
+    for name, v in header.items():
+        assert v > 0 and v & (v - 1) == 0 and not v & (0xF << 8), name
+    assert "VFACE_TUNE_VARIANT(v) ((v) << 8)" in src
+
+
 def test_no_gpu_means_loud_failure():
     from vface_amd import hip
     hip.load()

@@ -2,8 +2,9 @@
 """A/B of TWO BUILDS of libvface_hip.so in one process, interleaved rounds (guide rule 24): the same C-ABI call timed through
 both libraries alternately.  usage: python tools/ab_libs.py <base.so> <new.so> [what ...]
 what: attn40 (dh=40, n=4096, 24 samples), attn40s3 (shared-score form, 8 frames x 3 value sets), attn80, attn160,
-      gemm:<M>x<N>x<K>[:geglu|:res32] ...   Prints median / min microseconds per build and the ratio; for attention also the
-      rel-L2 of each build against an fp64 reference (2 samples)."""
+      gemm:<M>x<N>x<K>[:geglu|:res32|:nobig] ...   Prints median / min microseconds per build and the ratio; for GEMMs and
+      convolutions whether the two builds store the same bits; for attention the rel-L2 of each build against an fp64
+      reference (2 samples)."""
 import ctypes as C
 import os
 import statistics
@@ -78,6 +79,18 @@ def attn_case(dh, n, N, sets=1, variant=0):
     print(f"    outputs bit-identical across builds: {torch.equal(outs[ks[0]], outs[ks[1]])}")
 
 
+def bit_identity(run, out):
+    """One more call through each build into the zeroed ``out``: are the two results the same bits?"""
+    outs = {}
+    for k in LIBS:
+        use(k); out.zero_(); run(); torch.cuda.synchronize()
+        outs[k] = out.clone()
+    ks = list(LIBS)
+    d = (outs[ks[0]].float() - outs[ks[1]].float())
+    print(f"    outputs bit-identical across builds: {torch.equal(outs[ks[0]], outs[ks[1]])}; rel-L2 of the difference {(d.norm() / outs[ks[0]].float().norm()).item():.2e}; "
+          f"elements that differ {(d != 0).float().mean().item():.2e}")
+
+
 def gemm_case(spec):
     parts = spec.split(":")
     M, N, K = (int(v) for v in parts[0].split("x"))
@@ -91,12 +104,13 @@ def gemm_case(spec):
         run = lambda: hip.gemm(a, w, out, M=M, N=N, K=K, lda=K, ldc=N // 2, bias=bias, flags=hip.EPI_GEGLU)
     elif mode == "res32":
         r32 = torch.randn(M, N, device=DEV, generator=g)
-        o32 = torch.empty(M, N, device=DEV)
-        run = lambda: hip.gemm(a, w, None, M=M, N=N, K=K, lda=K, ldc=0, bias=bias, residual32=r32, out32=o32)
-    else:
+        out = torch.empty(M, N, device=DEV)
+        run = lambda: hip.gemm(a, w, None, M=M, N=N, K=K, lda=K, ldc=0, bias=bias, residual32=r32, out32=out)
+    else:      # ("nobig": the 128-row kernel of gemm.hip where the library would take the 256-row tile)
         out = torch.empty(M, N, dtype=torch.float16, device=DEV)
-        run = lambda: hip.gemm(a, w, out, M=M, N=N, K=K, lda=K, ldc=N, bias=bias)
+        run = lambda: hip.gemm(a, w, out, M=M, N=N, K=K, lda=K, ldc=N, bias=bias, flags=hip.TUNE_NO_BIG_TILE if mode == "nobig" else 0)
     ab(f"gemm {spec}", run, flops=2.0 * M * N * K)
+    bit_identity(run, out)
 
 
 def conv_case(spec):
@@ -118,14 +132,7 @@ def conv_case(spec):
         kw.update(residual32=r32, out32=o32)
     run = lambda: hip.conv3x3(x, w, out, **kw)
     ab(f"conv3x3 {spec}", run, flops=2.0 * N * H * H * cout * 9 * cin)
-    outs = {}
-    for k in LIBS:
-        use(k); out.zero_(); run(); torch.cuda.synchronize()
-        outs[k] = out.clone()
-    ks = list(LIBS)
-    d = (outs[ks[0]].float() - outs[ks[1]].float())
-    print(f"    outputs bit-identical across builds: {torch.equal(outs[ks[0]], outs[ks[1]])}; rel-L2 of the difference {(d.norm() / outs[ks[0]].float().norm()).item():.2e}; "
-          f"elements that differ {(d != 0).float().mean().item():.2e}")
+    bit_identity(run, out)
 
 
 if __name__ == "__main__":

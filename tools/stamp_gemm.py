@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic: prologue / K loop / epilogue cycles per wave of the plain GEMM (gemm.hip flag 0x4000) on the short-K level-0 shapes."""
+"""Diagnostic: prologue / K loop / epilogue cycles per wave of the plain GEMM (gemm.hip's stamped instantiation, flag TUNE_STAMPS) on the short-K level-0 shapes."""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,10 +15,10 @@ for name, M, N, K, var in [("qkv L0", 98304, 960, 320, 6), ("proj L0", 98304, 32
     bn = 160 if var == 6 else 128
     nblk = ((M + 127) // 128) * ((N + bn - 1) // bn)
     dbg = torch.zeros(nblk * 32 // (2 * N) + 2, N, 2, dtype=torch.float32, device="cuda")
-    for abl, fl in (("16-bit out", 0),):   # (the diagnostic flag is not accepted together with the fp32 stream operands)
+    for abl, fl in (("16-bit out", 0),):   # (stamps are built for the 16-bit wide epilogue without a residual only)
         kw = {}
         for _ in range(3):
-            hip.gemm(x, w, out, M=M, N=N, K=K, lda=K, ldc=N, bias=b, flags=(var << 8) | 0x4000 | fl, colstats=dbg, split_k=False, **kw)
+            hip.gemm(x, w, out, M=M, N=N, K=K, lda=K, ldc=N, bias=b, flags=(var << 8) | hip.TUNE_STAMPS | fl, colstats=dbg, split_k=False, **kw)
         torch.cuda.synchronize()
         d = dbg.flatten()[: nblk * 16].reshape(nblk, 4, 4).cpu()
         m = d.mean(dim=(0, 1))

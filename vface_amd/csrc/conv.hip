@@ -36,7 +36,13 @@ namespace {
 
 constexpr int TP = VF_PATCH_TP;        // output tile: TP x TP pixels of one image (16; dispatch.hpp)
 
-// DIAG: diagnostic build (flag 0x4000, tools/stamp_conv.py; never used by the engine): s_memtime stamps around the parts of
+// Ablation switches of the stamped build (added by hand to the flags of tools/stamp_conv.py): read in the DIAG instantiation only, where they take the
+// K loop's LDS-DMA and its waits, the workgroup barriers or the fragment reads out to see what the rest costs (the outputs are then wrong).  The first two deliberately alias GEMM_BIG_W256 and GEMM_BIG_W320,
+// the width bits of gemm_big.hip's tile, which this kernel never consults; the third is no flag of any other kernel.
+enum { ABL_NO_LOOP_DMA = 0x200000, ABL_NO_BARRIER = 0x400000, ABL_NO_FRAGMENT_READS = 0x800000 };
+static_assert(ABL_NO_LOOP_DMA == GEMM_BIG_W256 && ABL_NO_BARRIER == GEMM_BIG_W320, "the ablation bits alias the big tile's width bits");
+
+// DIAG: diagnostic build (flag GEMM_STAMPS, tools/stamp_conv.py; never used by the engine): s_memtime stamps around the parts of
 // the kernel and of every K-tile period; the sums go to the colstats pointer as [workgroup][wave][8] floats and feed no output.
 // GNT: the build with the fused input normalisation (GroupNorm-apply + SiLU on the staged patch); a separate instantiation so
 // the plain convolution keeps its register allocation.
@@ -185,7 +191,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
 
     // weight tile kt -> ring slot `slot` (every K tile is 64 columns = 128 B of every weight row)
     auto issue_B = [&](int kt, int slot) {
-        if (DIAG && (p.flags & 0x200000) && kt >= 2) return;     // ablation: no LDS-DMA inside the K loop
+        if (DIAG && (p.flags & ABL_NO_LOOP_DMA) && kt >= 2) return;     // ablation: no LDS-DMA inside the K loop
         unsigned char* dst = sB + slot * BSLOT;
         const unsigned koff = (unsigned)(kt0 + kt) * 64u * ES;
 #pragma unroll
@@ -198,7 +204,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     };
     // piece i (compile-time) of this wave for the window patch of channel chunk c
     auto issue_P = [&](int c, int i) {
-        if (DIAG && (p.flags & 0x200000) && c >= 1) return;
+        if (DIAG && (p.flags & ABL_NO_LOOP_DMA) && c >= 1) return;
         const int piece = wave + 8 * i;
         if (piece < NPIECES) {
             const unsigned off = poff[i] != OOB ? poff[i] + (unsigned)c * 64u * ES : OOB;
@@ -322,14 +328,14 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
     // order): tile kt, and every patch piece issued before it; then the workgroup barrier that publishes them
     auto period_sync = [&](bool more) {
         if (gn) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's in-place patch transforms are in LDS
-        if (DIAG && (p.flags & 0x200000)) { if (!(p.flags & 0x400000)) __builtin_amdgcn_s_barrier(); return; }   // ablation: no DMA wait
+        if (DIAG && (p.flags & ABL_NO_LOOP_DMA)) { if (!(p.flags & ABL_NO_BARRIER)) __builtin_amdgcn_s_barrier(); return; }   // ablation: no DMA wait
         if (more) {
             if (NB_SPLIT == 0 || wave >= NB_SPLIT) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB_LO) : "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NB_HI) : "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        if (!(DIAG && (p.flags & 0x400000))) __builtin_amdgcn_s_barrier();                                        // ablation: no barrier
+        if (!(DIAG && (p.flags & ABL_NO_BARRIER))) __builtin_amdgcn_s_barrier();                                        // ablation: no barrier
         asm volatile("" ::: "memory");
     };
 
@@ -394,7 +400,7 @@ __global__ __launch_bounds__(512, 2) void conv_patch_kernel(GemmParams p) {
             mfma_X();
             __builtin_amdgcn_sched_barrier(0);
             ++kt;
-            if (DIAG && (p.flags & 0x800000)) abl_reads = true;
+            if (DIAG && (p.flags & ABL_NO_FRAGMENT_READS)) abl_reads = true;
         }
     }
     // ---- tail: the fused 1x1 shortcut -- one 16 x 16-pixel x 64-channel tile of the second source per K tile

@@ -41,7 +41,7 @@ int tile_group(int ntm, int ntn, double a_mt, double w_nt, bool l2_cap) {
 bool conv_in16_ok(const GemmParams& p) {
     if (p.mode != 1 || p.Cin != 16 || p.ntaps != 9 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.upsample || p.pad != 1 || p.pad_x != 1) return false;
     if (p.A2 || p.residual || p.rowbias || p.gn_ab || p.out_phase || p.res_f32) return false;
-    if (p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NO_PATCH | 0x4000 | (0xF << 8))) return false;      // (GEMM_NO_PATCH: A/B, the generic kernel)
+    if (p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NO_PATCH | GEMM_STAMPS | (0xF << 8))) return false;      // (GEMM_NO_PATCH: A/B, the generic kernel)
     if ((p.N % VF_IN16_CH) || p.K != VF_IN16_K || p.Kw < VF_IN16_K || (p.ldw & 7)) return false;
     if (p.OH != p.H || p.OW != p.W || ((p.H * p.W) & 63) || (p.W & 15) || p.M != (p.M / (p.H * p.W)) * p.H * p.W) return false;
     if (!p.C && !p.C32) return false;
@@ -60,16 +60,16 @@ int conv_patch_tile(const GemmParams& p) {
     if (!((p.KH == 3 && p.KW == 3) || (p.KH == 2 && p.KW == 2)) || p.ntaps != p.KH * p.KW) return 0;
     if (p.pad < 0 || p.pad_x < 0 || p.pad > 1 || p.pad_x > 1) return 0;
     if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE)) || (p.N & 7)) return 0;
-    if ((p.flags & 0x4000) && !(p.KH == 3 && p.N % 160 == 0 && p.colstats)) return 0;   // diagnostic build: one instantiation
+    if ((p.flags & GEMM_STAMPS) && !(p.KH == 3 && p.N % 160 == 0 && p.colstats)) return 0;   // the stamped build: one instantiation
     if (p.A2 && (((p.K - p.K1) & 63) || p.KH != 3)) return 0;
-    if (p.gn_ab && (p.KH != 3 || (p.ld_gn_ab < p.Cin) || misaligned(p.gn_ab, 15) || (p.flags & 0x4000))) return 0;
+    if (p.gn_ab && (p.KH != 3 || (p.ld_gn_ab < p.Cin) || misaligned(p.gn_ab, 15) || (p.flags & GEMM_STAMPS))) return 0;
     if (p.colstats && ((p.H * p.W) & 63)) return 0;
     if (p.residual && !p.res_f32 && (misaligned(p.residual, 15) || (p.ldr & 7))) return 0;
     if (misaligned(p.C, 15) || (p.C && (p.ldc & 7))) return 0;
     const bool ok160 = p.N % 160 == 0, ok128 = p.N % 128 == 0;
     if (p.gn_ab) return ok128 ? 128 : 0;   // the fused-normalisation build exists 128 wide only (the 160-wide one spilled 36 B)
     if (p.KH == 2 && (p.residual || p.res_f32)) return ok128 ? 128 : 0;      // ... and so does the 2 x 2 window with a residual operand
-    if (ok160 && ok128 && !(p.flags & (GEMM_PATCH_BN160 | 0x4000))) {
+    if (ok160 && ok128 && !(p.flags & (GEMM_PATCH_BN160 | GEMM_STAMPS))) {
         // Both widths tile N (640, 1280, 1920 channels): one workgroup per CU, so a launch takes ceil(workgroups / CUs) rounds, and a 128-wide
         // workgroup takes ~0.8 of a 160-wide one (32 instead of 40 MFMAs per wave and K tile, same fixed costs).  Measured
         // (tools/quantisation_probe.py, 24 samples): 32x32 640->640: 160-wide 384 workgroups = 1.5 rounds 181.6 us, 128-wide 480 = 1.9 rounds 153.6
@@ -92,7 +92,7 @@ int q8_grid_split(int N) {
 int conv_q8_split(const GemmParams& p) {
     if (p.mode != 1 || p.stride != 1 || p.upsample || p.out_phase || (p.Cin & 63) || p.gn_ab) return 0;
     if (p.H != 8 || p.W != 8 || p.OH != 8 || p.OW != 8 || p.KH != 3 || p.KW != 3 || p.ntaps != 9 || p.pad != 1 || p.pad_x != 1) return 0;
-    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_NO_PATCH | 0x4000 | (0xF << 8))) || (p.N % 128)) return 0;
+    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_NO_PATCH | GEMM_STAMPS | (0xF << 8))) || (p.N % 128)) return 0;
     if (p.A2 && ((p.K - p.K1) & 63)) return 0;
     if (p.rows_per_sample != 64 && p.rowbias) return 0;
     const int nchunks = p.Cin >> 6;
@@ -120,7 +120,7 @@ int conv_kernel_choice(const GemmParams& p, int* arg) {
 int gemm_patch_tile(const GemmParams& p) {
     if (p.mode != 0 || p.A2 || p.out_phase || p.gn_ab || p.split_k > 1) return 0;
     if ((p.M % (TP * TP)) || (p.K & 63) || p.K < 128) return 0;
-    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | 0x4000)) || (p.N & 7)) return 0;
+    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_STAMPS)) || (p.N & 7)) return 0;
     if (p.rowbias && (p.rows_per_sample <= 0 || (p.rows_per_sample % (TP * TP)))) return 0;
     if (p.residual && !p.res_f32 && (misaligned(p.residual, 15) || (p.ldr & 7))) return 0;
     if (misaligned(p.C, 15) || (p.C && (p.ldc & 7))) return 0;
@@ -132,7 +132,7 @@ bool gemm_big_ok(const GemmParams& p) {
     if (p.mode != 0 || p.out_phase || p.gn_ab || p.split_k > 1 || p.a2_row_mod) return false;
     if ((p.N % BN2) || (p.K & 63) || p.K < 128 || (p.Kw < p.K)) return false;
     if (p.A2 && ((p.K1 & 63) || p.K1 <= 0 || p.K1 >= p.K)) return false;
-    if (p.flags & (GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_F32_TRANSPOSE | 0x4000 | (0xF << 8))) return false;
+    if (p.flags & (GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_F32_TRANSPOSE | GEMM_STAMPS | (0xF << 8))) return false;
     if (p.C32) {
         // the fp32 residual-stream form (EPI 3): carrier required; the per-sample row bias needs every 256-row tile inside one sample
         if (p.flags & GEMM_GEGLU) return false;
@@ -218,14 +218,26 @@ bool split_operands_ok(const GemmParams& p, int s) {
            !(p.residual && (misaligned(p.residual, 15) || (p.ldr & 7))) && !(p.ldc & 7) && !misaligned(p.C, 15);
 }
 
+// THE rule for GEMM_STAMPS: is there a stamped instantiation for this launch?  conv.hip builds one (the patch-staged 3x3 kernel, 160 channels wide:
+// conv_patch_tile) and gemm.hip one per tile width of its plain two-stage kernel with the wide 16-bit epilogue and no residual; no other form
+// carries timing code.  The launch's colstats pointer is its stamp buffer, so no rule about statistics applies to it.
+bool stamps_built(const GemmParams& p) {
+    if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE)) || (p.N & 7) || p.residual || p.C32 || p.gn_ab) return false;
+    int arg;
+    if (p.mode == 1) return conv_kernel_choice(p, &arg) == 1;
+    return p.mode == 0 && (forced_variant(p.flags) == 0 || forced_variant(p.flags) == 5 || forced_variant(p.flags) == 6);
+}
+
 int validate(GemmParams& p) {
     p.split_k = 1; p.kt_per_split = 0;
     if (!p.A || !p.Wt || (!p.C && !p.C32) || !p.zeros) return VFACE_ERR_ARG;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return VFACE_ERR_ARG;
+    if (p.mode == 1 && p.ntaps == 0) { p.KH = p.KW = 3; p.ntaps = 9; p.pad_x = p.pad; }   // the plain 3x3 window
+    if ((p.flags & GEMM_STAMPS) && !stamps_built(p)) return VFACE_ERR_SHAPE;
     if (p.res_f32 && !p.residual) p.res_f32 = 0;
     if (p.res_f32 || p.C32) {
         // the fp32 residual stream lives in the wide epilogue (and the split-K reduce) only
-        if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | 0x4000)) || (p.N & 7)) return VFACE_ERR_SHAPE;
+        if ((p.flags & (GEMM_GEGLU | GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE)) || (p.N & 7)) return VFACE_ERR_SHAPE;
         if (p.C32 && (misaligned(p.C32, 15) || (p.ldc32 & 3))) return VFACE_ERR_ALIGN;
         if (p.res_f32 && (misaligned(p.residual, 15) || (p.ldr & 3))) return VFACE_ERR_ALIGN;
         if (p.out_phase && p.res_f32) return VFACE_ERR_SHAPE;
@@ -241,7 +253,6 @@ int validate(GemmParams& p) {
     if (p.A2 && (p.K1 <= 0 || (p.K1 % BK) || (p.lda2 & 7) || misaligned(p.A2, 15))) return VFACE_ERR_ALIGN;
     if (p.A2 && p.mode == 1 && ((p.Cin % 64) || ((p.K - p.K1) % BK) || p.upsample || p.a2_row_mod)) return VFACE_ERR_SHAPE;
     if (p.mode == 1) {
-        if (p.ntaps == 0) { p.KH = p.KW = 3; p.ntaps = 9; p.pad_x = p.pad; }   // the plain 3x3 window
         if (p.Cin <= 0 || (p.Cin & 7) || p.ntaps != p.KH * p.KW || p.ntaps > 9) return VFACE_ERR_SHAPE;
         if (p.A2 ? (p.K1 != p.ntaps * p.Cin || p.K <= p.K1) : (p.K != p.ntaps * p.Cin)) return VFACE_ERR_SHAPE;
         if (p.out_phase && (p.residual || (p.flags & GEMM_OUT_F32) || (p.N & 7))) return VFACE_ERR_SHAPE;
@@ -282,7 +293,7 @@ void plan_patch(VfGemmPlan& pl, int kernel, int bn) {
     const GemmParams& p = pl.p;
     const int KH = p.KH, KW = p.KW, npieces = ((TP + KW - 1) * (TP + KH - 1) + 7) / 8, nslot = (KH * KW % 3 == 0) ? 3 : 4;
     const int ntm = (p.M / (p.OH * p.OW)) * (p.H / TP) * (p.W / TP), ntn = p.N / bn;
-    pl.kernel = kernel; pl.bn = bn; pl.mode = KH; pl.form = p.gn_ab ? 4 : (p.flags & 0x4000) ? 3 : residual_form(p);
+    pl.kernel = kernel; pl.bn = bn; pl.mode = KH; pl.form = p.gn_ab ? 4 : (p.flags & GEMM_STAMPS) ? 3 : residual_form(p);
     pl.lds_bytes = 2 * npieces * 1024 + nslot * bn * 128 + (KH == 3 ? 2048 : 0); pl.grid_x = ntm * ntn;
     const double a_mt = (double)(TP + KW - 1) * (TP + KH - 1) * (p.Cin + (p.A2 ? (p.K - p.K1) : 0)) * 2.0;
     pl.p.tile_group = tile_group(ntm, ntn, a_mt, (double)bn * p.K * 2.0, false);
@@ -345,7 +356,7 @@ int vf_plan_gemm(const GemmParams& p_in, int persistent_grid, VfGemmPlan* plan) 
     if ((p.flags & GEMM_GEGLU) && (variant == 6 || variant == 8)) return VFACE_ERR_SHAPE;
     if (p.colstats && variant > 8) return VFACE_ERR_SHAPE;
     // 6. split-K
-    if (p.workspace && !p.out_phase && wide && !forced_variant(p.flags) && !(p.flags & 0x4000)) {
+    if (p.workspace && !p.out_phase && wide && !forced_variant(p.flags) && !(p.flags & GEMM_STAMPS)) {
         const int s = split_for(p.M, p.N, p.K, p.flags, p.rows_per_sample);
         if (s > 1 && split_operands_ok(p, s)) {
             const int nt = (p.K + BK - 1) / BK;
@@ -355,14 +366,14 @@ int vf_plan_gemm(const GemmParams& p_in, int persistent_grid, VfGemmPlan* plan) 
         }
     }
     pl.kernel = VF_KERNEL_GEMM; pl.bn = (variant == 5 || variant == 7) ? 128 : 160; pl.stages = wide ? 2 : 1;
-    pl.mode = p.mode == 0 ? 0 : (p.Cin % 64 == 0 ? 1 : 2); pl.form = residual_form(p); pl.reduce = p.split_k > 1;
+    pl.mode = p.mode == 0 ? 0 : (p.Cin % 64 == 0 ? 1 : 2); pl.form = (p.flags & GEMM_STAMPS) ? 3 : residual_form(p); pl.reduce = p.split_k > 1;
     pl.lds_bytes = pl.stages * (BM + pl.bn) * BK * 2;
     const int ntn = (p.N + pl.bn - 1) / pl.bn, ntm = (p.M + BM - 1) / BM, ntiles = ntm * ntn;
     // 7. persistent form: only where a workgroup would get more than one tile and the wide epilogue applies (measured on the UNet's shapes: +1..3 % for
     // the implicit convolutions, +-2 % noise for plain GEMMs, which keep one tile per workgroup unless GEMM_PERSIST asks otherwise), and only in the
     // instantiations that exist: not the generic window, not with a residual (they spilled 22-41 registers: gemm.hip launch_one)
     pl.persistent = wide && pl.mode != 2 && p.split_k == 1 && pl.form == 0 &&
-                    !(p.flags & (GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_NO_PERSIST | 0x4000)) &&
+                    !(p.flags & (GEMM_OUT_F32 | GEMM_NARROW_EPILOGUE | GEMM_NO_PERSIST | GEMM_STAMPS)) &&
                     !(p.N & 7) && ntiles > persistent_grid && (pl.mode != 0 || (p.flags & GEMM_PERSIST));
     pl.grid_x = pl.persistent ? persistent_grid : ntiles * p.split_k;
     // 8. tile order of the plain GEMM

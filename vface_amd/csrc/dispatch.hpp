@@ -4,7 +4,7 @@
 #pragma once
 #include <stdint.h>
 
-enum { GEMM_GEGLU = 1, GEMM_OUT_F32 = 2, GEMM_NO_XCD_REMAP = 0x1000, GEMM_NO_SETPRIO = 0x2000, GEMM_NARROW_EPILOGUE = 0x8000, GEMM_NO_PERSIST = 0x10000, GEMM_PERSIST = 0x20000,
+enum { GEMM_GEGLU = 1, GEMM_OUT_F32 = 2, GEMM_NO_XCD_REMAP = 0x1000, GEMM_NO_SETPRIO = 0x2000, GEMM_STAMPS = 0x4000 /* the stamped instantiation: cycle counts per part go to the colstats pointer (tools/stamp_gemm.py, stamp_conv.py) */, GEMM_NARROW_EPILOGUE = 0x8000, GEMM_NO_PERSIST = 0x10000, GEMM_PERSIST = 0x20000,
        GEMM_NO_PATCH = 0x80000, GEMM_PATCH = 0x100000, GEMM_GN8 = 0x8000000 /* A/B: fixed column groups of 8 n-tiles in the plain GEMM's tile order */, GEMM_NO_Q8 = 0x4000000 /* A/B: the 8x8 level stays on the im2col kernel */, GEMM_PATCH_BN160 = 0x2000000 /* A/B: the patch kernel's 160-wide tile wherever it divides N */, GEMM_F32_TRANSPOSE = 0x1000000 /* A/B: epilogue transposes in fp32 even where 16 bits would do */,
        GEMM_BIG = 0x10000000 /* take gemm_big.hip's 256 x 320 tile whenever the launch qualifies */, GEMM_NO_BIG = 0x20000000 /* A/B: never */,
        GEMM_BIG_W256 = 0x200000 /* gemm_big.hip: the 256-channel tile width wherever N allows it */, GEMM_BIG_W320 = 0x400000 /* ... never */ };  // (0x40000 = VFACE_CONV_PAD_TRAILING)  // bits 8..11 of flags: forced schedule variant (0 = automatic)
@@ -72,7 +72,7 @@ struct VfGemmPlan {
     GemmParams p;
     int kernel, bn;    // VfGemmKernel; tile width in channels
     int stages, mode;  // gemm.hip: LDS stages 1 | 2; 0 plain | 1 convolution, Cin % 64 == 0 | 2 convolution, generic window.  conv.hip: mode = the window, 3 | 2
-    int form;          // residual form 0 none | 1 16-bit | 2 fp32 (conv.hip also 3 diagnostic stamps | 4 fused GroupNorm); gemm_big.hip: epilogue 0 bias | 1 GEGLU | 2 residual | 3 fp32 stream
+    int form;          // residual form 0 none | 1 16-bit | 2 fp32 | 3 cycle stamps (GEMM_STAMPS) (conv.hip also 4 fused GroupNorm); gemm_big.hip: epilogue 0 bias | 1 GEGLU | 2 residual | 3 fp32 stream
     bool persistent;   // gemm.hip: grid_x resident workgroups walk the tiles
     bool reduce;       // the split-K reduce follows: it sums the fp32 partial tiles in split order and runs the epilogue (always behind the 8x8 form)
     int grid_x, grid_y, lds_bytes;      // (dynamic LDS)

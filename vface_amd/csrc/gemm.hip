@@ -35,9 +35,16 @@ namespace {
 constexpr int BM = VF_GEMM_BM, BK = VF_GEMM_BK;      // 128, 64 (dispatch.hpp)
 enum { MODE_PLAIN = 0, MODE_CONV_FAST = 1, MODE_CONV_GENERIC = 2 };
 
+// Cycle counts of the stamped instantiation; the product instantiations hold none.
+template <bool DIAG> struct GemmStamps {};
+template <> struct GemmStamps<true> { unsigned long long t0, t1, t2, last, epi[4]; };
+
 // RM: the residual form of the wide epilogue (0 none, 1 16-bit, 2 the fp32 stream) as an instantiation of its own; -1 = chosen
 // at run time (three copies of the epilogue in one kernel: 16-38 spilled registers at NT = 5, kept for the rare forms only)
-template <class TT, int MODE, int NT, bool DB, bool PERSIST, int RM = -1>
+// DIAG: the stamped build (flag GEMM_STAMPS, tools/stamp_gemm.py; never used by the engine): s_memtime stamps around prologue, K
+// loop and epilogue and around the four parts of every wide-epilogue pass.  The sums go to the colstats pointer as two blocks of
+// [workgroup][wave][4] floats and feed no output value.  Every stamp is `if constexpr (DIAG)`: no other instantiation has timing code.
+template <class TT, int MODE, int NT, bool DB, bool PERSIST, int RM = -1, bool DIAG = false>
 __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
     using E = typename TT::elem;
     using V8 = typename TT::v8;
@@ -51,8 +58,26 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
     const int lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    unsigned long long dbg_t0 = 0, dbg_t1 = 0, dbg_t2 = 0, dbg_e0 = 0, dbg_ew = 0, dbg_er = 0, dbg_es = 0;   // (diagnostic launches only)
-    if (p.flags & 0x4000) dbg_t0 = __builtin_amdgcn_s_memtime();
+    GemmStamps<DIAG> dbg{};
+    auto stamp = [&]() -> unsigned long long {
+        if constexpr (!DIAG) return 0ull;
+        unsigned long long tt;
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt)::"memory");
+        __builtin_amdgcn_sched_barrier(0);
+        return tt;
+    };
+    // End of part `part` of the wide epilogue (0 setup | 1 LDS writes | 2 LDS read wait | 3 convert + store).  DIAG: the cycles since the
+    // previous stamp go to the part's sum.  Every other instantiation keeps the scheduling boundary alone (no instruction): the parts of a
+    // 16-row pass are scheduled one by one.  Without it hipcc interleaves the four passes and eight of the eighteen two-stage
+    // instantiations of an element type take 3-12 more vector registers (229 -> 241 for the plain GEMM at NT = 5).
+    auto lap = [&](int part) {
+        if constexpr (DIAG) { const unsigned long long tt = stamp(); dbg.epi[part] += tt - dbg.last; dbg.last = tt; }
+        else __builtin_amdgcn_sched_barrier(0);
+    };
+    float* const stamps_out = DIAG ? p.colstats : nullptr;   // a stamped launch has no statistics: the pointer carries its stamp buffer
+    if (DIAG) p.colstats = nullptr;
+    if constexpr (DIAG) dbg.t0 = __builtin_amdgcn_s_memtime();
     // XCD-aware tile order (guide T1).  Workgroups are dealt round-robin to the 8 XCDs, each with its own 4 MiB L2.
     // Every XCD gets a contiguous run of the tile sequence L (bijective for any grid size: q = nwg/8, r = nwg%8),
     // and L walks the tile grid in column groups of GN = 8 n-tiles, m-major inside a group: the ~64 tiles an XCD
@@ -303,17 +328,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
         E* Cout = reinterpret_cast<E*>(p.C);
         float* C32 = p.C32;
         float* colstats = p.colstats;
-        const bool want_stats = colstats && !(p.flags & 0x4000);
-        const bool diag = p.flags & 0x4000;          // diagnostic launches (tools/stamp_gemm.py): s_memtime stamps around the parts
-        auto estamp = [&]() -> unsigned long long {
-            if (!diag) return 0;
-            unsigned long long t;
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-            __builtin_amdgcn_sched_barrier(0);
-            return t;
-        };
-        const unsigned long long e_in = estamp();
+        if constexpr (DIAG) dbg.last = stamp();
         float* scr = scr_base + wave * (16 * SP);
         const int OW = gg ? WN / 2 : WN;              // output columns of this wave
         const int CH = OW >> 3;                       // 16-byte chunks per output row
@@ -391,8 +406,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
                 acc[j][i][2] = (acc[j][i][2] + bj[j].z) + rbj[j].z; acc[j][i][3] = (acc[j][i][3] + bj[j].w) + rbj[j].w;
             }
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every load of this epilogue has landed; from here on only stores fly
-        unsigned long long e_t = estamp();
-        dbg_e0 = e_t - e_in;
+        lap(0);
         // per-lane output pointers at slab row `rrow`; the row of (tile row i, pass it) is a wave-uniform offset from them
         const bool phased = MODE != MODE_PLAIN && p.out_phase;
         E* pC = Cout + (long)(wrow0 + rrow) * p.ldc + ncol;
@@ -440,7 +454,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
                 // LDS operations of one wave execute in order: the reads below see the writes above, and the next
                 // tile row's writes cannot overtake these reads.  Every lane reads (rows clamped into the scratch), only
                 // the stores are predicated: the RI x 2 reads of the pass go out back to back.
-                { const unsigned long long t = estamp(); dbg_ew += t - e_t; e_t = t; }
+                lap(1);
                 float4 x[HALF ? 1 : RI][2];
                 V8 xh[HALF ? RI : 1];
 #pragma unroll
@@ -453,7 +467,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
                         x[it][1] = *reinterpret_cast<const float4*>(lrd + rc * SP + 4);
                     }
                 }
-                if (diag) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t = estamp(); dbg_er += t - e_t; e_t = t; }
+                if constexpr (DIAG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the wait for the reads above is part 2)
+                lap(2);
 #pragma unroll
                 for (int it = 0; it < RI; ++it) {
                     const int r = rrow + it * LPR;
@@ -500,7 +515,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
                                 *reinterpret_cast<float4*>(d32 + 4) = make_float4(v[4], v[5], v[6], v[7]);
                             }
                         }
-                        if (want_stats) {
+                        if (colstats) {
                             // statistics of the values the following GroupNorm will read: the fp32 carrier if there is one
                             if (!HALF && C32) {
 #pragma unroll
@@ -515,12 +530,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
                 if constexpr (RMODE != 0 && DEPTH < 4) {
                     if (i + DEPTH < 4) load_res(i + DEPTH, i % DEPTH);
                 }
-                { const unsigned long long t = estamp(); dbg_es += t - e_t; e_t = t; }
+                lap(3);
             }
         };
         if (RMODE == 0 && !C32 && !(p.flags & GEMM_F32_TRANSPOSE)) passes(std::integral_constant<bool, RMODE == 0>{});
         else passes(std::false_type{});
-        if (want_stats) {
+        if (colstats) {
             // fold the LPR row-lanes of every channel through the scratch (fixed order: reproducible)
             if (act) {
 #pragma unroll
@@ -599,41 +614,18 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
     if (DB) {
         // two LDS stages: tile kt+1 is in flight while tile kt feeds the MFMAs; one barrier per K tile
         stage(kt_begin, 0);
-        if (p.flags & 0x4000) {
-            // DIAGNOSTIC build path (never used by the engine): s_memtime stamps around the three parts of a K tile;
-            // the sums go to the colstats pointer as [workgroup][wave][4] floats and feed no output value.
-            auto stamp = [&]() {
-                unsigned long long t;
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-                __builtin_amdgcn_sched_barrier(0);
-                return t;
-            };
-            unsigned long long tw = 0, ts = 0, tc = 0;
-            const unsigned long long t_begin = stamp();
-            for (int kt = kt_begin; kt < nt; ++kt) {
-                const int cur = (kt - kt_begin) & 1;
-                const unsigned long long t0 = stamp();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                const unsigned long long t1 = stamp();
-                if (kt + 1 < nt) stage(kt + 1, cur ^ 1);
-                const unsigned long long t2 = stamp();
-                compute(cur);
-                const unsigned long long t3 = stamp();
-                tw += t1 - t0; ts += t2 - t1; tc += t3 - t2;
-            }
-            const unsigned long long t_end = stamp();
-            dbg_t1 = t_begin; dbg_t2 = t_end;
-            (void)tw; (void)ts; (void)tc;
-        } else
+        if constexpr (DIAG) dbg.t1 = stamp();
         for (int kt = kt_begin; kt < nt; ++kt) {
             const int cur = (kt - kt_begin) & 1;
+            stamp();      // (DIAG: the three parts of a K tile -- wait, stage, compute -- each start at a stamp, as they always have in the stamped loop)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
+            stamp();
             if (kt + 1 < nt) stage(kt + 1, cur ^ 1);
+            stamp();
             compute(cur);
         }
+        if constexpr (DIAG) dbg.t2 = stamp();
     } else {
         // one LDS stage, two barriers per K tile; latency is hidden by the other workgroups on the CU
         for (int kt = kt_begin; kt < nt; ++kt) {
@@ -663,23 +655,24 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
         return;
     }
 
-    if (DB && !(p.flags & GEMM_OUT_F32) && !(p.N & 7) && !(p.flags & GEMM_NARROW_EPILOGUE)) {
+    // (the stamped instantiation is planned for the wide epilogue only: dispatch.cpp)
+    if (DIAG || (DB && !(p.flags & GEMM_OUT_F32) && !(p.N & 7) && !(p.flags & GEMM_NARROW_EPILOGUE))) {
         __syncthreads();             // all waves are done with the last K tile: the stage buffers become scratch
         unsigned long long dbg_tb = 0;
-        if (p.flags & 0x4000) { __builtin_amdgcn_sched_barrier(0); dbg_tb = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+        if constexpr (DIAG) { __builtin_amdgcn_sched_barrier(0); dbg_tb = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
         run_wide(m0, n0, reinterpret_cast<float*>(smem_raw));
-        if (p.flags & 0x4000) {
+        if constexpr (DIAG) {
             __builtin_amdgcn_sched_barrier(0);
             const unsigned long long t3a = __builtin_amdgcn_s_memtime();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-            if (lane == 0 && p.colstats) {
-                float* d = p.colstats + ((long)blockIdx.x * 4 + wave) * 4;
+            if (lane == 0 && stamps_out) {
+                float* d = stamps_out + ((long)blockIdx.x * 4 + wave) * 4;
                 // [prologue, K loop, epilogue incl. the barrier before it and the drain of its stores, barrier wait alone]
-                d[0] = (float)(dbg_t1 - dbg_t0); d[1] = (float)(dbg_t2 - dbg_t1); d[2] = (float)(t3 - dbg_t2);
-                d[3] = (float)(dbg_tb - dbg_t2) + 65536.f * (float)((t3 - t3a) >> 4);   // (packed: barrier wait | store drain / 16)
-                float* e = p.colstats + ((long)gridDim.x * 4 + (long)blockIdx.x * 4 + wave) * 4;
-                e[0] = (float)dbg_e0; e[1] = (float)dbg_ew; e[2] = (float)dbg_er; e[3] = (float)dbg_es;   // epilogue: setup | LDS writes | LDS read wait | convert + store
+                d[0] = (float)(dbg.t1 - dbg.t0); d[1] = (float)(dbg.t2 - dbg.t1); d[2] = (float)(t3 - dbg.t2);
+                d[3] = (float)(dbg_tb - dbg.t2) + 65536.f * (float)((t3 - t3a) >> 4);   // (packed: barrier wait | store drain / 16)
+                float* e = stamps_out + ((long)gridDim.x * 4 + (long)blockIdx.x * 4 + wave) * 4;
+                e[0] = (float)dbg.epi[0]; e[1] = (float)dbg.epi[1]; e[2] = (float)dbg.epi[2]; e[3] = (float)dbg.epi[3];   // epilogue: setup | LDS writes | LDS read wait | convert + store
             }
         }
         return;
@@ -694,7 +687,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
     // optional per-channel (sum, sum of squares) of the STORED values over this wave's 64 rows: the GroupNorm that
     // consumes this tensor gets its statistics from the producer instead of re-reading the tensor (util.py:214-216)
     float* colstats = p.colstats;
-    const bool want_stats = colstats && !(p.flags & 0x4000);
     float cs[NT][4], cq[NT][4];
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -734,7 +726,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) o[r] = from_f32<E>(v[r]);
                     *reinterpret_cast<typename TT::v4*>(reinterpret_cast<E*>(p.C) + (long)m * p.ldc + nb) = o;
-                    if (want_stats) {
+                    if (colstats) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { const float f = to_f32(o[r]); cs[j][r] += f; cq[j][r] += f * f; }
                     }
@@ -772,16 +764,6 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(GemmParams p) {
                 *reinterpret_cast<typename TT::v4*>(reinterpret_cast<E*>(p.C) + (long)m * p.ldc + oc) = o;
             }
         }
-    }
-    if (p.flags & 0x4000) {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-        if (lane == 0 && colstats) {
-            float* d = colstats + ((long)blockIdx.x * 4 + wave) * 4;
-            d[0] = (float)(dbg_t1 - dbg_t0); d[1] = (float)(dbg_t2 - dbg_t1); d[2] = (float)(t3 - dbg_t2); d[3] = 0.f;
-        }
-        return;
     }
     if (colstats && !geglu && !out32) {
         // fold the 16 rows-lanes of each column with DPP adds (quad_perm xor 1, xor 2, then row_ror 4, 8): no LDS
@@ -893,8 +875,12 @@ int launch_one(const VfGemmPlan& pl, hipStream_t stream) {
     int which = 0;
     if constexpr (DB && MODE != MODE_CONV_GENERIC) {
         if (pl.persistent) { which = 1; kern = gemm_kernel<TT, MODE, NT, DB, DB, 0>; }
+        else if (pl.form == 3) {      // cycle stamps (tools/stamp_gemm.py): built for the fp16 plain GEMM only
+            if constexpr (MODE == MODE_PLAIN && std::is_same<TT, F16>::value) { which = 2; kern = gemm_kernel<TT, MODE, NT, DB, false, 0, true>; }
+        }
         else { which = 3 + pl.form; kern = pl.form == 2 ? gemm_kernel<TT, MODE, NT, DB, false, 2> : pl.form == 1 ? gemm_kernel<TT, MODE, NT, DB, false, 1> : gemm_kernel<TT, MODE, NT, DB, false, 0>; }
-    } else kern = gemm_kernel<TT, MODE, NT, DB, false>;
+    } else if (pl.form != 3) kern = gemm_kernel<TT, MODE, NT, DB, false>;
+    if (!kern) return VF_ERR_SHAPE;      // (a stamped launch of a form without stamps.  dispatch.cpp plans the plain two-stage form only; it does not see the element type)
     static VfOncePerDevice attr_set[6];
     if (pl.lds_bytes > 64 * 1024 && !attr_set[which].set_lds(reinterpret_cast<const void*>(kern), pl.lds_bytes)) return VF_ERR_LAUNCH;
     hipLaunchKernelGGL(kern, dim3(pl.grid_x), dim3(256), pl.lds_bytes, stream, pl.p);

@@ -20,6 +20,9 @@ LIB_PATH = os.environ.get("VFACE_HIP_LIB") or os.path.join(_HERE, "lib", "libvfa
 F16, BF16 = 0, 1
 EPI_GEGLU, EPI_OUT_F32 = 1, 2
 CONV_PAD_TRAILING = 0x40000  # conv3x3: zero padding (0,1,0,1) (the VAE encoder's Downsample)
+TUNE_NO_XCD_REMAP, TUNE_NO_SETPRIO = 0x1000, 0x2000  # A/B: gemm tiles in launch order / no raised wave priority around the MFMAs (conv.hip: split load issue)
+TUNE_STAMPS = 0x4000  # diagnostic: the stamped instantiation; `colstats` receives cycle counts (tools/stamp_gemm.py, tools/stamp_conv.py)
+TUNE_NARROW_EPILOGUE = 0x8000  # A/B: gemm.hip stores from the accumulator layout, no LDS transpose
 TUNE_NO_PATCH, TUNE_PATCH = 0x80000, 0x100000  # conv3x3*: never / always (where the shape allows) the patch-staged kernel
 TUNE_GN8 = 0x8000000  # A/B: fixed 8-wide column groups in the plain GEMM's tile order
 TUNE_NO_Q8 = 0x4000000  # A/B: the 8x8 level stays on the im2col kernel
