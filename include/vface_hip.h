@@ -372,7 +372,7 @@ int vface_yuv420_to_rgb(const uint8_t* i420, int64_t frame_stride, int W, int H,
  * The reference hands the target video to cv2.VideoCapture (:240-285).  Of the codecs that decodes, baseline JPEG is built here:
  * vface_amd/scripts/mjpeg_in.py walks an AVI with an MJPG stream and parses each frame's headers on the host (8-bit, three
  * components, Y 2 x 2, Cb and Cr 1 x 1, one scan), the SCANS cross to the device -- about a tenth of the I420 bytes at quality 90 --
- * and these three entry points turn them into the I420 rows vface_yuv420_to_rgb reads (matrix 1, full_range 1, chroma 1: JFIF).
+ * and these entry points turn them into the I420 rows vface_yuv420_to_rgb reads (matrix 1, full_range 1, chroma 1: JFIF).
  * csrc/mjpeg_in.hip; the interval decoder is csrc/jpeg_interval.hpp, which a host program runs under sanitizers.
  *
  * Common to the three: `mcus` = mcu_rows * mcu_cols per frame, the same for every frame of a call; restart [frames] = the DRI
@@ -400,6 +400,22 @@ int vface_yuv420_to_rgb(const uint8_t* i420, int64_t frame_stride, int W, int H,
  *   NULL pointer, mcus, frames, max_intervals or scan_bytes <= 0: VFACE_ERR_ARG; scan_bytes >= 2^31, max_intervals > mcus,
  *   frame_stride < mcus * 384: VFACE_ERR_SHAPE; tables off 4 bytes: VFACE_ERR_ALIGN.
  *
+ * vface_jpeg_decode_entropy_parallel: vface_jpeg_decode_entropy's arguments, its output and its statuses -- the same for every input,
+ *   valid or corrupt -- from many lanes per restart interval, for scans without restart markers (one interval per frame, which the
+ *   call above gives ONE lane).  An interval is cut into subsequences of subseq_bytes raw scan bytes; one workgroup per (frame,
+ *   interval) walks them in chunks of 64 or 256 (chosen on the host from scan_bytes / (frames * max_intervals) / subseq_bytes),
+ *   decodes every subsequence of a chunk from a guessed state (its first bit, first block of an MCU, DC symbol next) and repeats, each
+ *   lane taking its left neighbour's exit state, until a round changes nothing: at most one round per lane, whatever the bytes are.
+ *   A prefix sum of the blocks begun places every lane's coefficients; DC values are a prefix sum of the differences per component.
+ *   A frame in which the serial routine would report anything (3..8) is cleared and decoded again by that routine in the last launch
+ *   of the call, on a device flag: status and partial output of a bad frame are vface_jpeg_decode_entropy's by construction.  The
+ *   per-subsequence routine is csrc/jpeg_subseq.hpp, which a host program runs under sanitizers; the same promise holds for reads
+ *   and writes.  workspace: vface_jpeg_decode_entropy_parallel_workspace_bytes(frames) bytes, 4-byte aligned.  rounds: NULL, or
+ *   [frames][max_intervals] int32 = the rounds that changed a state, summed over an interval's chunks; 0 for a frame or interval
+ *   that was not decoded.
+ *   The refusals of vface_jpeg_decode_entropy, and: NULL workspace: VFACE_ERR_ARG; subseq_bytes outside 4..1024 or no multiple of 4,
+ *   workspace_bytes too small: VFACE_ERR_SHAPE; workspace off 4 bytes: VFACE_ERR_ALIGN.
+ *
  * vface_jpeg_planes: coefficient frames as above (frame f at coef + f * coef_stride) and quant [frames][3][64], the quantisation
  *   table of Y, Cb, Cr of every frame, row-major -> out: one I420 frame per frame, frame f at out + f * row_stride: Y [H][W], Cb
  *   [ch][cw], Cr [ch][cw], cw = (W + 1) / 2, ch = (H + 1) / 2, cropped out of the whole MCUs.  Dequantisation, an integer 8 x 8
@@ -414,6 +430,11 @@ int vface_jpeg_scan_index(const uint8_t* scans, int64_t scan_bytes, const int64_
 int vface_jpeg_decode_entropy(const uint8_t* scans, int64_t scan_bytes, const int32_t* ranges, const int32_t* restart,
                               const uint8_t* tables, int mcus, int frames, int max_intervals, int16_t* out, int64_t frame_stride,
                               int32_t* status, void* stream);
+size_t vface_jpeg_decode_entropy_parallel_workspace_bytes(int frames);
+int vface_jpeg_decode_entropy_parallel(const uint8_t* scans, int64_t scan_bytes, const int32_t* ranges, const int32_t* restart,
+                                       const uint8_t* tables, int mcus, int frames, int max_intervals, int16_t* out,
+                                       int64_t frame_stride, int32_t* status, int subseq_bytes, void* workspace,
+                                       size_t workspace_bytes, int32_t* rounds, void* stream);
 int vface_jpeg_planes(const int16_t* coef, int64_t coef_stride, const uint8_t* quant, int W, int H, int frames, uint8_t* out,
                       int64_t row_stride, void* stream);
 

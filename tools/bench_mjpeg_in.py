@@ -2,15 +2,20 @@
 conversion behind them, the upload they need, the Y4M ``video_in`` stage (upload + convert) on the same frames in the same run, and
 Pillow's (libjpeg-turbo's) decode of the same files on the host.
 
-    python tools/bench_mjpeg_in.py [--calls 10] [--quality 90]
+    python tools/bench_mjpeg_in.py [--calls 10] [--quality 90] [--subseq_bytes 128 [64 256 ..]] [--cases NAME ..]
 
-Three cases, one JSON line each:
+Five cases, one JSON line each:
   writer_1080p   32 frames of 1920 x 1080 as ``MJPEGWriter`` writes them: one restart interval per MCU row, so 68 lanes per frame
-  pillow_1080p   the same frames as Pillow writes them: NO restart markers (what ffmpeg writes too), so ONE lane per frame
+  pillow_1080p   the same frames as Pillow writes them: NO restart markers (what ffmpeg writes too), so ONE interval per frame
   writer_512     8 frames of 512 x 512 from the writer
-The frames are smooth seeded pictures (sinusoids, a ramp, sigma = 4 noise): noise alone would not compress.  Each launch is timed
-between two HIP events, ``--calls`` samples after a warm-up, alternating so that a busy moment on a shared machine falls on all of
-them; medians, minima and maxima are reported.  Host-to-device copies come from pinned buffers."""
+  pillow_1080p_flat        32 flat frames from Pillow: the stream on which guessed states never fall into step with the true ones
+  pillow_1080p_noise_q100  8 frames of uniform noise from Pillow at quality 100: long codes, late synchronisation
+The frames of the first three are smooth seeded pictures (sinusoids, a ramp, sigma = 4 noise): noise alone would not compress.
+``decode_entropy`` is timed in BOTH forms in the same run -- ``hip.jpeg_decode_entropy`` (one lane per restart interval) and
+``hip.jpeg_decode_entropy_parallel`` at every ``--subseq_bytes`` -- and the two results are compared bit for bit before anything is
+timed; ``rounds`` (synchronisation rounds that changed a state, summed over the call) and the subsequence count stand beside each
+parallel time.  Each launch is timed between two HIP events, ``--calls`` samples after a warm-up, alternating so that a busy moment
+on a shared machine falls on all of them; medians, minima and maxima are reported.  Host-to-device copies come from pinned buffers."""
 import argparse
 import io
 import json
@@ -27,7 +32,8 @@ from vface_amd import hip  # noqa: E402
 from vface_amd.scripts import mjpeg, mjpeg_in  # noqa: E402
 
 DEV = torch.device("cuda", 0)
-CASES = (("writer_1080p", 32, 1920, 1080, "writer"), ("pillow_1080p", 32, 1920, 1080, "pillow"), ("writer_512", 8, 512, 512, "writer"))
+CASES = (("writer_1080p", 32, 1920, 1080, "writer"), ("pillow_1080p", 32, 1920, 1080, "pillow"), ("writer_512", 8, 512, 512, "writer"),
+         ("pillow_1080p_flat", 32, 1920, 1080, "pillow_flat"), ("pillow_1080p_noise_q100", 8, 1920, 1080, "pillow_noise"))
 
 
 def pictures(frames, W, H):
@@ -48,8 +54,14 @@ def timed(fn):
     return a.elapsed_time(b), out
 
 
-def measure(name, frames, W, H, source, calls, quality):
-    rgb = pictures(frames, W, H)
+def measure(name, frames, W, H, source, calls, quality, sizes):
+    if source == "pillow_flat":
+        rgb = torch.tensor([90, 140, 200], dtype=torch.uint8, device=DEV).expand(frames, H, W, 3).contiguous()
+    elif source == "pillow_noise":
+        rgb = torch.randint(0, 256, (frames, H, W, 3), dtype=torch.uint8, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1))
+        quality = 100
+    else:
+        rgb = pictures(frames, W, H)
     host = rgb.cpu().numpy()
     if source == "writer":
         with tempfile.TemporaryDirectory() as tmp:
@@ -84,6 +96,12 @@ def measure(name, frames, W, H, source, calls, quality):
     def entropy():
         state["coef"], _ = hip.jpeg_decode_entropy(dev["scans"], state["ranges"], state["status"], dev["restart"], dev["tables"], mcus)
 
+    def entropy_parallel(size):
+        def run():
+            state["coef_parallel"], _ = hip.jpeg_decode_entropy_parallel(dev["scans"], state["ranges"], state["status"], dev["restart"],
+                                                                         dev["tables"], mcus, size)
+        return run
+
     def planes():
         state["rows"] = hip.jpeg_planes(state["coef"], dev["quant"], W, H)
 
@@ -99,6 +117,14 @@ def measure(name, frames, W, H, source, calls, quality):
         fn()
     torch.cuda.synchronize()
     assert state["status"].cpu().tolist() == [0] * frames, state["status"].cpu().tolist()
+    # the parallel form: the same coefficients, its round counts, then a step of its own per subsequence size
+    rounds = {}
+    for size in sizes:
+        coef, status, r = hip.jpeg_decode_entropy_parallel(dev["scans"], state["ranges"], state["status"], dev["restart"], dev["tables"], mcus,
+                                                           size, return_rounds=True)
+        assert torch.equal(coef, state["coef"]) and status.cpu().tolist() == [0] * frames, (name, size)
+        rounds[size] = int(r.sum())
+        steps[f"decode_entropy_parallel_{size}"] = entropy_parallel(size)
     i420_host = state["rows"].cpu().pin_memory()
     i420_dev = torch.empty_like(state["rows"])
     y4m_rgb = torch.empty_like(state["rgb"])
@@ -126,6 +152,14 @@ def measure(name, frames, W, H, source, calls, quality):
            "pillow_cpu_decode_ms_median": statistics.median(pillow), "pillow_cpu_decode_ms_min": min(pillow)}
     for k, v in ms.items():
         rec[k + "_ms_median"], rec[k + "_ms_min"], rec[k + "_ms_max"] = statistics.median(v), min(v), max(v)
+    rec["subseq_bytes"] = list(sizes)
+    for size in sizes:
+        rec[f"rounds_{size}"] = rounds[size]
+        # (about: every frame's bytes spread evenly over its intervals)
+        rec[f"subsequences_{size}"] = sum((len(r.scan) // hip.jpeg_interval_count(mcus, r.restart) // size + 1)
+                                          * hip.jpeg_interval_count(mcus, r.restart) for r in read.records)
+    rec["entropy_auto"] = mjpeg_in.entropy_path(read, mcus)
+    rec["longest_interval_bytes"] = max(len(r.scan) / hip.jpeg_interval_count(mcus, r.restart) for r in read.records)
     rec["decoder_ms_median"] = sum(rec[k + "_ms_median"] for k in ("scan_index", "decode_entropy", "planes", "yuv420_to_rgb"))
     rec["video_in_ms_median"] = rec["decoder_ms_median"] + rec["h2d_scans_and_tables_ms_median"]
     return rec
@@ -135,11 +169,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--quality", type=int, default=90)
+    ap.add_argument("--subseq_bytes", type=int, nargs="+", default=[mjpeg_in.SUBSEQ_BYTES],
+                    help="subsequence sizes of the parallel entropy decoder to time (multiples of 4 in 4..1024): a sweep")
+    ap.add_argument("--cases", nargs="+", default=[c[0] for c in CASES], choices=[c[0] for c in CASES])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("An MI355X is required: there is nothing to time without one.")
     for name, frames, W, H, source in CASES:
-        print(json.dumps(measure(name, frames, W, H, source, a.calls, a.quality)), flush=True)
+        if name in a.cases:
+            print(json.dumps(measure(name, frames, W, H, source, a.calls, a.quality, a.subseq_bytes)), flush=True)
 
 
 if __name__ == "__main__":

@@ -2,10 +2,12 @@
 // host): the scans of baseline 4:2:0 JPEG frames, as vface_amd/scripts/mjpeg_in.py cuts them out of an AVI, -> the I420 rows that
 // vface_yuv420_to_rgb (csrc/demux.hip) turns into RGB frames.  The host parses headers only; the compressed bytes cross to the device.
 //
-// Three entry points, each beside its kernels -- the mirror image of csrc/mjpeg.hip:
+// Four entry points, each beside its kernels -- the mirror image of csrc/mjpeg.hip:
 //   vface_jpeg_scan_index      finds the RSTm markers of every frame's scan: the byte range of every restart interval
 //   vface_jpeg_decode_entropy  Huffman decoding with the frame's own tables, one lane per interval -> the coefficient layout that
 //                              vface_jpeg_coefficients writes (vface_jpeg_entropy followed by this is the identity)
+//   vface_jpeg_decode_entropy_parallel  the same output from many lanes per interval: fixed-size subsequences decoded from guessed
+//                              states and stitched by self-synchronisation (csrc/jpeg_subseq.hpp), for scans without restart markers
 //   vface_jpeg_planes          dequantisation, 8 x 8 inverse DCT, level shift, clamp, crop -> I420 rows
 //
 // The interval decoder is csrc/jpeg_interval.hpp, shared with a host program that runs it under sanitizers: the bytes of a file
@@ -21,6 +23,7 @@
 // for every int16 coefficient and every Q (jpeg_decode_model.value_ranges).
 #include "common.hpp"
 #include "jpeg_interval.hpp"
+#include "jpeg_subseq.hpp"
 #include "launch.hpp"
 #include "vface_kernels.hpp"
 
@@ -154,17 +157,20 @@ __global__ __launch_bounds__(256) void jpeg_clear_kernel(short* __restrict__ out
 // interval 64 c + l with the shared routine.  Frames that vface_jpeg_scan_index refused are left cleared.  A range that does not
 // lie inside the scan buffer (the ranges are device data) is refused as VF_JPEG_SHORT before a byte is read.  The frame's status
 // is the largest of its intervals' codes.
+// With `flags` (the last launch of vface_jpeg_decode_entropy_parallel; nullptr otherwise): only frames whose flag is set are decoded,
+// and the workgroup clears the MCUs of its 64 intervals first.
 __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(const unsigned char* __restrict__ scans, long scan_bytes,
                                                                  const int* __restrict__ ranges, const int* __restrict__ restart,
                                                                  const unsigned char* __restrict__ tables, int mcus, int frames,
                                                                  int max_intervals, int chunks, short* __restrict__ out,
-                                                                 long frame_stride, int* status) {
+                                                                 long frame_stride, int* status, const int* __restrict__ flags) {
     __shared__ VfJpegTables tab;
     static_assert(sizeof(VfJpegTables) == 2304 && sizeof(VfJpegTables) % 4 == 0, "the table block of scripts/mjpeg_in.py");
     const int lane = threadIdx.x;
     const long items = (long)frames * chunks;
     for (long it = blockIdx.x; it < items; it += gridDim.x) {
         const int f = (int)(it / chunks), c = (int)(it - (long)f * chunks);
+        if (flags && !flags[f]) continue;
         __syncthreads();
         const unsigned* src = (const unsigned*)(tables + (long)f * sizeof(VfJpegTables));
         for (int i = lane; i < (int)(sizeof(VfJpegTables) / 4); i += 64) ((unsigned*)&tab)[i] = src[i];
@@ -172,6 +178,12 @@ __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(const unsigned 
         const int r = restart[f];
         const int step = r <= 0 || r >= mcus ? mcus : r;
         const int n = min(interval_count(mcus, r), max_intervals);
+        if (flags) {
+            const long lo = min((long)c * 64 * step, (long)mcus) * kMcuCoefs, hi = min(((long)c * 64 + 64) * step, (long)mcus) * kMcuCoefs;
+            if (c * 64 < n)
+                for (long e = lo + lane; e < hi; e += 64) out[f * frame_stride + e] = 0;
+            __syncthreads();
+        }
         const int i = c * 64 + lane;
         if (i >= n || status[f] == VF_JPEG_MARKER_COUNT || status[f] == VF_JPEG_MARKER_ORDER) continue;
         const int m0 = i * step, m1 = min(m0 + step, mcus);
@@ -198,9 +210,196 @@ extern "C" int vface_jpeg_decode_entropy(const uint8_t* scans, int64_t scan_byte
     hipLaunchKernelGGL(jpeg_clear_kernel, dim3(vf_grid(total, 256 * 8, 4096)), dim3(256), 0, stream, (short*)out, (long)frame_stride,
                        per_frame, total);
     const int chunks = (max_intervals + 63) / 64;
+    hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3(vf_grid((long)frames * chunks, 1, kDecodeGridCap)), dim3(64), 0, stream,
+                       scans, (long)scan_bytes, ranges, restart, tables, mcus, frames, max_intervals, chunks, (short*)out,
+                       (long)frame_stride, status, (const int*)nullptr);
+    return vf_launched();
+}
+
+// ---- entropy decoding, many lanes per interval -----------------------------------------------------------------------------------
+namespace {
+
+constexpr int kParallelGridCap = 4096;    // workgroups (one (frame, interval) each) before the grid loops
+
+__global__ __launch_bounds__(256) void jpeg_flags_clear_kernel(int* __restrict__ flags, int frames) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < frames; i += gridDim.x * 256) flags[i] = 0;
+}
+
+// exclusive prefix sum of x over the L lanes of the workgroup, and the sum of all; wsum: L / 64 words of LDS
+template <int L>
+__device__ inline int group_exclusive_scan(int x, int* wsum, int& all) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int incl = wave_inclusive_scan(x, lane);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    all = 0;
+#pragma unroll
+    for (int w = 0; w < L / 64; ++w) {
+        if (w < wave) before += wsum[w];
+        all += wsum[w];
+    }
+    __syncthreads();
+    return before + incl - x;
+}
+
+// One workgroup of L lanes per (frame, interval); csrc/jpeg_subseq.hpp states the subsequences, the state and the routine.
+//   The interval is walked in chunks of L subsequences.  Lane 0 of a chunk starts from the verified exit state of the chunk before
+//   (the interval's first bit, slot 0, k 0 for chunk 0), every other lane from its guess.  Then rounds: lane i >= 1 compares lane
+//   i - 1's exit state with the start state it used last and decodes again only where they differ; the chunk is done when a round
+//   changes nothing -- after at most L - 1 rounds that change something, since lane j is exact after j rounds whatever the bytes
+//   are.  rounds [frames][max_intervals] counts the rounds that changed something, summed over the chunks.
+//   Write pass: a prefix sum of the blocks the lanes began gives every lane its first block; it decodes once more from its
+//   verified start state and writes AC coefficients and DC differences.  DC pass: per component an inclusive scan of the
+//   differences over the interval's MCUs (int32 arithmetic, wrap-around not undefined: the first sum that leaves int16 is seen).
+//   Anything the serial routine would report -- met by a lane that holds a block below `blocks`, too few blocks begun, a DC sum
+//   outside int16, a range outside the buffer -- sets flags[f]; the launch behind this one decodes such a frame serially.
+template <int L>
+__global__ __launch_bounds__(L) void jpeg_decode_parallel_kernel(const unsigned char* __restrict__ scans, long scan_bytes,
+                                                                 const int* __restrict__ ranges, const int* __restrict__ restart,
+                                                                 const unsigned char* __restrict__ tables, int mcus, int frames,
+                                                                 int max_intervals, int subseq_bytes, short* __restrict__ out,
+                                                                 long frame_stride, const int* __restrict__ status,
+                                                                 int* __restrict__ flags, int* __restrict__ rounds) {
+    __shared__ VfJpegTables tab;
+    __shared__ VfJpegSubState exits[L];
+    __shared__ int wsum[L / 64];
+    const int tid = threadIdx.x;
+    const long items = (long)frames * max_intervals;
+    for (long it = blockIdx.x; it < items; it += gridDim.x) {
+        const int f = (int)(it / max_intervals), i = (int)(it - (long)f * max_intervals);
+        const int r = restart[f];
+        const int step = r <= 0 || r >= mcus ? mcus : r;
+        const int n = min(interval_count(mcus, r), max_intervals);
+        const int refused = status[f];
+        const int m0 = min((long)i * step, (long)mcus), m1 = min(m0 + step, mcus);
+        const long begin = ranges[it * 2], end = ranges[it * 2 + 1];
+        const bool inside = m0 < m1 && begin >= 0 && begin <= end && end <= scan_bytes;
+        if (i >= n || refused == VF_JPEG_MARKER_COUNT || refused == VF_JPEG_MARKER_ORDER || !inside) {       // (the same for every lane)
+            if (tid == 0) {
+                if (rounds) rounds[it] = 0;
+                if (i < n && refused != VF_JPEG_MARKER_COUNT && refused != VF_JPEG_MARKER_ORDER) flags[f] = 1;
+            }
+            continue;
+        }
+        __syncthreads();
+        const unsigned* src = (const unsigned*)(tables + (long)f * sizeof(VfJpegTables));
+        for (int w = tid; w < (int)(sizeof(VfJpegTables) / 4); w += L) ((unsigned*)&tab)[w] = src[w];
+        __syncthreads();
+        const int blocks = (m1 - m0) * 6, max_steps = 8 * subseq_bytes;
+        short* o = out + f * frame_stride + (long)m0 * kMcuCoefs;
+        const long nsub = vf_jpeg_subseq_count(end - begin, subseq_bytes);
+        VfJpegSubState carry = {(int32_t)begin, 0};
+        long blocks_before = 0;
+        int ran = 0;
+        bool fault = false;
+        for (long c0 = 0; c0 < nsub; c0 += L) {
+            const bool live = c0 + tid < nsub;
+            const long sub_begin = begin + (c0 + tid) * subseq_bytes, sub_end = sub_begin + subseq_bytes;
+            VfJpegSubState start = carry, reached = carry;
+            int begun = 0;
+            if (live) {
+                if (tid > 0) start = vf_jpeg_subseq_guess(scans, begin, end, sub_begin);
+                reached = start;
+                vf_jpeg_decode_subseq(scans, begin, end, sub_end, max_steps, &tab, reached, begun, 0, 0, nullptr);
+            }
+            exits[tid] = reached;
+            for (int round = 0; round < L; ++round) {
+                __syncthreads();
+                VfJpegSubState want = start;
+                if (live && tid > 0) want = exits[tid - 1];
+                const bool changed = !vf_jpeg_sub_same(want, start);
+                if (!__syncthreads_or(changed ? 1 : 0)) break;          // (a barrier: every exit state has been read)
+                ++ran;
+                if (changed) {
+                    start = reached = want;
+                    vf_jpeg_decode_subseq(scans, begin, end, sub_end, max_steps, &tab, reached, begun, 0, 0, nullptr);
+                    exits[tid] = reached;
+                }
+            }
+            __syncthreads();
+            carry = exits[L - 1];
+            int all;
+            const int first = group_exclusive_scan<L>(live ? begun : 0, wsum, all);
+            if (live) {
+                int again;
+                VfJpegSubState from = start;
+                if (vf_jpeg_decode_subseq(scans, begin, end, sub_end, max_steps, &tab, from, again, blocks_before + first, blocks, o) != VF_JPEG_OK)
+                    fault = true;
+            }
+            blocks_before += all;
+        }
+        if (blocks_before < blocks) fault = true;
+        __syncthreads();                                                // the differences are in memory for every lane
+        unsigned before[3] = {0u, 0u, 0u};
+        for (int mb = 0; mb < m1 - m0; mb += L) {
+            const int m = mb + tid;
+            short* p = o + (long)m * kMcuCoefs;
+            unsigned y[4] = {0u, 0u, 0u, 0u}, cb = 0u, cr = 0u;
+            if (m < m1 - m0) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) y[q] = (unsigned)(int)p[q * 64] + (q ? y[q - 1] : 0u);
+                cb = (unsigned)(int)p[4 * 64];
+                cr = (unsigned)(int)p[5 * 64];
+            }
+            int all_y, all_cb, all_cr;
+            const unsigned by = before[0] + (unsigned)group_exclusive_scan<L>((int)y[3], wsum, all_y);
+            const unsigned bcb = before[1] + (unsigned)group_exclusive_scan<L>((int)cb, wsum, all_cb);
+            const unsigned bcr = before[2] + (unsigned)group_exclusive_scan<L>((int)cr, wsum, all_cr);
+            if (m < m1 - m0) {
+                const int v[6] = {(int)(by + y[0]), (int)(by + y[1]), (int)(by + y[2]), (int)(by + y[3]), (int)(bcb + cb), (int)(bcr + cr)};
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    if (v[q] < -32768 || v[q] > 32767) fault = true;
+                    p[q * 64] = (short)v[q];
+                }
+            }
+            before[0] += (unsigned)all_y;
+            before[1] += (unsigned)all_cb;
+            before[2] += (unsigned)all_cr;
+        }
+        if (fault) flags[f] = 1;
+        if (rounds && tid == 0) rounds[it] = ran;
+    }
+}
+
+}  // namespace
+
+extern "C" size_t vface_jpeg_decode_entropy_parallel_workspace_bytes(int frames) {
+    return frames > 0 ? (size_t)frames * sizeof(int) : 0;
+}
+
+extern "C" int vface_jpeg_decode_entropy_parallel(const uint8_t* scans, int64_t scan_bytes, const int32_t* ranges,
+                                                  const int32_t* restart, const uint8_t* tables, int mcus, int frames,
+                                                  int max_intervals, int16_t* out, int64_t frame_stride, int32_t* status,
+                                                  int subseq_bytes, void* workspace, size_t workspace_bytes, int32_t* rounds,
+                                                  void* stream_) {
+    hipStream_t stream = vf_stream(stream_);
+    if (!scans || !ranges || !restart || !tables || !out || !status || !workspace || mcus <= 0 || frames <= 0 || max_intervals <= 0 ||
+        scan_bytes <= 0)
+        return VF_ERR_ARG;
+    if (scan_bytes > 0x7FFFFFFFL || max_intervals > mcus || frame_stride < (long)mcus * kMcuCoefs) return VF_ERR_SHAPE;
+    if (subseq_bytes < kVfJpegSubseqMin || subseq_bytes > kVfJpegSubseqMax || subseq_bytes % 4 != 0) return VF_ERR_SHAPE;
+    if (workspace_bytes < vface_jpeg_decode_entropy_parallel_workspace_bytes(frames)) return VF_ERR_SHAPE;
+    if (((size_t)tables & 3) != 0 || ((size_t)workspace & 3) != 0) return VF_ERR_ALIGN;
+    int* flags = (int*)workspace;
+    const long per_frame = (long)mcus * kMcuCoefs, total = per_frame * frames;
+    hipLaunchKernelGGL(jpeg_clear_kernel, dim3(vf_grid(total, 256 * 8, 4096)), dim3(256), 0, stream, (short*)out, (long)frame_stride,
+                       per_frame, total);
+    hipLaunchKernelGGL(jpeg_flags_clear_kernel, dim3(vf_grid(frames, 256, 64)), dim3(256), 0, stream, flags, frames);
+    const dim3 grid(vf_grid((long)frames * max_intervals, 1, kParallelGridCap));
+    if (vf_jpeg_subseq_lanes((long)scan_bytes, frames, max_intervals, subseq_bytes) == kVfJpegLanesLong)
+        hipLaunchKernelGGL(jpeg_decode_parallel_kernel<kVfJpegLanesLong>, grid, dim3(kVfJpegLanesLong), 0, stream, scans, (long)scan_bytes,
+                           ranges, restart, tables, mcus, frames, max_intervals, subseq_bytes, (short*)out, (long)frame_stride,
+                           (const int*)status, flags, rounds);
+    else
+        hipLaunchKernelGGL(jpeg_decode_parallel_kernel<kVfJpegLanesShort>, grid, dim3(kVfJpegLanesShort), 0, stream, scans, (long)scan_bytes,
+                           ranges, restart, tables, mcus, frames, max_intervals, subseq_bytes, (short*)out, (long)frame_stride,
+                           (const int*)status, flags, rounds);
+    const int chunks = (max_intervals + 63) / 64;
     hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3(vf_grid((long)frames * chunks, 1, kDecodeGridCap)), dim3(64), 0, stream, scans,
                        (long)scan_bytes, ranges, restart, tables, mcus, frames, max_intervals, chunks, (short*)out, (long)frame_stride,
-                       status);
+                       status, (const int*)flags);
     return vf_launched();
 }
 

@@ -92,6 +92,8 @@ SIGNATURES = {
     "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_jpeg_scan_index": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_jpeg_decode_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
+    "vface_jpeg_decode_entropy_parallel_workspace_bytes": (_sz, [_i32]),
+    "vface_jpeg_decode_entropy_parallel": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp, _sz, _vp, _vp]),
     "vface_jpeg_planes": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp]),
     "vface_quad_crop": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
     "vface_dataset_tensors": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
@@ -719,6 +721,29 @@ def jpeg_scan_index(scans: torch.Tensor, offsets: torch.Tensor, lengths: torch.T
     return out, status
 
 
+def _jpeg_decode_args(what, scans, ranges, status, restart, tables, mcus, out):
+    """The checks ``jpeg_decode_entropy`` and ``jpeg_decode_entropy_parallel`` share -> (F, mcus, max_intervals, out, frame stride)."""
+    if not isinstance(ranges, torch.Tensor) or ranges.dim() != 3:
+        raise VFaceHipError(f"{what}: ranges must be int32 [F, max_intervals, 2]")
+    F_, mcus, max_intervals = _jpeg_in_frames(what, scans, restart, mcus, ranges.shape[1])
+    if ranges.dtype != torch.int32 or tuple(ranges.shape) != (F_, max_intervals, 2) or not ranges.is_contiguous() or ranges.device != scans.device:
+        raise VFaceHipError(f"{what}: ranges must be a contiguous int32 {[F_, max_intervals, 2]} tensor on the scans' device")
+    if (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (F_,) or not status.is_contiguous()
+            or status.device != scans.device):
+        raise VFaceHipError(f"{what}: status must be a contiguous int32 [{F_}] tensor on the scans' device")
+    if (not isinstance(tables, torch.Tensor) or tables.dtype != torch.uint8 or tuple(tables.shape) != (F_, JPEG_TABLE_BYTES)
+            or not tables.is_contiguous() or tables.device != scans.device):
+        raise VFaceHipError(f"{what}: tables must be a contiguous uint8 {[F_, JPEG_TABLE_BYTES]} tensor on the scans' device")
+    shape, n = (F_, mcus, 6, 64), mcus * JPEG_MCU_COEFS
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=scans.device)
+    elif (out.dtype != torch.int16 or tuple(out.shape) != shape or not out[0].is_contiguous() or (F_ > 1 and out.stride(0) < n)
+          or out.device != scans.device):
+        raise VFaceHipError(f"{what}: out must be an int16 {list(shape)} view on the scans' device, frames contiguous, "
+                            f"frame stride >= {n}")
+    return F_, mcus, max_intervals, out, out.stride(0) if F_ > 1 else max(out.stride(0), n)
+
+
 def jpeg_decode_entropy(scans: torch.Tensor, ranges: torch.Tensor, status: torch.Tensor, restart: torch.Tensor,
                         tables: torch.Tensor, mcus: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``ranges`` and ``status`` of ``jpeg_scan_index`` -> ``(coefficients, status)``: int16 [F, mcus, 6, 64], the layout
@@ -728,28 +753,49 @@ def jpeg_decode_entropy(scans: torch.Tensor, ranges: torch.Tensor, status: torch
     interval with the routine of csrc/jpeg_interval.hpp: no byte outside an interval is read and no element outside its MCUs is
     written, whatever the bytes are.  Every frame is cleared first; a refused frame stays zero.  ``out``: an int16 view
     [F, mcus, 6, 64] with contiguous frames, frame stride at least one frame; elements between frames are not written."""
-    if not isinstance(ranges, torch.Tensor) or ranges.dim() != 3:
-        raise VFaceHipError("jpeg_decode_entropy: ranges must be int32 [F, max_intervals, 2]")
-    F_, mcus, max_intervals = _jpeg_in_frames("jpeg_decode_entropy", scans, restart, mcus, ranges.shape[1])
-    if ranges.dtype != torch.int32 or tuple(ranges.shape) != (F_, max_intervals, 2) or not ranges.is_contiguous() or ranges.device != scans.device:
-        raise VFaceHipError(f"jpeg_decode_entropy: ranges must be a contiguous int32 {[F_, max_intervals, 2]} tensor on the scans' device")
-    if (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or tuple(status.shape) != (F_,) or not status.is_contiguous()
-            or status.device != scans.device):
-        raise VFaceHipError(f"jpeg_decode_entropy: status must be a contiguous int32 [{F_}] tensor on the scans' device")
-    if (not isinstance(tables, torch.Tensor) or tables.dtype != torch.uint8 or tuple(tables.shape) != (F_, JPEG_TABLE_BYTES)
-            or not tables.is_contiguous() or tables.device != scans.device):
-        raise VFaceHipError(f"jpeg_decode_entropy: tables must be a contiguous uint8 {[F_, JPEG_TABLE_BYTES]} tensor on the scans' device")
-    shape, n = (F_, mcus, 6, 64), mcus * JPEG_MCU_COEFS
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int16, device=scans.device)
-    elif (out.dtype != torch.int16 or tuple(out.shape) != shape or not out[0].is_contiguous() or (F_ > 1 and out.stride(0) < n)
-          or out.device != scans.device):
-        raise VFaceHipError(f"jpeg_decode_entropy: out must be an int16 {list(shape)} view on the scans' device, frames contiguous, "
-                            f"frame stride >= {n}")
-    stride = out.stride(0) if F_ > 1 else max(out.stride(0), n)
+    F_, mcus, max_intervals, out, stride = _jpeg_decode_args("jpeg_decode_entropy", scans, ranges, status, restart, tables, mcus, out)
     _check(load().vface_jpeg_decode_entropy(_p(scans), scans.numel(), _p(ranges), _p(restart), _p(tables), mcus, F_, max_intervals,
                                             _p(out), stride, _p(status), _stream()), "vface_jpeg_decode_entropy")
     return out, status
+
+
+JPEG_PARALLEL_LANES = (64, 256)     # lanes (subsequences) per chunk of the two instantiations (csrc/jpeg_subseq.hpp)
+_jpeg_parallel_ws = {}
+
+
+def jpeg_parallel_lanes(scan_bytes: int, frames: int, max_intervals: int, subseq_bytes: int) -> int:
+    """Lanes per chunk ``vface_jpeg_decode_entropy_parallel`` picks for a call (``vf_jpeg_subseq_lanes`` of csrc/jpeg_subseq.hpp, the
+    same integer arithmetic): the long form once the average interval holds at least as many subsequences as the short form has
+    lanes.  ``rounds`` depends on it, the coefficients do not."""
+    intervals = max(int(frames) * int(max_intervals), 1)
+    return JPEG_PARALLEL_LANES[1] if int(scan_bytes) // intervals // int(subseq_bytes) >= JPEG_PARALLEL_LANES[0] else JPEG_PARALLEL_LANES[0]
+
+
+def jpeg_decode_entropy_parallel(scans: torch.Tensor, ranges: torch.Tensor, status: torch.Tensor, restart: torch.Tensor,
+                                 tables: torch.Tensor, mcus: int, subseq_bytes: int = 256, out: Optional[torch.Tensor] = None,
+                                 return_rounds: bool = False):
+    """``jpeg_decode_entropy``'s arguments and result -- the same coefficients and statuses for every input, valid or corrupt --
+    from many lanes per restart interval: the interval is cut into subsequences of ``subseq_bytes`` raw scan bytes (a multiple of
+    4 in 4..1024; 256 is what tools/bench_mjpeg_in.py's sweep chose), one workgroup decodes them from guessed states, chunk by chunk, and stitches them by self-synchronisation; DC
+    values come from a prefix sum of the differences; a frame the serial routine would refuse is decoded again by the serial
+    routine itself (csrc/jpeg_subseq.hpp, csrc/mjpeg_in.hip).  For scans without restart markers, where ``jpeg_decode_entropy``
+    has one lane per frame.  ``return_rounds``: also int32 [F, max_intervals], the synchronisation rounds that changed a state,
+    summed over an interval's chunks (at most its subsequences minus its chunks: a stream that never synchronises)."""
+    F_, mcus, max_intervals, out, stride = _jpeg_decode_args("jpeg_decode_entropy_parallel", scans, ranges, status, restart, tables,
+                                                             mcus, out)
+    subseq_bytes = int(subseq_bytes)
+    if not 4 <= subseq_bytes <= 1024 or subseq_bytes % 4:
+        raise VFaceHipError(f"jpeg_decode_entropy_parallel: subseq_bytes must be a multiple of 4 in 4..1024; got {subseq_bytes}")
+    lib = load()
+    need = int(lib.vface_jpeg_decode_entropy_parallel_workspace_bytes(F_))
+    ws = _jpeg_parallel_ws.get(str(scans.device))
+    if ws is None or ws.numel() < need:
+        ws = _jpeg_parallel_ws[str(scans.device)] = torch.empty(need, dtype=torch.uint8, device=scans.device)
+    rounds = torch.empty(F_, max_intervals, dtype=torch.int32, device=scans.device) if return_rounds else None
+    _check(lib.vface_jpeg_decode_entropy_parallel(_p(scans), scans.numel(), _p(ranges), _p(restart), _p(tables), mcus, F_, max_intervals,
+                                                  _p(out), stride, _p(status), subseq_bytes, _p(ws), ws.numel(), _p(rounds), _stream()),
+           "vface_jpeg_decode_entropy_parallel")
+    return (out, status, rounds) if return_rounds else (out, status)
 
 
 def jpeg_planes(coef: torch.Tensor, quant: torch.Tensor, W: int, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -109,6 +109,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--chroma_upsample", choices=["sited", "nearest"], default=None,
                    help="with --target_video: sited (default) = interpolate the chroma where the header says its samples sit "
                         "(C420jpeg: centre; C420mpeg2: left); nearest = repeat each sample over its 2 x 2 block")
+    p.add_argument("--video_in_entropy", choices=["auto", "serial", "parallel"], default=None,
+                   help="with --target_video FILE.avi: how the Huffman decoder spreads a frame over lanes.  serial = one lane per "
+                        "restart interval; parallel = many lanes inside an interval, stitched by self-synchronisation "
+                        "(csrc/jpeg_subseq.hpp); auto (default) = parallel where a restart interval is long -- files without restart markers "
+                        "(ffmpeg's, Pillow's, most cameras') above all -- serial otherwise (scripts/mjpeg_in.entropy_path).  The frames "
+                        "are the same bit for bit.  Refused with a .y4m")
     p.add_argument("--src_image", type=str, default=None, help="real-clip run: the source image (the identity to put in)")
     p.add_argument("--landmarks", type=str, default=None,
                    help="real-clip run: .npz with dlib's 68 points, which this build does not compute -- frames [N, 68, 2] (a NaN row = "
@@ -266,11 +272,24 @@ def check_clip_options(opt):
 
 
 def check_video_in_options(opt):
-    """--video_in_matrix and --chroma_upsample say how --target_video is read: without it they would be ignored, so they are refused."""
+    """--video_in_matrix, --chroma_upsample and --video_in_entropy say how --target_video is read: without it they would be ignored, so
+    they are refused."""
     opt = normalise_options(opt)
     for flag in ("video_in_matrix", "chroma_upsample"):
         if vars(opt)[flag] is not None and not opt.target_video:
             raise SystemExit(f"--{flag} says how --target_video is converted: it needs --target_video FILE.y4m")
+    if opt.video_in_entropy is not None and not opt.target_video:
+        raise SystemExit("--video_in_entropy says how --target_video is decoded: it needs --target_video FILE.avi")
+
+
+def check_video_in_reader(opt, video):
+    """The flags that belong to ONE of the two readers of --target_video, once the file's first bytes have said which it is."""
+    if video.fixed_matrix and opt.video_in_matrix:
+        raise SystemExit(f"--video_in_matrix names the matrix of a file that cannot tag it; {opt.target_video} is Motion-JPEG, and "
+                         f"JFIF fixes full-range BT.601: leave the flag out")
+    if not video.fixed_matrix and opt.video_in_entropy:
+        raise SystemExit(f"--video_in_entropy chooses the Huffman decoder of Motion-JPEG; {opt.target_video} is YUV4MPEG2, which has "
+                         f"no entropy coding: leave the flag out")
 
 
 def check_video_out_options(opt):
@@ -341,9 +360,7 @@ def _run(opt) -> dict:
         if opt.target_video:
             from .mjpeg_in import open_video
             video = open_video(opt.target_video)            # by the file's first bytes: a YUV4MPEG2 file, or an AVI with an MJPG stream
-            if video.fixed_matrix and opt.video_in_matrix:
-                raise SystemExit(f"--video_in_matrix names the matrix of a file that cannot tag it; {opt.target_video} is Motion-JPEG, and "
-                                 f"JFIF fixes full-range BT.601: leave the flag out")
+            check_video_in_reader(opt, video)
             clip = ClipInputs.from_video(video, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         else:
             clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)

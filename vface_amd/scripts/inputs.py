@@ -225,6 +225,7 @@ class ClipRunInputs:
         self.plan = batch_plan(opt)
         self._last_labels = {}      # batch id -> its last frame's label map, for the first frame of the batch after it
         self.matrix, self.chroma_upsample = opt.video_in_matrix or "bt709", opt.chroma_upsample or "sited"
+        self.entropy = getattr(opt, "video_in_entropy", None) or "auto"     # (an AVI's Huffman decoder: scripts/mjpeg_in.entropy_path)
         self._seconds = {}          # batch id -> wall seconds of what this provider did on the device for it (`own_seconds`)
 
     def _rows(self, k):
@@ -252,6 +253,8 @@ class ClipRunInputs:
 
     def _rgb(self, read):
         """What the clip's reader handed out (I420 rows of a Y4M file, the scans of an AVI's JPEG frames) -> device RGB frames."""
+        if self.clip.video.fixed_matrix:            # Motion-JPEG: --video_in_entropy is its reader's alone
+            return self.clip.video.to_rgb(read, self.device, self.matrix, self.chroma_upsample, entropy=self.entropy)
         return self.clip.video.to_rgb(read, self.device, self.matrix, self.chroma_upsample)
 
     def own_seconds(self, k):

@@ -14,7 +14,9 @@ full-range BT.601, centre-sited chroma) there.
   takes the typical tables of T.81 Annex K, as AVI MJPG frames commonly do.  Size and sampling are those of frame 0.
 - **One RIFF only**: a file continued in ``AVIX`` chunks (OpenDML) is refused; ``indx`` / ``ix##`` chunks of a file that ends in its
   first RIFF are index data and are skipped.  Audio chunks are skipped.  Raw ``.mjpeg`` streams, QuickTime and MP4 are not read.
-- A file without restart markers (ffmpeg's) decodes with one lane per FRAME: correct, and slow.
+- A file without restart markers (ffmpeg's, Pillow's, most cameras') is ONE interval per frame: ``hip.jpeg_decode_entropy`` gives it
+  one lane, ``hip.jpeg_decode_entropy_parallel`` cuts it into subsequences and decodes them on many lanes (csrc/jpeg_subseq.hpp).
+  ``entropy_path`` chooses between the two; the coefficients are the same bit for bit.
 """
 from __future__ import annotations
 
@@ -257,12 +259,33 @@ class MJPEGFrames:
                 "tables": torch.from_numpy(np.stack([r.tables for r in self.records]))}
 
 
-def decode(frames: MJPEGFrames, device, chroma: str = "centre"):
+# ``entropy="auto"`` takes the parallel decoder once the longest restart interval of a call averages this many scan bytes: just under
+# the shortest intervals tools/bench_mjpeg_in.py measured (the writer's 512 x 512 frames, one interval per MCU row, 1789 bytes on
+# average), where the parallel form already wins by 1.46x; it wins by more on every longer one.  Shorter intervals were
+# not measured and stay serial.
+PARALLEL_MIN_INTERVAL_BYTES = 1750
+SUBSEQ_BYTES = 256              # the parallel decoder's subsequence size: beats the serial form on every case of the sweep (so does 512)
+
+
+def entropy_path(frames: "MJPEGFrames", mcus: int) -> str:
+    """``"serial"`` | ``"parallel"`` for one ``decode`` call, from the host's records alone: parallel when the largest
+    ``len(scan) / interval count`` of the call reaches ``PARALLEL_MIN_INTERVAL_BYTES`` -- every file without restart markers but
+    the smallest, and files with restart markers whose intervals are long."""
+    from ..hip import jpeg_interval_count
+    longest = max(len(r.scan) / jpeg_interval_count(mcus, r.restart) for r in frames.records)
+    return "parallel" if longest >= PARALLEL_MIN_INTERVAL_BYTES else "serial"
+
+
+def decode(frames: MJPEGFrames, device, chroma: str = "centre", entropy: str = "auto"):
     """``MJPEGReader.read``'s result -> ``(rgb, status)``: device uint8 [F, H, W, 3] and the per-frame status as a host list
     (0 = decoded; ``hip.JPEG_STATUS`` names the others -- such a frame's pixels are those of the coefficients that were decoded
     before the fault, zeros behind them).  ``chroma``: centre (JFIF's siting; the (3, 1)/4 weights are libjpeg's "fancy"
-    upsampling) | nearest.  Four launches and one copy of the statuses; there is no host decoder."""
+    upsampling) | nearest.  ``entropy``: serial (one lane per restart interval) | parallel (many lanes inside an interval) | auto
+    (``entropy_path``); the result does not depend on it.  A handful of launches and one copy of the statuses; there is no host
+    decoder."""
     from .. import hip
+    if entropy not in ("auto", "serial", "parallel"):
+        raise hip.VFaceHipError(f"mjpeg_in.decode: entropy is auto, serial or parallel; got {entropy!r}")
     if not isinstance(frames, MJPEGFrames) or len(frames) == 0:
         raise hip.VFaceHipError("mjpeg_in.decode: frames must be what MJPEGReader.read returned, at least one frame")
     device = torch.device(device)
@@ -274,7 +297,10 @@ def decode(frames: MJPEGFrames, device, chroma: str = "centre"):
     mcus = mcu_count(frames.W, frames.H)
     most = max(hip.jpeg_interval_count(mcus, r.restart) for r in frames.records)
     ranges, status = hip.jpeg_scan_index(p["scans"], p["offsets"], p["lengths"], p["restart"], mcus, most)
-    coef, status = hip.jpeg_decode_entropy(p["scans"], ranges, status, p["restart"], p["tables"], mcus)
+    if (entropy_path(frames, mcus) if entropy == "auto" else entropy) == "parallel":
+        coef, status = hip.jpeg_decode_entropy_parallel(p["scans"], ranges, status, p["restart"], p["tables"], mcus, SUBSEQ_BYTES)
+    else:
+        coef, status = hip.jpeg_decode_entropy(p["scans"], ranges, status, p["restart"], p["tables"], mcus)
     rows = hip.jpeg_planes(coef, p["quant"], frames.W, frames.H)
     rgb = hip.yuv420_to_rgb(rows, frames.W, frames.H, matrix="bt601", full_range=True, chroma=chroma)
     return rgb, status.cpu().tolist()
@@ -453,11 +479,11 @@ class MJPEGReader:
             records.append(FrameRecord(i, data[frame.scan[0]:frame.scan[1]], frame.restart, quant_block(frame), huffman_block(frame)))
         return MJPEGFrames(self.path, self.W, self.H, records)
 
-    def to_rgb(self, frames: MJPEGFrames, device, matrix=None, chroma_upsample: str = "sited") -> torch.Tensor:
+    def to_rgb(self, frames: MJPEGFrames, device, matrix=None, chroma_upsample: str = "sited", entropy: str = "auto") -> torch.Tensor:
         """The common surface of the readers (``demux.Y4MReader.to_rgb``): what ``read`` returned -> device uint8 [F, H, W, 3].
-        A frame that does not decode ends the run."""
+        ``entropy``: ``decode``'s.  A frame that does not decode ends the run."""
         from .. import hip
-        rgb, status = decode(frames, device, "nearest" if chroma_upsample == "nearest" else "centre")
+        rgb, status = decode(frames, device, "nearest" if chroma_upsample == "nearest" else "centre", entropy)
         for record, code in zip(frames.records, status):
             if code:
                 raise SystemExit(f"{self.path}: frame {record.index} does not decode: {hip.JPEG_STATUS.get(code, code)} (status {code})")
