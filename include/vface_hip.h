@@ -350,6 +350,37 @@ size_t vface_jpeg_entropy_workspace_bytes(int mcus, int frames, int restart);
 int vface_jpeg_entropy(const int16_t* coef, int64_t frame_stride, int mcus, int frames, int restart, uint8_t* out, int64_t out_bytes,
                        int32_t* lengths, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG frames out (REFace/scripts/VFace_inference_batch.py:636) -------------------------------------------------------------
+ * The reference's main output is one PNG per pasted frame (:636).  These entry points make the deflate body of every frame's zlib
+ * stream on the device; vface_amd/scripts/png.py adds 78 01, the Adler-32, the chunk framing and the CRC, and the host receives the
+ * compressed bytes and O(stripes) scalars only.  csrc/png.hip; the code-length construction is csrc/png_huffman.hpp, which a host
+ * program runs under sanitizers.  The format is stated once in tests/png_model.py and equalled byte for byte.
+ *
+ * vface_png_filter (:636): rgb [frames][H][W][3] -> rows [frames][H][1 + 3 W]: every row's filter byte and filtered bytes.  A row
+ *   takes the type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; bpp 3; the row above a frame's row 0 is zeros) whose filtered bytes,
+ *   read as signed, have the smallest sum of absolute values; a tie goes to the lowest type.  Predictions read the source pixels.
+ *   NULL pointer, W, H or frames <= 0: VFACE_ERR_ARG; W > 2^22 or (1 + 3 W) * H >= 2^31: VFACE_ERR_SHAPE.
+ *
+ * vface_png_deflate (:636): rows [frames][H][row_bytes] of ANY bytes, row_bytes >= 1 -> one deflate body per frame, packed back
+ *   to back into out; offsets [frames] and lengths [frames] take each body's place and byte count.  A frame is cut into stripes
+ *   of stripe_rows rows (the last may be shorter), coded independently by one workgroup each: a dynamic-Huffman block, BFINAL 0, of
+ *   literals and distance-1 matches of 3..258 (greedy: a run's first byte is a literal, the rest is cut into matches of 258, a
+ *   remainder of 3 or more is one match, of 1 or 2 literals), ended by symbol 256 and followed by an empty stored block (3 bits,
+ *   padding, 00 00 FF FF) that byte-aligns it -- or, where that is not SMALLER, stored blocks of at most 65535 bytes.  03 00, an
+ *   empty final fixed block, ends a body.  Lit/len codes of at most 15 bits, HLIT 29, one distance code of length 1, code-length
+ *   codes of at most 7 bits, zero runs as symbols 18 and 17 (csrc/png_huffman.hpp).  adler [frames][stripes][2], stripes =
+ *   ceil(H / stripe_rows): (s1, s2) of Adler-32 over every stripe's bytes alone.  Bytes past out_bytes are dropped, never written:
+ *   out_bytes >= frames * vface_png_deflate_bound(row_bytes, H, stripe_rows) always suffices and is reached by incompressible rows.
+ *   workspace: vface_png_deflate_workspace_bytes(row_bytes, H, frames, stripe_rows) bytes, 16-byte aligned.  Three launches, no
+ *   allocation, no host synchronisation.
+ *   NULL pointer, row_bytes, H, frames, stripe_rows or out_bytes <= 0: VFACE_ERR_ARG; row_bytes * H or the bound >= 2^31, a workspace
+ *   too small: VFACE_ERR_SHAPE; a workspace off 16 bytes: VFACE_ERR_ALIGN. */
+int vface_png_filter(const uint8_t* rgb, int W, int H, int frames, uint8_t* rows, void* stream);
+int64_t vface_png_deflate_bound(int row_bytes, int rows, int stripe_rows);
+size_t vface_png_deflate_workspace_bytes(int row_bytes, int H, int frames, int stripe_rows);
+int vface_png_deflate(const uint8_t* rows, int row_bytes, int H, int frames, int stripe_rows, uint8_t* out, int64_t out_bytes,
+                      int64_t* offsets, int32_t* lengths, uint32_t* adler, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- video in, colour half (REFace/scripts/VFace_inference_batch.py:240-285) --------------------------------------------------
  * The reference decodes the target video on the host (cv2.VideoCapture, BGR -> RGB, PNG per frame, :240-285).  The H.264 decoder
  * is not built here either; vface_amd/scripts/demux.py reads the YUV4MPEG2 file any decoder writes (`ffmpeg -i in.mp4 clip.y4m`),

@@ -89,6 +89,10 @@ SIGNATURES = {
     "vface_jpeg_coefficients": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "vface_jpeg_entropy_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "vface_jpeg_entropy": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "vface_png_filter": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "vface_png_deflate_bound": (_i64, [_i32, _i32, _i32]),
+    "vface_png_deflate_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "vface_png_deflate": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_jpeg_scan_index": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_jpeg_decode_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -635,6 +639,74 @@ def jpeg_entropy(coef: torch.Tensor, restart: int, out: Optional[torch.Tensor] =
     _check(lib.vface_jpeg_entropy(_p(coef), stride, mcus, F_, restart, _p(out), out.numel(), _p(lengths), _p(ws), ws.numel(),
                                   _stream()), "vface_jpeg_entropy")
     return out, lengths
+
+
+# ---- PNG frames out (:636; csrc/png.hip)
+PNG_STRIPE_ROWS = 16               # rows of a frame that make one independent deflate block: tools/bench_png.py's sweep over 4, 8, 16, 32
+                                   # (profiles/r11_a_*): the fastest at 512 x 512, within 5 % of 8 at 1920 x 1080, smaller files than either
+PNG_FILTER_GRID_CAP = 2048         # kPngFilterGridCap: workgroups of PNG_FILTER_ROWS_PER_GROUP rows before the grid loops
+PNG_FILTER_ROWS_PER_GROUP = 4
+PNG_DEFLATE_GRID_CAP = 4096        # kPngDeflateGridCap: workgroups, one (frame, stripe) each, before the grid loops
+_png_ws = {}
+
+
+def png_deflate_bound(row_bytes: int, rows: int, stripe_rows: int = PNG_STRIPE_ROWS) -> int:
+    """Bytes that always hold the deflate body of ``rows`` rows of ``row_bytes`` bytes: every stripe as stored blocks of at most
+    65535 bytes (5 bytes of header each) and the final ``03 00``.  Exact for incompressible rows: a stripe whose dynamic block
+    would not be smaller is stored."""
+    return int(load().vface_png_deflate_bound(int(row_bytes), int(rows), int(stripe_rows)))
+
+
+def png_filter(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 device frames [F, H, W, 3] -> uint8 [F, H, 1 + 3 W]: every row's PNG filter byte and filtered bytes (:636).  A row takes
+    the type (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; bpp 3; zeros above row 0) whose filtered bytes, read as signed, have the
+    smallest sum of absolute values, a tie the lowest type; ``tests/png_model.filter_rows`` bit for bit (csrc/png.hip)."""
+    if (not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
+            or frames_u8.shape[-1] != 3 or not frames_u8.is_contiguous()):
+        raise VFaceHipError("png_filter: frames must be contiguous uint8 [F, H, W, 3] on the GPU")
+    F_, H, W, _ = frames_u8.shape
+    if min(F_, H, W) <= 0:
+        raise VFaceHipError("png_filter: F, H and W must be positive")
+    shape = (F_, H, 1 + 3 * W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames_u8.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != frames_u8.device or not out.is_contiguous():
+        raise VFaceHipError(f"png_filter: out must be a contiguous uint8 {list(shape)} tensor on the frames' device")
+    _check(load().vface_png_filter(_p(frames_u8), W, H, F_, _p(out), _stream()), "vface_png_filter")
+    return out
+
+
+def png_deflate(rows: torch.Tensor, stripe_rows: int = PNG_STRIPE_ROWS, out: Optional[torch.Tensor] = None):
+    """Row buffers of ANY bytes, device uint8 [F, H, row_bytes] -> ``(out, meta, offsets)``: every frame's deflate body packed back
+    to back in the uint8 buffer ``out`` (frame f at ``offsets[f]``, int64 [F]) and int32 ``meta``: ``meta[:F]`` the bodies' byte
+    counts, ``meta[F:]`` viewed as [F, stripes, 2] the Adler-32 halves (s1, s2) of every stripe's bytes -- one small copy gives the host
+    all it needs besides ``out[:lengths.sum()]``.  Stripes of ``stripe_rows`` rows are coded independently: one dynamic-Huffman
+    block of literals and distance-1 matches closed by an empty stored block, or stored blocks where that is not smaller; ``03 00``
+    ends a body (csrc/png.hip; ``tests/png_model.deflate_rows`` byte for byte).  ``out``: a contiguous uint8 buffer, by default
+    F x ``png_deflate_bound``.  Bytes that a smaller ``out`` cannot hold are dropped, and the caller sees it from the lengths."""
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 3 or not rows.is_contiguous():
+        raise VFaceHipError("png_deflate: rows must be a contiguous uint8 [F, H, row_bytes] tensor on the GPU")
+    F_, H, rb = rows.shape
+    stripe_rows = int(stripe_rows)
+    if min(F_, H, rb) <= 0 or stripe_rows <= 0:
+        raise VFaceHipError(f"png_deflate: F, H, row_bytes and stripe_rows must be positive; got {F_}, {H}, {rb}, {stripe_rows}")
+    if rb * H >= 1 << 31 or png_deflate_bound(rb, H, stripe_rows) >= 1 << 31:
+        raise VFaceHipError(f"png_deflate: a frame's rows and its bound stay below 2^31 bytes; got {rb} x {H}")
+    if out is None:
+        out = torch.empty(F_ * png_deflate_bound(rb, H, stripe_rows), dtype=torch.uint8, device=rows.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != rows.device or out.numel() == 0:
+        raise VFaceHipError("png_deflate: out must be a contiguous uint8 buffer on the rows' device")
+    lib = load()
+    need = int(lib.vface_png_deflate_workspace_bytes(rb, H, F_, stripe_rows))
+    ws = _png_ws.get(str(rows.device))
+    if ws is None or ws.numel() < need:
+        ws = _png_ws[str(rows.device)] = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    stripes = (H + stripe_rows - 1) // stripe_rows
+    meta = torch.empty(F_ + 2 * F_ * stripes, dtype=torch.int32, device=rows.device)
+    offsets = torch.empty(F_, dtype=torch.int64, device=rows.device)
+    _check(lib.vface_png_deflate(_p(rows), rb, H, F_, stripe_rows, _p(out), out.numel(), _p(offsets), _p(meta), _p(meta[F_:]), _p(ws),
+                                 ws.numel(), _stream()), "vface_png_deflate")
+    return out, meta, offsets
 
 
 YUV_MATRICES = {"bt709": 0, "bt601": 1}

@@ -14,7 +14,8 @@ Without ``--synthetic`` the run is a real clip's (``run_clip``): every one of th
 landmarks file from disk (``scripts/clip_io.py``; dlib and the H.264 decoder stay outside, so dlib's 68 points and the decoded clip
 are inputs: the ``{index}.png`` frames the reference writes at ``:285``, or -- ``--target_video`` -- the YUV4MPEG2 file any decoder
 writes, whose I420 planes are uploaded and converted to RGB on the GPU, ``scripts/demux.py``, csrc/demux.hip), the pasted frames out
-as PNG (``:636``) and, with ``--video_out``, as a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps
+as PNG (``:636``; by Pillow on the host or, with ``--png_encoder gpu``, filtered and deflated on the GPU: ``scripts/png.py``,
+csrc/png.hip) and, with ``--video_out``, as a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps
 (``:646-654``; ``scripts/mux.py``) or, with ``--video_codec mjpeg``, as Motion-JPEG in an AVI: a baseline JPEG encoder on the GPU
 (``scripts/mjpeg.py``, csrc/mjpeg.hip), a compressed file every player opens.  H.264 and audio are not built.
 
@@ -129,6 +130,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "assumes, 10 fps, no audio")
     p.add_argument("--video_quality", type=int, default=None,
                    help="with --video_codec mjpeg: libjpeg's quality scale, 1..100 (default 90): the tables Pillow's quality= yields")
+    p.add_argument("--png_encoder", choices=["pillow", "gpu"], default="pillow",
+                   help="how the pasted frames' PNGs (:636) are compressed: pillow (default) = Pillow on the host, frame by frame; gpu = "
+                        "filter and deflate on the GPU (csrc/png.hip, scripts/png.py; distance-1 matches only), timed as the batch's "
+                        "png_out stage.  Both are lossless and decode to the same pixels")
     p.add_argument("--synthetic_weights", action="store_true",
                    help="real-clip run on seeded weights for every model (the seeds of --synthetic) instead of --ckpt, "
                         "--faceParsing_ckpt and --raft_ckpt: for tests and smoke runs")

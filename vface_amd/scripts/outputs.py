@@ -12,20 +12,41 @@ def _save_png(frame_u8, path):
     Image.fromarray(frame_u8.cpu().numpy()).save(path)                                             # :636
 
 
+class _PNGSink:
+    """``--png_encoder``: ``pillow`` saves frame by frame on the host, untimed, as before; ``gpu`` encodes a batch's frames in one
+    call of ``scripts/png.py``'s ``PNGEncoder`` (made for the first batch's size) under the batch's ``png_out`` stage."""
+
+    def __init__(self, opt):
+        self.gpu, self.encoder = getattr(opt, "png_encoder", "pillow") == "gpu", None
+
+    def save(self, b, paths):
+        if not self.gpu:
+            for f, path in enumerate(paths):
+                _save_png(b.pasted[f], path)
+            return
+        with b.timer("png_out"):
+            H, W = b.pasted.shape[1], b.pasted.shape[2]
+            if self.encoder is None or (self.encoder.W, self.encoder.H) != (W, H):
+                from .png import PNGEncoder
+                self.encoder = PNGEncoder(W, H)
+            for path, data in zip(paths, self.encoder.encode(b.pasted)):
+                with open(path, "wb") as f:
+                    f.write(data)
+
+
 class SeededOutputs:
     """``--synthetic``: ``samples_batch{k}.pt``, ``pixels_batch{k}.pt`` and ``pasted_b{k}_f{f}.png`` under ``--Base_dir``,
     nothing with ``--skip_save``."""
 
     def __init__(self, opt):
-        self.dir, self.save = opt.Base_dir, not opt.skip_save
+        self.dir, self.save, self.png = opt.Base_dir, not opt.skip_save, _PNGSink(opt)
         os.makedirs(self.dir, exist_ok=True)
 
     def write(self, b):
         if not self.save:
             return
         if b.pasted is not None:
-            for f in range(b.pasted.shape[0]):
-                _save_png(b.pasted[f], os.path.join(self.dir, f"pasted_b{b.id}_f{f}.png"))
+            self.png.save(b, [os.path.join(self.dir, f"pasted_b{b.id}_f{f}.png") for f in range(b.pasted.shape[0])])
         torch.save(b.samples.cpu(), os.path.join(self.dir, f"samples_batch{b.id}.pt"))
         if b.pixels is not None:
             torch.save(b.pixels.cpu(), os.path.join(self.dir, f"pixels_batch{b.id}.pt"))
@@ -35,14 +56,14 @@ class SeededOutputs:
 
 
 class ClipOutputs:
-    """A clip from disk: the pasted frames as ``Base_dir/results/{index}.png`` (:636) unless ``--skip_save`` and, with
+    """A clip from disk: the pasted frames as ``Base_dir/results/{index}.png`` (:636; ``--png_encoder``) unless ``--skip_save`` and, with
     ``--video_out``, as YUV4MPEG2 in frame order (:646-654: yuv420p, BT.709, tv range, 10 fps; scripts/mux.py), the batch's
     ``video_out`` stage -- or, with ``--video_codec mjpeg``, as Motion-JPEG in an AVI at ``--video_quality`` (default 90;
     scripts/mjpeg.py), the same stage.  The file is opened by the first batch, whose frames give its size."""
 
     def __init__(self, opt):
         self.dir, self.save, self.video_out, self.writer = opt.Base_dir, not opt.skip_save, opt.video_out, None
-        self.codec, self.quality = opt.video_codec or "y4m", opt.video_quality
+        self.codec, self.quality, self.png = opt.video_codec or "y4m", opt.video_quality, _PNGSink(opt)
         os.makedirs(self.dir, exist_ok=True)
 
     def write(self, b):
@@ -59,8 +80,7 @@ class ClipOutputs:
                 self.writer.write(b.pasted)
         if self.save:
             os.makedirs(os.path.join(self.dir, "results"), exist_ok=True)
-            for f, index in enumerate(b.frame_ids):
-                _save_png(b.pasted[f], os.path.join(self.dir, "results", f"{index}.png"))
+            self.png.save(b, [os.path.join(self.dir, "results", f"{index}.png") for index in b.frame_ids])
 
     def close(self):
         if self.writer is not None:
