@@ -381,6 +381,44 @@ size_t vface_png_deflate_workspace_bytes(int row_bytes, int H, int frames, int s
 int vface_png_deflate(const uint8_t* rows, int row_bytes, int H, int frames, int stripe_rows, uint8_t* out, int64_t out_bytes,
                       int64_t* offsets, int32_t* lengths, uint32_t* adler, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG frames in (REFace/scripts/VFace_inference_batch.py:285) --------------------------------------------------------------
+ * The reference writes the target clip as {index}.png (:285) and reads the folder back.  vface_amd/scripts/png_in.py walks each
+ * file's chunks on the host (CRCs, IHDR, the zlib header) and uploads the deflate bodies as they lie in the files; these entry
+ * points make 8-bit RGB frames of them on the device.  csrc/png_in.hip; what file bytes steer is csrc/png_inflate.hpp, which a
+ * host program runs under sanitizers.  The format is stated once in tests/png_inflate_model.py and equalled bit for bit.
+ *
+ * vface_png_inflate: raw deflate bodies (RFC 1951; no zlib header, no Adler-32), file f at streams + offsets[f], lengths[f] bytes
+ *   -> the filtered rows, file f at rows + f * file_stride, exactly `expect` bytes where status[f] is 0.  Stored, fixed and dynamic
+ *   blocks, code lengths up to 15 bits, repeats running across the literal/distance boundary, distances up to 32768.  One wave per
+ *   file.  No byte outside [offsets[f], offsets[f] + lengths[f]) is read; a range that does not lie inside [0, stream_bytes) gets
+ *   status 1.  No byte outside the file's `expect` bytes is written whatever the stream holds, and none past produced[f].
+ *   status[f] is the first condition met in stream order (within a dynamic header in this order): 0 the final block ended with
+ *   exactly `expect` bytes; 1 a bit was needed past the stream's end; 2 block type 3; 3 stored block, LEN != ~NLEN; 4 more than 286
+ *   literal/length or 30 distance codes; 5 the code-length code is over-subscribed or incomplete; 6 repeat 16 with no previous length,
+ *   or a repeat past HLIT + HDIST; 7 no code for symbol 256; 8 the literal/length set is over-subscribed, or incomplete and not a
+ *   single 1-bit code; 9 the same for the distance set (no code at all is legal); 10 bits that are no literal/length code, or symbol
+ *   286 / 287; 11 bits that are no distance code, or symbol 30 / 31; 12 a distance greater than the bytes produced so far; 13 more
+ *   than `expect` bytes (the token that would pass it is not written); 14 the final block ended with fewer.  zlib 1.2.11 accepts a
+ *   stream exactly where this does.  produced[f]: bytes written; consumed[f]: whole bytes of the body behind the last bit taken
+ *   (lengths[f] for status 1 -- but 0, like produced[f], for a file whose range lies outside the stream buffer: nothing of it was
+ *   read; bytes behind the final block are accepted and not counted); adler [files][2]: (s1, s2) of Adler-32
+ *   over the produced bytes.  One launch, no allocation, no host synchronisation.
+ *   NULL pointer, files, stream_bytes or expect <= 0: VFACE_ERR_ARG; expect or stream_bytes >= 2^31, file_stride < expect:
+ *   VFACE_ERR_SHAPE.
+ *
+ * vface_png_unfilter: rows [files][H][1 + bpp W] at file_stride -> rgb [files][H][W][3]: the five filter types (0 None, 1 Sub,
+ *   2 Up, 3 Average, 4 Paeth with ties a, b, c) undone with bytes mod 256, the row above row 0 zeros, bpp bytes to the left; bpp 4
+ *   drops alpha, bpp 1 replicates grey.  status[f]: 0, or 1 + the first row whose filter byte is above 4.  A file whose
+ *   inflate_status is not 0 is not read; its frame, and the frame of a file with a bad filter byte, is cleared to 0.  One wave per
+ *   file walks bands of 64 rows in a skewed wavefront, every lane loading and storing its own row.
+ *   NULL pointer, W, H or files <= 0: VFACE_ERR_ARG; bpp outside {1, 3, 4}, (1 + bpp W) * H >= 2^31, file_stride below that, or
+ *   W > 8192 (the row carried between bands lives in LDS): VFACE_ERR_SHAPE. */
+int vface_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, const int32_t* lengths, int files,
+                      uint8_t* rows, int64_t file_stride, int64_t expect, int32_t* status, int32_t* produced, int32_t* consumed,
+                      uint32_t* adler, void* stream);
+int vface_png_unfilter(const uint8_t* rows, int64_t file_stride, int W, int H, int bpp, int files, const int32_t* inflate_status,
+                       uint8_t* rgb, int32_t* status, void* stream);
+
 /* ---- video in, colour half (REFace/scripts/VFace_inference_batch.py:240-285) --------------------------------------------------
  * The reference decodes the target video on the host (cv2.VideoCapture, BGR -> RGB, PNG per frame, :240-285).  The H.264 decoder
  * is not built here either; vface_amd/scripts/demux.py reads the YUV4MPEG2 file any decoder writes (`ffmpeg -i in.mp4 clip.y4m`),

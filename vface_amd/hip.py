@@ -93,6 +93,8 @@ SIGNATURES = {
     "vface_png_deflate_bound": (_i64, [_i32, _i32, _i32]),
     "vface_png_deflate_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "vface_png_deflate": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vface_png_inflate": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "vface_png_unfilter": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_jpeg_scan_index": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_jpeg_decode_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -707,6 +709,75 @@ def png_deflate(rows: torch.Tensor, stripe_rows: int = PNG_STRIPE_ROWS, out: Opt
     _check(lib.vface_png_deflate(_p(rows), rb, H, F_, stripe_rows, _p(out), out.numel(), _p(offsets), _p(meta), _p(meta[F_:]), _p(ws),
                                  ws.numel(), _stream()), "vface_png_deflate")
     return out, meta, offsets
+
+
+# ---- PNG frames in (:285; csrc/png_in.hip)
+PNG_UNFILTER_MAX_W = 8192          # kUnfilterMaxW: the row carried from one band of 64 rows to the next lives in LDS
+PNG_INFLATE_GRID_CAP = 1024        # kInflateGridCap: workgroups, one file each, before the grid loops
+
+
+def _is_dev(t, dtype, dim=None):
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and (dim is None or t.dim() == dim)
+
+
+def png_inflate(streams: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, expect: int, out: Optional[torch.Tensor] = None,
+                meta: Optional[torch.Tensor] = None):
+    """Raw deflate bodies (RFC 1951), file f the ``lengths[f]`` (int32 [F]) bytes at ``offsets[f]`` (int64 [F]) of the uint8 device
+    buffer ``streams`` -> ``(rows, meta)``: uint8 [F, expect], each file's bytes, and int32 ``meta`` [5, F]: status, produced,
+    consumed, and in ``meta[3:]`` viewed as [F, 2] the Adler-32 halves (s1, s2) of the produced bytes.  Status 0: the final block
+    ended with exactly ``expect`` bytes; 1..14 name what stopped the stream first (``scripts/png_in.INFLATE_STATUS``); such a file's
+    row holds the ``produced`` bytes made before, and nothing is written behind them.  One wave per file (csrc/png_in.hip;
+    ``tests/png_inflate_model.inflate`` bit for bit).  ``out``: a uint8 [F, >= expect] buffer; ``meta``: an int32 [5, F] one."""
+    if not _is_dev(streams, torch.uint8, 1) or streams.numel() == 0:
+        raise VFaceHipError("png_inflate: streams must be a contiguous uint8 buffer on the GPU, at least one byte")
+    if not _is_dev(offsets, torch.int64, 1) or not _is_dev(lengths, torch.int32, 1) or offsets.numel() != lengths.numel() or offsets.numel() == 0:
+        raise VFaceHipError("png_inflate: offsets (int64) and lengths (int32) must be contiguous [F] tensors on the GPU, F >= 1")
+    if offsets.device != streams.device or lengths.device != streams.device:
+        raise VFaceHipError("png_inflate: streams, offsets and lengths must be on one device")
+    F_, expect = offsets.numel(), int(expect)
+    if not 0 < expect < 1 << 31 or streams.numel() >= 1 << 31:
+        raise VFaceHipError(f"png_inflate: expect and the stream buffer are 1 .. 2^31 - 1 bytes; got {expect}, {streams.numel()}")
+    if out is None:
+        out = torch.empty((F_, expect), dtype=torch.uint8, device=streams.device)
+    elif not _is_dev(out, torch.uint8, 2) or out.shape[0] != F_ or out.shape[1] < expect or out.device != streams.device:
+        raise VFaceHipError(f"png_inflate: out must be a contiguous uint8 [{F_}, >= {expect}] tensor on the streams' device")
+    if meta is None:
+        meta = torch.empty((5, F_), dtype=torch.int32, device=streams.device)
+    elif not _is_dev(meta, torch.int32, 2) or tuple(meta.shape) != (5, F_) or meta.device != streams.device:
+        raise VFaceHipError(f"png_inflate: meta must be a contiguous int32 [5, {F_}] tensor on the streams' device")
+    _check(load().vface_png_inflate(_p(streams), streams.numel(), _p(offsets), _p(lengths), F_, _p(out), out.shape[1], expect, _p(meta[0]),
+                                    _p(meta[1]), _p(meta[2]), _p(meta[3]), _stream()), "vface_png_inflate")
+    return out, meta
+
+
+def png_unfilter(rows: torch.Tensor, W: int, H: int, bpp: int, inflate_status: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 status: Optional[torch.Tensor] = None):
+    """Filtered rows, device uint8 [F, >= H (1 + bpp W)] (``png_inflate``'s rows) -> ``(rgb, status)``: uint8 [F, H, W, 3] and int32
+    [F]: 0, or 1 + the first row whose filter byte is above 4.  bpp 3 = RGB, 4 = RGBA (alpha dropped), 1 = grey (replicated).  A
+    file whose ``inflate_status`` (int32 [F]) is not 0 is not read; its frame, like that of a file with a bad filter byte, is
+    zeros (csrc/png_in.hip; ``tests/png_inflate_model.unfilter`` bit for bit)."""
+    W, H, bpp = int(W), int(H), int(bpp)
+    if bpp not in (1, 3, 4) or min(W, H) <= 0:
+        raise VFaceHipError(f"png_unfilter: W and H must be positive and bpp 1, 3 or 4; got {W}, {H}, {bpp}")
+    need = (1 + bpp * W) * H
+    if need >= 1 << 31 or W > PNG_UNFILTER_MAX_W:
+        raise VFaceHipError(f"png_unfilter: a frame's rows stay below 2^31 bytes and W at or below {PNG_UNFILTER_MAX_W}; got {W} x {H}")
+    if not _is_dev(rows, torch.uint8, 2) or rows.shape[0] == 0 or rows.shape[1] < need:
+        raise VFaceHipError(f"png_unfilter: rows must be a contiguous uint8 [F, >= {need}] tensor on the GPU")
+    F_ = rows.shape[0]
+    if not _is_dev(inflate_status, torch.int32, 1) or inflate_status.numel() != F_ or inflate_status.device != rows.device:
+        raise VFaceHipError(f"png_unfilter: inflate_status must be a contiguous int32 [{F_}] tensor on the rows' device")
+    if out is None:
+        out = torch.empty((F_, H, W, 3), dtype=torch.uint8, device=rows.device)
+    elif not _is_dev(out, torch.uint8, 4) or tuple(out.shape) != (F_, H, W, 3) or out.device != rows.device:
+        raise VFaceHipError(f"png_unfilter: out must be a contiguous uint8 [{F_}, {H}, {W}, 3] tensor on the rows' device")
+    if status is None:
+        status = torch.empty(F_, dtype=torch.int32, device=rows.device)
+    elif not _is_dev(status, torch.int32, 1) or status.numel() != F_ or status.device != rows.device:
+        raise VFaceHipError(f"png_unfilter: status must be a contiguous int32 [{F_}] tensor on the rows' device")
+    _check(load().vface_png_unfilter(_p(rows), rows.shape[1], W, H, bpp, F_, _p(inflate_status), _p(out), _p(status), _stream()),
+           "vface_png_unfilter")
+    return out, status
 
 
 YUV_MATRICES = {"bt709": 0, "bt601": 1}

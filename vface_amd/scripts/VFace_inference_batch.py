@@ -12,7 +12,8 @@ stand-in each by the stage itself on the GPU (synthetic weights unless ``--ckpt`
 
 Without ``--synthetic`` the run is a real clip's (``run_clip``): every one of those stages, on frames, a source image and a
 landmarks file from disk (``scripts/clip_io.py``; dlib and the H.264 decoder stay outside, so dlib's 68 points and the decoded clip
-are inputs: the ``{index}.png`` frames the reference writes at ``:285``, or -- ``--target_video`` -- the YUV4MPEG2 file any decoder
+are inputs: the ``{index}.png`` frames the reference writes at ``:285`` (read by Pillow on the host or, with ``--png_decoder gpu``,
+inflated and unfiltered on the GPU: ``scripts/png_in.py``, csrc/png_in.hip), or -- ``--target_video`` -- the YUV4MPEG2 file any decoder
 writes, whose I420 planes are uploaded and converted to RGB on the GPU, ``scripts/demux.py``, csrc/demux.hip), the pasted frames out
 as PNG (``:636``; by Pillow on the host or, with ``--png_encoder gpu``, filtered and deflated on the GPU: ``scripts/png.py``,
 csrc/png.hip) and, with ``--video_out``, as a YUV4MPEG2 file in the reference's ``yuv420p`` / BT.709 / ``tv`` range at 10 fps
@@ -130,6 +131,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "assumes, 10 fps, no audio")
     p.add_argument("--video_quality", type=int, default=None,
                    help="with --video_codec mjpeg: libjpeg's quality scale, 1..100 (default 90): the tables Pillow's quality= yields")
+    p.add_argument("--png_decoder", choices=["pillow", "gpu"], default="pillow",
+                   help="how the {index}.png files of --target_frames are decoded: pillow (default) = Pillow on the host, frame by "
+                        "frame; gpu = the host checks each file's chunks and uploads the compressed bytes, inflate and unfilter run on "
+                        "the GPU (csrc/png_in.hip, scripts/png_in.py; 8-bit RGB, RGBA and grey, not interlaced, at most 8192 pixels "
+                        "wide), timed with the host's reading and checking as the batch's png_in stage.  The frames are the same bit "
+                        "for bit.  Not with --target_video or --synthetic")
     p.add_argument("--png_encoder", choices=["pillow", "gpu"], default="pillow",
                    help="how the pasted frames' PNGs (:636) are compressed: pillow (default) = Pillow on the host, frame by frame; gpu = "
                         "filter and deflate on the GPU (csrc/png.hip, scripts/png.py; distance-1 matches only), timed as the batch's "
@@ -297,6 +304,17 @@ def check_video_in_reader(opt, video):
                          f"no entropy coding: leave the flag out")
 
 
+def check_png_decoder_options(opt):
+    """--png_decoder gpu says how the folder of --target_frames is read: a run that reads no such folder refuses it."""
+    opt = normalise_options(opt)
+    if opt.png_decoder != "gpu":
+        return
+    if opt.synthetic:
+        raise SystemExit("--png_decoder gpu decodes the PNG files of --target_frames: --synthetic reads no frames from disk")
+    if opt.target_video:
+        raise SystemExit("--png_decoder gpu decodes the PNG files of --target_frames: --target_video reads the clip from a video file")
+
+
 def check_video_out_options(opt):
     """--video_codec says how --video_out is written and --video_quality how the mjpeg codec quantises: alone they would be
     ignored, so they are refused."""
@@ -315,6 +333,7 @@ def check_options(opt):
     clip's: its files and checkpoints are asked for and every stage is switched on."""
     check_video_in_options(opt)
     check_video_out_options(opt)
+    check_png_decoder_options(opt)
     if not opt.synthetic:
         check_clip_options(opt)
     if opt.intake and not opt.with_vae:
@@ -367,6 +386,8 @@ def _run(opt) -> dict:
             video = open_video(opt.target_video)            # by the file's first bytes: a YUV4MPEG2 file, or an AVI with an MJPG stream
             check_video_in_reader(opt, video)
             clip = ClipInputs.from_video(video, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
+        elif opt.png_decoder == "gpu":
+            clip = ClipInputs.from_png_folder(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         else:
             clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         inputs, sink_type = providers.ClipRunInputs(clip, opt, dev), outputs.ClipOutputs

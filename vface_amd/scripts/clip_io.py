@@ -179,6 +179,25 @@ class ClipInputs:
         self._set_up(src_image, landmarks, n_frames, H, W, image_size)
         return self
 
+    @classmethod
+    def from_png_folder(cls, target_frames: str, src_image: str, landmarks: str, n_frames: int, H: int, W: int, image_size: int = 1024):
+        """The folder form with the frames decoded on the device (``--png_decoder gpu``): the folder's own ``frame_ids`` and
+        ``paths`` as ``__init__`` keeps them, and ``batch`` hands out the ``PNGFrames`` that a ``scripts/png_in.PNGFolderReader``
+        over those paths read -- parsed files, not pixels; the reader's ``to_rgb`` decodes them (``inputs.ClipRunInputs``).  The
+        clip's size is the first file's IHDR; a ``.jpg`` in the folder is refused by name."""
+        from .png_in import PNGFolderReader
+        listed = list_frames(target_frames)
+        if len(listed) < n_frames:
+            raise SystemExit(f"--target_frames {target_frames}: {len(listed)} frame file(s), --n_frames asks for {n_frames}")
+        listed = listed[:n_frames]
+        self = cls.__new__(cls)
+        self.frame_ids = [i for i, _ in listed]
+        self.paths = [p for _, p in listed]
+        self.video = PNGFolderReader(self.paths, f"--target_frames {target_frames}")
+        self.size = (self.video.H, self.video.W)
+        self._set_up(src_image, landmarks, n_frames, H, W, image_size)
+        return self
+
     def _set_up(self, src_image, landmarks, n_frames, H, W, image_size):
         from .intake import inv_transforms, quad_from_landmarks
         self.source_u8 = load_image(src_image)[None]                 # [1, Hs, Ws, 3]

@@ -13,7 +13,8 @@ The questions, for batch ``k`` of ``F = --n_samples`` frames (tensors on the pro
     inherits(k)             per frame: does it take the label map of the frame before (no landmarks, :297-303)?
     carry_labels(k, maps)   the label maps with the inherited ones put in; remembers batch k's last map for batch k + 1
     own_seconds(k)          stage name -> wall seconds of device work the provider did itself for batch k (``video_in``: the upload
-                            and colour conversion of a clip read from a video file); asked once, after ``intake_frames``
+                            and colour conversion of a clip read from a video file; ``png_in``: reading and parsing a folder's PNG
+                            files on the host, their upload and decoding, under ``--png_decoder gpu``); asked once, after ``intake_frames``
     landmarks(k)            conditioning landmarks [F, 136]
     source()                source frame [1, Hs, Ws, 3], quad (host), label map or None, landmarks [1, 136], identity features or None
     learnable_vector()      a seeded value for the model's learnable_vector on seeded weights, or None = leave the module's own
@@ -215,7 +216,9 @@ class ClipRunInputs:
     (``ClipInputs.from_video``) the clip hands out what the file's reader read -- I420 rows of a Y4M file, the compressed scans of
     an AVI's JPEG frames -- and the reader's ``to_rgb`` makes the RGB frames on the device (``hip.yuv420_to_rgb``; matrix and chroma
     siting from ``--video_in_matrix``, ``--chroma_upsample`` and the file's header; for an AVI the decoder of ``scripts/mjpeg_in.py``
-    in front of it), timed as stage ``video_in``."""
+    in front of it), timed as stage ``video_in``.  Over a folder read with ``--png_decoder gpu`` (``ClipInputs.from_png_folder``) it
+    hands out parsed PNG files and ``scripts/png_in.py`` decodes them on the device; reading and parsing on the host and the decode are
+    timed together as stage ``png_in``."""
     frame_size_order = "width_height"   # (a clip is rarely square: paste_back.PasteBack)
     record_keys = ("frame_ids", "pasted_frames", "crops", "conditioning")
 
@@ -239,7 +242,9 @@ class ClipRunInputs:
         return None, None, None     # :423 uc = learnable_vector; c and tc come from the conditioning stage
 
     def intake_frames(self, k):
+        t_read = time.time()
         given = self.clip.batch(k, self.F, whole_clip=self.whole)
+        t_read = time.time() - t_read
         if self.clip.video is None:
             return given["frames"].to(self.device), given["crop_frames"].to(self.device), given["quads"], None
         # a video file: what its reader hands out crosses to the device (I420 rows, or JPEG scans) and becomes RGB frames there
@@ -248,11 +253,16 @@ class ClipRunInputs:
         frames = self._rgb(given["frames"])
         crop_frames = frames if given["crop_frames"] is given["frames"] else self._rgb(given["crop_frames"])
         torch.cuda.synchronize(self.device)
-        self._seconds[k] = {"video_in": time.time() - t0}
+        stage = getattr(self.clip.video, "stage", "video_in")
+        # png_in also holds the host's half, which ran inside clip.batch: reading the files, every chunk's CRC, joining the IDATs
+        self._seconds[k] = {stage: time.time() - t0 + (t_read if stage == "png_in" else 0.0)}
         return frames, crop_frames, given["quads"], None
 
     def _rgb(self, read):
-        """What the clip's reader handed out (I420 rows of a Y4M file, the scans of an AVI's JPEG frames) -> device RGB frames."""
+        """What the clip's reader handed out (I420 rows of a Y4M file, the scans of an AVI's JPEG frames, the parsed files of a
+        folder of PNGs under ``--png_decoder gpu``: stage ``png_in``) -> device RGB frames."""
+        if getattr(self.clip.video, "stage", None) == "png_in":     # scripts/png_in.PNGFolderReader: no matrix, no chroma
+            return self.clip.video.to_rgb(read, self.device)
         if self.clip.video.fixed_matrix:            # Motion-JPEG: --video_in_entropy is its reader's alone
             return self.clip.video.to_rgb(read, self.device, self.matrix, self.chroma_upsample, entropy=self.entropy)
         return self.clip.video.to_rgb(read, self.device, self.matrix, self.chroma_upsample)
