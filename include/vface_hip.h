@@ -419,6 +419,31 @@ int vface_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_
 int vface_png_unfilter(const uint8_t* rows, int64_t file_stride, int W, int H, int bpp, int files, const int32_t* inflate_status,
                        uint8_t* rgb, int32_t* status, void* stream);
 
+/* vface_png_inflate_parallel: vface_png_inflate on many waves per file, block by block (csrc/png_in_par.hip; the pieces and a host
+ *   routine that sanitizers run are csrc/png_inflate_par.hpp, the protocol is stated in tests/png_inflate_par_model.py).  The
+ *   arguments up to adler are vface_png_inflate's, and rows[0 .. produced), status, produced, consumed and adler are what it writes
+ *   for EVERY input, valid or corrupt, bit for bit; nothing is written behind produced[f], nothing is read outside a file's range.
+ *   A file's body is cut into chunks of chunk_bytes (64 .. 2^20, a multiple of 4).  Chunk 0's segment starts at bit 0; chunk c >= 1's
+ *   at the smallest bit of its own range at which a dynamic block's header reads with status 0; a chunk without one starts none.
+ *   One wave per segment counts its bytes (up to the first block that ends at or behind the next segment's start, or a final one);
+ *   a file whose segments report no status, end exactly on one another with BFINAL in the last alone, and sum to `expect` is decoded
+ *   segment by segment into 16-bit elements (a byte, or 0x8000 | k: the byte k positions into the 32 768 in front of the segment)
+ *   and resolved in order into rows.  An accepted chain is the serial decode's own block sequence, by induction from bit 0.  Every
+ *   other file is decoded by vface_png_inflate's kernel in the call's last launch.
+ *   info: NULL or [files][4]: info[f][0] segments decoded in parallel and accepted, or 0 where the serial kernel decoded the file;
+ *   info[f][1] why it did: 0 it did not, 1 the chain did not close, 2 a segment reported a status (1 .. 11), 3 the byte count is not
+ *   `expect` (statuses 13, 14 among them), 4 a distance reaches in front of the file (status 12), 5 the file's range lies outside the
+ *   buffer; where several hold, 5, 2, 1, 3, 4 in that order; info[f][2] candidates found; info[f][3] 0.
+ *   workspace: vface_png_inflate_parallel_workspace_bytes(files, stream_bytes, expect, chunk_bytes) bytes (0 for arguments the call
+ *   refuses), 16-byte aligned: the segment tables of files * ceil(stream_bytes / chunk_bytes) entries and 2 * files * expect bytes
+ *   of elements.  Six launches, no allocation, no host synchronisation.
+ *   Refusals are vface_png_inflate's, and: NULL workspace: VFACE_ERR_ARG; chunk_bytes outside 64 .. 2^20 or no multiple of 4, a
+ *   workspace too small: VFACE_ERR_SHAPE; a workspace off 16 bytes: VFACE_ERR_ALIGN. */
+size_t vface_png_inflate_parallel_workspace_bytes(int files, int64_t stream_bytes, int64_t expect, int chunk_bytes);
+int vface_png_inflate_parallel(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, const int32_t* lengths, int files,
+                               uint8_t* rows, int64_t file_stride, int64_t expect, int32_t* status, int32_t* produced, int32_t* consumed,
+                               uint32_t* adler, int chunk_bytes, void* workspace, size_t workspace_bytes, int32_t* info, void* stream);
+
 /* ---- video in, colour half (REFace/scripts/VFace_inference_batch.py:240-285) --------------------------------------------------
  * The reference decodes the target video on the host (cv2.VideoCapture, BGR -> RGB, PNG per frame, :240-285).  The H.264 decoder
  * is not built here either; vface_amd/scripts/demux.py reads the YUV4MPEG2 file any decoder writes (`ffmpeg -i in.mp4 clip.y4m`),

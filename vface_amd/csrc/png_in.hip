@@ -62,17 +62,21 @@ __device__ inline T wave_sum(T x) {
 // Every lane runs the decode with the same values; what a lane does alone is marked by `lane`.
 // A file's bytes go to the ring as they are produced and from the ring to rows + f * file_stride in pieces of about kFlushBytes,
 // which is also where the Adler halves are summed; what was produced before a fault is written too, nothing behind it.
+// With `flags` (the last launch of vface_png_inflate_parallel, csrc/png_in_par.hip; nullptr otherwise): only files whose flag is set
+// are decoded, and nothing of the others is touched.
 __global__ __launch_bounds__(64) void png_inflate_kernel(const unsigned char* __restrict__ streams, long stream_bytes,
                                                          const long* __restrict__ offsets, const int* __restrict__ lengths, int files,
                                                          unsigned char* __restrict__ rows, long file_stride, long expect,
                                                          int* __restrict__ status_out, int* __restrict__ produced,
-                                                         int* __restrict__ consumed, unsigned* __restrict__ adler) {
+                                                         int* __restrict__ consumed, unsigned* __restrict__ adler,
+                                                         const int* __restrict__ flags) {
     __shared__ unsigned char ring[kInfWindow];
     __shared__ VfInfTables tb;
     __shared__ unsigned char win[kInWindow];
     const int lane = threadIdx.x;
 
     for (long f = blockIdx.x; f < files; f += gridDim.x) {
+        if (flags && !flags[f]) continue;
         const long off = offsets[f], n = lengths[f];
         unsigned s1 = 1, s2 = 0;
         long op = 0, flushed = 0, used = 0;
@@ -182,6 +186,15 @@ __global__ __launch_bounds__(64) void png_inflate_kernel(const unsigned char* __
 
 }  // namespace
 
+// the launch itself, for vface_png_inflate_parallel's flagged files too (the caller has checked the arguments)
+int vf_launch_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, const int32_t* lengths, int files, uint8_t* rows,
+                          int64_t file_stride, int64_t expect, int32_t* status, int32_t* produced, int32_t* consumed, uint32_t* adler,
+                          const int* flags, hipStream_t stream) {
+    hipLaunchKernelGGL(png_inflate_kernel, dim3(vf_grid(files, 1, kInflateGridCap)), dim3(64), 0, stream, streams, (long)stream_bytes,
+                       (const long*)offsets, lengths, files, rows, (long)file_stride, (long)expect, status, produced, consumed, adler, flags);
+    return vf_launched();
+}
+
 extern "C" int vface_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, const int32_t* lengths, int files,
                                  uint8_t* rows, int64_t file_stride, int64_t expect, int32_t* status, int32_t* produced, int32_t* consumed,
                                  uint32_t* adler, void* stream_) {
@@ -190,9 +203,8 @@ extern "C" int vface_png_inflate(const uint8_t* streams, int64_t stream_bytes, c
         expect <= 0)
         return VF_ERR_ARG;
     if (expect >= (1L << 31) || stream_bytes >= (1L << 31) || file_stride < expect) return VF_ERR_SHAPE;
-    hipLaunchKernelGGL(png_inflate_kernel, dim3(vf_grid(files, 1, kInflateGridCap)), dim3(64), 0, stream, streams, (long)stream_bytes,
-                       (const long*)offsets, lengths, files, rows, (long)file_stride, (long)expect, status, produced, consumed, adler);
-    return vf_launched();
+    return vf_launch_png_inflate(streams, stream_bytes, offsets, lengths, files, rows, file_stride, expect, status, produced, consumed, adler,
+                                 nullptr, stream);
 }
 
 // ---- unfilter ---------------------------------------------------------------------------------------------------------------------

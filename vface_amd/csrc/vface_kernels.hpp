@@ -117,6 +117,12 @@ struct AttnParams {
 };
 int vf_launch_attention(const AttnParams& p, int dtype, hipStream_t stream);
 
+// png_in.hip: vface_png_inflate's one-wave-per-file kernel on the files whose flag is set (flags == nullptr: on all), for
+// png_in_par.hip's fallback; the arguments are vface_png_inflate's, already checked
+int vf_launch_png_inflate(const uint8_t* streams, int64_t stream_bytes, const int64_t* offsets, const int32_t* lengths, int files, uint8_t* rows,
+                          int64_t file_stride, int64_t expect, int32_t* status, int32_t* produced, int32_t* consumed, uint32_t* adler,
+                          const int* flags, hipStream_t stream);
+
 // pointwise.hip / raft.hip: what capi.cpp's size queries and workspace checks call
 int vf_gn_partial_floats(int nimg, int hw, int C, int groups);
 int vf_chan_stats_slices(int hw);

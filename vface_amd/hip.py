@@ -95,6 +95,8 @@ SIGNATURES = {
     "vface_png_deflate": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "vface_png_inflate": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "vface_png_unfilter": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vface_png_inflate_parallel_workspace_bytes": (_sz, [_i32, _i64, _i64, _i32]),
+    "vface_png_inflate_parallel": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp, _vp]),
     "vface_yuv420_to_rgb": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vface_jpeg_scan_index": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "vface_jpeg_decode_entropy": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]),
@@ -778,6 +780,70 @@ def png_unfilter(rows: torch.Tensor, W: int, H: int, bpp: int, inflate_status: t
     _check(load().vface_png_unfilter(_p(rows), rows.shape[1], W, H, bpp, F_, _p(inflate_status), _p(out), _p(status), _stream()),
            "vface_png_unfilter")
     return out, status
+
+
+PNG_INFLATE_CHUNK_BYTES = 16384    # compressed bytes per chunk of png_inflate_parallel: zlib's level-6 streams of noisy frames start a block about
+                                   # every 16 KiB, so a chunk holds about one block start (tools/bench_png_in.py sweeps 4 .. 64 KiB)
+PNG_INFLATE_PAR_DECODE_GRID_CAP = 2048     # kFindGridCap, kCountGridCap (kWriteGridCap is 1024): workgroups of one wave before the grid loops
+PNG_INFLATE_PAR_RESOLVE_GRID_CAP = 256     # kResolveGridCap: workgroups, one file each
+PNG_INFLATE_FALLBACK_REASONS = {0: "none", 1: "the chain of segments did not close", 2: "a segment reported a status",
+                                3: "the byte count is not the image's", 4: "a distance reaches in front of the file",
+                                5: "the file's range lies outside the buffer"}
+_png_par_ws = {}
+
+
+def png_inflate_parallel_workspace_bytes(files: int, stream_bytes: int, expect: int, chunk_bytes: int = PNG_INFLATE_CHUNK_BYTES) -> int:
+    """Bytes of workspace ``vface_png_inflate_parallel`` asks for: the segment tables of ``files * ceil(stream_bytes / chunk_bytes)``
+    entries and two bytes per output byte."""
+    need = int(load().vface_png_inflate_parallel_workspace_bytes(int(files), int(stream_bytes), int(expect), int(chunk_bytes)))
+    if need == 0:
+        raise VFaceHipError(f"png_inflate_parallel: files, stream_bytes and expect are 1 .. 2^31 - 1 and chunk_bytes a multiple of 4 in "
+                            f"64 .. 2^20; got {files}, {stream_bytes}, {expect}, {chunk_bytes}")
+    return need
+
+
+def png_inflate_parallel(streams: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, expect: int,
+                         chunk_bytes: int = PNG_INFLATE_CHUNK_BYTES, out: Optional[torch.Tensor] = None, meta: Optional[torch.Tensor] = None,
+                         info: Optional[torch.Tensor] = None):
+    """``png_inflate`` with many waves per file -> ``(rows, meta, info)``: rows and meta are ``png_inflate``'s bit for bit, for every
+    input.  A file's body is cut into chunks of ``chunk_bytes``; a chunk in which a dynamic block starts begins a segment there, one
+    wave per segment counts and then decodes it into 16-bit elements, and the segments are resolved in order
+    (csrc/png_in_par.hip; ``tests/png_inflate_par_model.inflate_parallel``).  A file whose segments do not chain up exactly is
+    decoded by ``png_inflate``'s kernel in the same call.  ``info``: int32 [F, 4]: segments decoded in parallel (0: the serial
+    kernel decoded the file), why it did (``PNG_INFLATE_FALLBACK_REASONS``), candidates found, 0.  The workspace is kept here, per
+    device, and grown when needed."""
+    chunk_bytes = int(chunk_bytes)
+    if not 64 <= chunk_bytes <= 1 << 20 or chunk_bytes % 4:
+        raise VFaceHipError(f"png_inflate_parallel: chunk_bytes must be a multiple of 4 in 64 .. 2^20; got {chunk_bytes}")
+    if not _is_dev(streams, torch.uint8, 1) or streams.numel() == 0:
+        raise VFaceHipError("png_inflate_parallel: streams must be a contiguous uint8 buffer on the GPU, at least one byte")
+    if not _is_dev(offsets, torch.int64, 1) or not _is_dev(lengths, torch.int32, 1) or offsets.numel() != lengths.numel() or offsets.numel() == 0:
+        raise VFaceHipError("png_inflate_parallel: offsets (int64) and lengths (int32) must be contiguous [F] tensors on the GPU, F >= 1")
+    if offsets.device != streams.device or lengths.device != streams.device:
+        raise VFaceHipError("png_inflate_parallel: streams, offsets and lengths must be on one device")
+    F_, expect = offsets.numel(), int(expect)
+    if not 0 < expect < 1 << 31 or streams.numel() >= 1 << 31:
+        raise VFaceHipError(f"png_inflate_parallel: expect and the stream buffer are 1 .. 2^31 - 1 bytes; got {expect}, {streams.numel()}")
+    if out is None:
+        out = torch.empty((F_, expect), dtype=torch.uint8, device=streams.device)
+    elif not _is_dev(out, torch.uint8, 2) or out.shape[0] != F_ or out.shape[1] < expect or out.device != streams.device:
+        raise VFaceHipError(f"png_inflate_parallel: out must be a contiguous uint8 [{F_}, >= {expect}] tensor on the streams' device")
+    if meta is None:
+        meta = torch.empty((5, F_), dtype=torch.int32, device=streams.device)
+    elif not _is_dev(meta, torch.int32, 2) or tuple(meta.shape) != (5, F_) or meta.device != streams.device:
+        raise VFaceHipError(f"png_inflate_parallel: meta must be a contiguous int32 [5, {F_}] tensor on the streams' device")
+    if info is None:
+        info = torch.empty((F_, 4), dtype=torch.int32, device=streams.device)
+    elif not _is_dev(info, torch.int32, 2) or tuple(info.shape) != (F_, 4) or info.device != streams.device:
+        raise VFaceHipError(f"png_inflate_parallel: info must be a contiguous int32 [{F_}, 4] tensor on the streams' device")
+    need = png_inflate_parallel_workspace_bytes(F_, streams.numel(), expect, chunk_bytes)
+    ws = _png_par_ws.get(str(streams.device))
+    if ws is None or ws.numel() < need:
+        ws = _png_par_ws[str(streams.device)] = torch.empty(need, dtype=torch.uint8, device=streams.device)
+    _check(load().vface_png_inflate_parallel(_p(streams), streams.numel(), _p(offsets), _p(lengths), F_, _p(out), out.shape[1], expect,
+                                             _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(meta[3]), chunk_bytes, _p(ws), ws.numel(), _p(info),
+                                             _stream()), "vface_png_inflate_parallel")
+    return out, meta, info
 
 
 YUV_MATRICES = {"bt709": 0, "bt601": 1}

@@ -137,6 +137,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the GPU (csrc/png_in.hip, scripts/png_in.py; 8-bit RGB, RGBA and grey, not interlaced, at most 8192 pixels "
                         "wide), timed with the host's reading and checking as the batch's png_in stage.  The frames are the same bit "
                         "for bit.  Not with --target_video or --synthetic")
+    p.add_argument("--png_in_inflate", choices=["auto", "serial", "parallel"], default="serial",
+                   help="with --png_decoder gpu: how a file's deflate stream is inflated: serial (default) = one wave per file; parallel "
+                        "= many waves per file, one per stretch of blocks that starts in a chunk of 16 KiB (csrc/png_in_par.hip), a file "
+                        "whose stretches do not chain up exactly is decoded serially in the same call; auto = parallel where the mean "
+                        "compressed frame exceeds scripts/png_in.PARALLEL_MIN_BODY_BYTES.  The frames are the same bit for bit")
     p.add_argument("--png_encoder", choices=["pillow", "gpu"], default="pillow",
                    help="how the pasted frames' PNGs (:636) are compressed: pillow (default) = Pillow on the host, frame by frame; gpu = "
                         "filter and deflate on the GPU (csrc/png.hip, scripts/png.py; distance-1 matches only), timed as the batch's "
@@ -308,6 +313,8 @@ def check_png_decoder_options(opt):
     """--png_decoder gpu says how the folder of --target_frames is read: a run that reads no such folder refuses it."""
     opt = normalise_options(opt)
     if opt.png_decoder != "gpu":
+        if getattr(opt, "png_in_inflate", "serial") != "serial":
+            raise SystemExit(f"--png_in_inflate {opt.png_in_inflate} says how the GPU decoder inflates: it needs --png_decoder gpu")
         return
     if opt.synthetic:
         raise SystemExit("--png_decoder gpu decodes the PNG files of --target_frames: --synthetic reads no frames from disk")
@@ -388,6 +395,7 @@ def _run(opt) -> dict:
             clip = ClipInputs.from_video(video, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         elif opt.png_decoder == "gpu":
             clip = ClipInputs.from_png_folder(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
+            clip.video.inflate = opt.png_in_inflate
         else:
             clip = ClipInputs(opt.target_frames, opt.src_image, opt.landmarks, opt.n_frames, opt.H, opt.W)
         inputs, sink_type = providers.ClipRunInputs(clip, opt, dev), outputs.ClipOutputs

@@ -14,6 +14,8 @@ compares it with the file's.  There is no host inflate on this path.
 - Bytes of the zlib stream behind the final block's end and its Adler-32 are accepted, as libpng and Pillow accept them: the
   checksum is read where the decoder says the final block ended (``file_adler``).
 - A file that does not decode ends the run with its name, the status by name and, for a filter byte above 4, the row.
+- ``--png_in_inflate parallel`` (``decode(inflate="parallel")``) inflates one file on many waves, block by block
+  (``hip.png_inflate_parallel``, csrc/png_in_par.hip): the same bytes, statuses and messages; ``auto`` picks by ``inflate_path``.
 - The source image stays Pillow's: one image per clip.
 
 The format is stated in ``tests/png_inflate_model.py``; it decodes what ``--png_encoder gpu`` wrote.
@@ -195,14 +197,38 @@ class PNGFrames:
 
 
 _staging = {}                       # decode's pinned upload buffer
+INFLATE_MODES = ("auto", "serial", "parallel")
+PARALLEL_CHUNK_BYTES = 16384        # hip.PNG_INFLATE_CHUNK_BYTES: about one of zlib's level-6 blocks of a noisy frame
+# ``auto`` takes the parallel inflate where the mean deflate body of a batch exceeds this many bytes.  Source: tools/bench_png_in.py,
+# profiles/r13_a_png_inflate_parallel_stages.jsonl ("Frames in, PNG: one stream on many waves"): Pillow's smooth 512 x 512
+# file (0.12 MB, 3 segments) is where the two paths are level (51.5 against 57.9 ms), every Huffman-coded case above it gains 4.9x or
+# more.  Body size cannot see stored-block files, where the serial inflate is a copy and wins.  The default of --png_in_inflate stays
+# ``serial`` until the ``png_in`` stage has been timed in a production-size run.
+PARALLEL_MIN_BODY_BYTES = 8 * PARALLEL_CHUNK_BYTES
+last_info = None                    # the parallel inflate's info rows of the last ``decode`` (one int32 [F, 4] tensor per bpp group), or None
 
 
-def decode(frames: PNGFrames, device) -> torch.Tensor:
+def inflate_path(mode: str, body_bytes: int, files: int) -> str:
+    """Which inflate a batch of ``files`` deflate bodies of ``body_bytes`` bytes in all takes: ``mode`` itself, or for ``auto``
+    ``"parallel"`` where the mean body exceeds ``PARALLEL_MIN_BODY_BYTES`` and ``"serial"`` otherwise."""
+    if mode not in INFLATE_MODES:
+        raise ValueError(f"inflate must be one of {INFLATE_MODES}; got {mode!r}")
+    if mode != "auto":
+        return mode
+    return "parallel" if body_bytes > PARALLEL_MIN_BODY_BYTES * max(int(files), 1) else "serial"
+
+
+def decode(frames: PNGFrames, device, inflate: str = "serial", chunk_bytes: Optional[int] = None) -> torch.Tensor:
     """``PNGFolderReader.read``'s result -> device uint8 [F, H, W, 3].  Per group of files with one bpp (a folder usually is one
     group): one upload of the packed bodies from pinned memory, one ``hip.png_inflate``, one ``hip.png_unfilter`` and one small copy
     back of status, produced, consumed, the Adler halves and the unfilter status.  A file that does not decode -- a non-zero
-    status, an Adler-32 other than the file's, a filter byte above 4 -- raises ``SystemExit`` with its path."""
+    status, an Adler-32 other than the file's, a filter byte above 4 -- raises ``SystemExit`` with its path.
+    ``inflate``: ``"serial"`` (one wave per file), ``"parallel"`` (``hip.png_inflate_parallel``: many waves per file, chunks of
+    ``chunk_bytes``, by default ``PARALLEL_CHUNK_BYTES``; the same bytes, statuses and messages) or ``"auto"`` (``inflate_path``)."""
     from .. import hip
+    global last_info
+    if inflate not in INFLATE_MODES:
+        raise hip.VFaceHipError(f"png_in.decode: inflate must be one of {INFLATE_MODES}; got {inflate!r}")
     if not isinstance(frames, PNGFrames) or len(frames) == 0:
         raise hip.VFaceHipError("png_in.decode: frames must be what PNGFolderReader.read returned, at least one frame")
     device = torch.device(device)
@@ -215,7 +241,7 @@ def decode(frames: PNGFrames, device) -> torch.Tensor:
     groups = {}
     for row, r in enumerate(frames.records):
         groups.setdefault(r.bpp, []).append(row)
-    rgb = None
+    rgb, last_info = None, None
     for bpp, rows_of in groups.items():
         part = PNGFrames(W, H, [frames.records[i] for i in rows_of])
         p = part.packed(_staging.get("buffer"))
@@ -228,7 +254,11 @@ def decode(frames: PNGFrames, device) -> torch.Tensor:
         streams = dev[p["streams_at"]:]
         expect = (1 + bpp * W) * H
         meta = torch.empty((6, F), dtype=torch.int32, device=device)
-        rows, _ = hip.png_inflate(streams, offsets, lengths, expect, meta=meta[:5])
+        if inflate_path(inflate, sum(len(r.body) for r in part.records), F) == "parallel":
+            rows, _, info = hip.png_inflate_parallel(streams, offsets, lengths, expect, chunk_bytes or PARALLEL_CHUNK_BYTES, meta=meta[:5])
+            last_info = (last_info or []) + [info]
+        else:
+            rows, _ = hip.png_inflate(streams, offsets, lengths, expect, meta=meta[:5])
         out, _ = hip.png_unfilter(rows, W, H, bpp, meta[0], status=meta[5])
         status, produced, consumed, halves_a, halves_b, bad_row = meta.cpu().tolist()       # the one copy back
         halves = halves_a + halves_b                                            # [F][2], flat
@@ -255,6 +285,7 @@ class PNGFolderReader:
     ``len()``, ``read(indices) -> PNGFrames`` (indices into ``paths``) and ``to_rgb``.  ``read`` parses the files it is asked for;
     a frame of another size than the first is refused from its header."""
     stage = "png_in"                # the stage ``inputs.ClipRunInputs`` times this reader's work as: ``read`` and ``to_rgb``
+    inflate = "serial"              # --png_in_inflate: which inflate ``to_rgb`` asks ``decode`` for
 
     def __init__(self, paths: List[str], path: str = "--target_frames"):
         self.path, self.paths = path, list(paths)
@@ -292,7 +323,7 @@ class PNGFolderReader:
         return PNGFrames(self.W, self.H, records)
 
     def to_rgb(self, frames: PNGFrames, device) -> torch.Tensor:
-        return decode(frames, device)
+        return decode(frames, device, inflate=self.inflate)
 
     def close(self):
         pass
