@@ -381,6 +381,50 @@ size_t vface_png_deflate_workspace_bytes(int row_bytes, int H, int frames, int s
 int vface_png_deflate(const uint8_t* rows, int row_bytes, int H, int frames, int stripe_rows, uint8_t* out, int64_t out_bytes,
                       int64_t* offsets, int32_t* lengths, uint32_t* adler, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- GIF out (REFace/scripts/VFace_inference_batch.py:658) ---------------------------------------------------------------------
+ * The reference ends a run with clips.write_gif(...) of the pasted frames (:658).  These entry points make, per frame, a palette of
+ * up to 256 colours and the complete image data of a GIF frame on the device; vface_amd/scripts/gif.py adds the fixed headers and the
+ * 768 palette bytes.  csrc/gif.hip; the cut rule is csrc/gif_palette.hpp and the encoder csrc/gif_lzw.hpp, which a host program runs
+ * under sanitizers.  The format is stated once in tests/gif_model.py and equalled bit for bit.  Every call that takes W and H:
+ * W, H in 1..65535 and W * H <= 2^24 (a box's channel sum, at most 255 * 2^24, fits 32 bits), otherwise VFACE_ERR_SHAPE; a NULL
+ * pointer or W, H, frames <= 0: VFACE_ERR_ARG.  No allocation, no host synchronisation.
+ *
+ * vface_gif_histogram (:658): rgb [frames][H][W][3] -> counts [frames][32768]: the pixels per cell,
+ *   cell(r, g, b) = (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3).  counts is zeroed by the call.
+ *
+ * vface_gif_boxes (:658): counts [frames][32768] -> labels [frames][32768], a box number per cell (0 for an empty cell), and
+ *   ncolors [frames], the number of boxes = min(256, non-empty cells).  Median cut: box 0 holds every non-empty cell; up to 255 times
+ *   the box with at least two non-empty cells and the largest population x longest side in cells (lowest number on a tie) is cut
+ *   along its longest axis (ties R, G, B) at the population median, both sides non-empty; the upper side takes the next number.
+ *
+ * vface_gif_palette (:658): rgb and labels -> palette [frames][256][3]: entry i is the mean of the pixels whose cell lies in box i,
+ *   each channel (2 sum + n) / (2 n) rounded down; an entry without pixels is zeros.  sums: frames * 4096 bytes of workspace,
+ *   4-byte aligned (VFACE_ERR_ALIGN), zeroed by the call.
+ *
+ * vface_gif_map (:658): rgb, palette and ncolors -> indices [frames][W * H]: every pixel's entry of smallest squared RGB distance
+ *   among the first ncolors[frame] (clamped to 1..256), the lowest index on a tie.  Exact search, 256 distances per pixel.
+ *
+ * vface_gif_lzw (:658): indices [frames][npix] -> every frame's image data packed back to back into out, frame f at offsets[f],
+ *   offsets[frames] the end (offsets: int64 [frames + 1]).  Image data: 08, the bit stream padded to a byte in sub-blocks of at most
+ *   255 bytes behind their length byte, 00.  Minimum code size 8 (Clear 256, end of information 257, first free code 258, 9 to 12
+ *   bits, LSB first).  The stream is Clear, then per segment of seg_pixels indices (the last may be shorter) its greedy LZW codes
+ *   from an empty table and its terminator: Clear if another segment follows, end of information after the last; a table that fills
+ *   inside a segment is answered by a Clear at 12 bits.  One wave codes a segment; a code's bit offset follows from its number
+ *   alone, so all codes are then placed in parallel.  Bytes at or past out_bytes are dropped, never written, and offsets stay
+ *   the true ones: out_bytes >= frames * vface_gif_lzw_bound(npix, seg_pixels) always suffices.  workspace:
+ *   vface_gif_lzw_workspace_bytes(npix, frames, seg_pixels) bytes, 16-byte aligned.  One memset and four launches.
+ *   NULL pointer, npix, frames, seg_pixels or out_bytes <= 0: VFACE_ERR_ARG; npix > 2^24, seg_pixels > 65535, a workspace too
+ *   small: VFACE_ERR_SHAPE; a workspace off 16 bytes: VFACE_ERR_ALIGN.  The two size queries return 0 for such arguments. */
+int vface_gif_histogram(const uint8_t* rgb, int W, int H, int frames, uint32_t* counts, void* stream);
+int vface_gif_boxes(const uint32_t* counts, int frames, uint8_t* labels, int32_t* ncolors, void* stream);
+int vface_gif_palette(const uint8_t* rgb, int W, int H, int frames, const uint8_t* labels, uint8_t* palette, uint32_t* sums, void* stream);
+int vface_gif_map(const uint8_t* rgb, int W, int H, int frames, const uint8_t* palette, const int32_t* ncolors, uint8_t* indices,
+                  void* stream);
+int64_t vface_gif_lzw_bound(int64_t npix, int seg_pixels);
+size_t vface_gif_lzw_workspace_bytes(int64_t npix, int frames, int seg_pixels);
+int vface_gif_lzw(const uint8_t* indices, int64_t npix, int frames, int seg_pixels, uint8_t* out, int64_t out_bytes, int64_t* offsets,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- PNG frames in (REFace/scripts/VFace_inference_batch.py:285) --------------------------------------------------------------
  * The reference writes the target clip as {index}.png (:285) and reads the folder back.  vface_amd/scripts/png_in.py walks each
  * file's chunks on the host (CRCs, IHDR, the zlib header) and uploads the deflate bodies as they lie in the files; these entry

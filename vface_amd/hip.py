@@ -93,6 +93,13 @@ SIGNATURES = {
     "vface_png_deflate_bound": (_i64, [_i32, _i32, _i32]),
     "vface_png_deflate_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "vface_png_deflate": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "vface_gif_histogram": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "vface_gif_boxes": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "vface_gif_palette": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vface_gif_map": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "vface_gif_lzw_bound": (_i64, [_i64, _i32]),
+    "vface_gif_lzw_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "vface_gif_lzw": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
     "vface_png_inflate": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "vface_png_unfilter": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vface_png_inflate_parallel_workspace_bytes": (_sz, [_i32, _i64, _i64, _i32]),
@@ -711,6 +718,121 @@ def png_deflate(rows: torch.Tensor, stripe_rows: int = PNG_STRIPE_ROWS, out: Opt
     _check(lib.vface_png_deflate(_p(rows), rb, H, F_, stripe_rows, _p(out), out.numel(), _p(offsets), _p(meta), _p(meta[F_:]), _p(ws),
                                  ws.numel(), _stream()), "vface_png_deflate")
     return out, meta, offsets
+
+
+# ---- GIF out (:658; csrc/gif.hip)
+GIF_SEG_PIXELS = 16384             # indices of a frame that one wave codes from an empty table: tools/bench_gif.py's sweep over 1024 .. 16384
+                                   # (profiles/r14_a_*): the LZW pass for 32 frames of 1920 x 1080 takes the same time at every length (22.2 ..
+                                   # 23.0 ms), and the image data shrinks from 680 kB (1024) over 534 kB (4096) to 350 kB per smooth frame, 906 /
+                                   # 777 / 586 kB per noisy one, where Pillow's one stream takes 298 / 587 kB; one frame alone pays 4.5 ms
+                                   # instead of 1.3
+GIF_CELLS, GIF_COLORS = 32768, 256
+GIF_MAX_SIDE, GIF_MAX_PIXELS = 65535, 1 << 24      # kGifMaxSide, kGifMaxPixels: a box's channel sum, at most 255 * 2^24, fits 32 bits
+GIF_MAX_SEG_PIXELS = 65535
+GIF_HIST_SHARE, GIF_HIST_GRID_CAP = 65536, 1024    # kGifHistShare pixels per workgroup; workgroups before the grid loops
+GIF_BOXES_GRID_CAP = 64                            # kGifBoxesGridCap: workgroups, one frame each
+GIF_PALETTE_SHARE, GIF_PALETTE_GRID_CAP = 16384, 2048
+GIF_MAP_SHARE, GIF_MAP_GRID_CAP = 8192, 4096
+GIF_LZW_GRID_CAP = 4096                            # kGifLzwGridCap: workgroups of one wave, one (frame, segment) each
+GIF_LZW_FLAT_GRID_CAP = 2048                       # kGifFlatGridCap: workgroups of 256 codes (the pack) or bytes (the framing)
+_gif_ws = {}
+
+
+def _gif_frames(frames_u8, what):
+    if (not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
+            or frames_u8.shape[-1] != 3 or not frames_u8.is_contiguous()):
+        raise VFaceHipError(f"{what}: frames must be contiguous uint8 [F, H, W, 3] on the GPU")
+    F_, H, W, _ = frames_u8.shape
+    if F_ <= 0 or not (1 <= W <= GIF_MAX_SIDE and 1 <= H <= GIF_MAX_SIDE) or W * H > GIF_MAX_PIXELS:
+        raise VFaceHipError(f"{what}: F >= 1, W and H in 1..{GIF_MAX_SIDE} and W * H <= 2^24 (the histogram's 32-bit bound); got {F_}, {W} x {H}")
+    return F_, H, W
+
+
+def _gif_buffer(t, dtype, shape, device, what):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        raise VFaceHipError(f"{what} must be a contiguous {dtype} {list(shape)} tensor on the frames' device")
+    return t
+
+
+def gif_histogram(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 device frames [F, H, W, 3] -> int32 [F, 32768] (read as unsigned): the pixels in every cell of 8 x 8 x 8,
+    cell = (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) (:658; csrc/gif.hip; ``tests/gif_model.histogram``)."""
+    F_, H, W = _gif_frames(frames_u8, "gif_histogram")
+    out = _gif_buffer(out, torch.int32, (F_, GIF_CELLS), frames_u8.device, "gif_histogram: out")
+    _check(load().vface_gif_histogram(_p(frames_u8), W, H, F_, _p(out), _stream()), "vface_gif_histogram")
+    return out
+
+
+def gif_boxes(counts: torch.Tensor, labels: Optional[torch.Tensor] = None, ncolors: Optional[torch.Tensor] = None):
+    """``gif_histogram``'s counts [F, 32768] -> ``(labels, ncolors)``: uint8 [F, 32768], the median-cut box of every cell (0 for an empty
+    cell), and int32 [F], the number of boxes.  The rule is csrc/gif_palette.hpp's (``tests/gif_model.boxes`` bit for bit)."""
+    if (not isinstance(counts, torch.Tensor) or not counts.is_cuda or counts.dtype != torch.int32 or counts.dim() != 2
+            or counts.shape[1] != GIF_CELLS or counts.shape[0] <= 0 or not counts.is_contiguous()):
+        raise VFaceHipError(f"gif_boxes: counts must be a contiguous int32 [F, {GIF_CELLS}] tensor on the GPU")
+    F_ = counts.shape[0]
+    labels = _gif_buffer(labels, torch.uint8, (F_, GIF_CELLS), counts.device, "gif_boxes: labels")
+    ncolors = _gif_buffer(ncolors, torch.int32, (F_,), counts.device, "gif_boxes: ncolors")
+    _check(load().vface_gif_boxes(_p(counts), F_, _p(labels), _p(ncolors), _stream()), "vface_gif_boxes")
+    return labels, ncolors
+
+
+def gif_palette(frames_u8: torch.Tensor, labels: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frames and ``gif_boxes``' labels -> uint8 [F, 256, 3]: entry i is the mean, halves up, of the pixels whose cell lies in box i;
+    entries without pixels are zeros (``tests/gif_model.palette``)."""
+    F_, H, W = _gif_frames(frames_u8, "gif_palette")
+    labels = _gif_buffer(labels, torch.uint8, (F_, GIF_CELLS), frames_u8.device, "gif_palette: labels")
+    out = _gif_buffer(out, torch.uint8, (F_, GIF_COLORS, 3), frames_u8.device, "gif_palette: out")
+    sums = torch.empty((F_, GIF_COLORS, 4), dtype=torch.int32, device=frames_u8.device)
+    _check(load().vface_gif_palette(_p(frames_u8), W, H, F_, _p(labels), _p(out), _p(sums), _stream()), "vface_gif_palette")
+    return out
+
+
+def gif_map(frames_u8: torch.Tensor, palette: torch.Tensor, ncolors: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Frames, palettes [F, 256, 3] and ncolors [F] -> uint8 [F, H * W]: every pixel's palette entry of smallest squared RGB distance
+    among the first ncolors, the lowest index on a tie; exact search (``tests/gif_model.index_map``)."""
+    F_, H, W = _gif_frames(frames_u8, "gif_map")
+    palette = _gif_buffer(palette, torch.uint8, (F_, GIF_COLORS, 3), frames_u8.device, "gif_map: palette")
+    ncolors = _gif_buffer(ncolors, torch.int32, (F_,), frames_u8.device, "gif_map: ncolors")
+    out = _gif_buffer(out, torch.uint8, (F_, H * W), frames_u8.device, "gif_map: out")
+    _check(load().vface_gif_map(_p(frames_u8), W, H, F_, _p(palette), _p(ncolors), _p(out), _stream()), "vface_gif_map")
+    return out
+
+
+def gif_lzw_bound(npix: int, seg_pixels: int = GIF_SEG_PIXELS) -> int:
+    """Bytes that always hold one frame's image data: every segment at the most codes it can make, the sub-block framing."""
+    n = int(load().vface_gif_lzw_bound(int(npix), int(seg_pixels)))
+    if n == 0:
+        raise VFaceHipError(f"gif_lzw: npix is 1..2^24 and seg_pixels 1..{GIF_MAX_SEG_PIXELS}; got {npix}, {seg_pixels}")
+    return n
+
+
+def gif_lzw(indices: torch.Tensor, seg_pixels: int = GIF_SEG_PIXELS, out: Optional[torch.Tensor] = None):
+    """Index maps, device uint8 [F, npix] -> ``(out, offsets)``: every frame's GIF image data (08, the LZW stream in sub-blocks, 00)
+    packed back to back in the uint8 buffer ``out``, frame f at ``out[offsets[f]:offsets[f + 1]]`` (int64 [F + 1]).  Segments of
+    ``seg_pixels`` indices are coded from an empty table by one wave each and end in a Clear (csrc/gif.hip;
+    ``tests/gif_model.image_data`` byte for byte).  ``out``: a contiguous uint8 buffer, by default F x ``gif_lzw_bound``.  Bytes that
+    a smaller ``out`` cannot hold are dropped; the caller sees it from ``offsets[F] > out.numel()``."""
+    if not isinstance(indices, torch.Tensor) or not indices.is_cuda or indices.dtype != torch.uint8 or indices.dim() != 2 or not indices.is_contiguous():
+        raise VFaceHipError("gif_lzw: indices must be a contiguous uint8 [F, npix] tensor on the GPU")
+    F_, npix = indices.shape
+    seg_pixels = int(seg_pixels)
+    if F_ <= 0 or not 1 <= npix <= GIF_MAX_PIXELS or not 1 <= seg_pixels <= GIF_MAX_SEG_PIXELS:
+        raise VFaceHipError(f"gif_lzw: F >= 1, npix in 1..2^24 and seg_pixels in 1..{GIF_MAX_SEG_PIXELS}; got {F_}, {npix}, {seg_pixels}")
+    if out is None:
+        out = torch.empty(F_ * gif_lzw_bound(npix, seg_pixels), dtype=torch.uint8, device=indices.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != indices.device or out.numel() == 0:
+        raise VFaceHipError("gif_lzw: out must be a contiguous uint8 buffer on the indices' device")
+    lib = load()
+    need = int(lib.vface_gif_lzw_workspace_bytes(npix, F_, seg_pixels))
+    ws = _gif_ws.get(str(indices.device))
+    if ws is None or ws.numel() < need:
+        ws = _gif_ws[str(indices.device)] = torch.empty(need, dtype=torch.uint8, device=indices.device)
+    offsets = torch.empty(F_ + 1, dtype=torch.int64, device=indices.device)
+    _check(lib.vface_gif_lzw(_p(indices), npix, F_, seg_pixels, _p(out), out.numel(), _p(offsets), _p(ws), ws.numel(), _stream()),
+           "vface_gif_lzw")
+    return out, offsets
 
 
 # ---- PNG frames in (:285; csrc/png_in.hip)

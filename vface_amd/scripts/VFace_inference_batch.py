@@ -146,6 +146,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="how the pasted frames' PNGs (:636) are compressed: pillow (default) = Pillow on the host, frame by frame; gpu = "
                         "filter and deflate on the GPU (csrc/png.hip, scripts/png.py; distance-1 matches only), timed as the batch's "
                         "png_out stage.  Both are lossless and decode to the same pixels")
+    p.add_argument("--gif_out", type=str, default=None,
+                   help="real-clip run: write the pasted frames as an animated GIF89a (:658; 10 fps, looping, a palette of 256 per "
+                        "frame), quantised and LZW-coded on the GPU (csrc/gif.hip, scripts/gif.py), timed as the batch's gif_out stage; "
+                        "beside --video_out and --png_encoder, and independent of both")
+    p.add_argument("--gif_seg_pixels", type=int, default=None,
+                   help="with --gif_out: indices of a frame coded from an empty LZW table by one wave, 1..65535 (default "
+                        "hip.GIF_SEG_PIXELS)")
     p.add_argument("--synthetic_weights", action="store_true",
                    help="real-clip run on seeded weights for every model (the seeds of --synthetic) instead of --ckpt, "
                         "--faceParsing_ckpt and --raft_ckpt: for tests and smoke runs")
@@ -335,12 +342,26 @@ def check_video_out_options(opt):
             raise SystemExit(f"--video_quality is libjpeg's scale, 1..100; got {opt.video_quality}")
 
 
+def check_gif_out_options(opt):
+    """--gif_out writes the frames of a clip; --gif_seg_pixels says how it cuts them: alone it would be ignored, so it is refused."""
+    opt = normalise_options(opt)
+    if opt.gif_seg_pixels is not None:
+        if not opt.gif_out:
+            raise SystemExit("--gif_seg_pixels says how --gif_out cuts a frame's indices: it needs --gif_out FILE")
+        if not 1 <= opt.gif_seg_pixels <= 65535:
+            raise SystemExit(f"--gif_seg_pixels is 1..65535 indices; got {opt.gif_seg_pixels}")
+    if opt.gif_out and opt.synthetic:
+        raise SystemExit("--gif_out writes the pasted frames of a real clip: --synthetic writes no clip (its sink saves tensors and "
+                         "single frames)")
+
+
 def check_options(opt):
     """Every dependency between flags, on normalised options, before anything is built.  Without ``--synthetic`` the run is a
     clip's: its files and checkpoints are asked for and every stage is switched on."""
     check_video_in_options(opt)
     check_video_out_options(opt)
     check_png_decoder_options(opt)
+    check_gif_out_options(opt)
     if not opt.synthetic:
         check_clip_options(opt)
     if opt.intake and not opt.with_vae:

@@ -59,11 +59,13 @@ class ClipOutputs:
     """A clip from disk: the pasted frames as ``Base_dir/results/{index}.png`` (:636; ``--png_encoder``) unless ``--skip_save`` and, with
     ``--video_out``, as YUV4MPEG2 in frame order (:646-654: yuv420p, BT.709, tv range, 10 fps; scripts/mux.py), the batch's
     ``video_out`` stage -- or, with ``--video_codec mjpeg``, as Motion-JPEG in an AVI at ``--video_quality`` (default 90;
-    scripts/mjpeg.py), the same stage.  The file is opened by the first batch, whose frames give its size."""
+    scripts/mjpeg.py), the same stage -- and, with ``--gif_out``, as an animated GIF (:658; scripts/gif.py), the batch's ``gif_out``
+    stage, whether or not ``--skip_save`` is given.  Each file is opened by the first batch, whose frames give its size."""
 
     def __init__(self, opt):
         self.dir, self.save, self.video_out, self.writer = opt.Base_dir, not opt.skip_save, opt.video_out, None
         self.codec, self.quality, self.png = opt.video_codec or "y4m", opt.video_quality, _PNGSink(opt)
+        self.gif_out, self.gif_seg_pixels, self.gif = getattr(opt, "gif_out", None), getattr(opt, "gif_seg_pixels", None), None
         os.makedirs(self.dir, exist_ok=True)
 
     def write(self, b):
@@ -78,6 +80,13 @@ class ClipOutputs:
                     self.writer = Y4MWriter(self.video_out, W, H)
             with b.timer("video_out"):
                 self.writer.write(b.pasted)
+        if self.gif_out:
+            if self.gif is None:
+                from .gif import GIFWriter
+                kw = {} if self.gif_seg_pixels is None else {"seg_pixels": self.gif_seg_pixels}
+                self.gif = GIFWriter(self.gif_out, b.pasted.shape[2], b.pasted.shape[1], **kw)
+            with b.timer("gif_out"):
+                self.gif.write(b.pasted)
         if self.save:
             os.makedirs(os.path.join(self.dir, "results"), exist_ok=True)
             self.png.save(b, [os.path.join(self.dir, "results", f"{index}.png") for index in b.frame_ids])
@@ -85,3 +94,5 @@ class ClipOutputs:
     def close(self):
         if self.writer is not None:
             self.writer.close()
+        if self.gif is not None:
+            self.gif.close()
