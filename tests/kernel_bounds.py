@@ -8,7 +8,8 @@ the convolutions' (``conv_ref_and_bound``), the column statistics' (``colstats_r
 one-pass sums, ``gn_cols_ref_and_bound`` from column sums, ``gn_apply_ref_and_bound`` from the device's statistics),
 ``linear_small_ref_and_bound``, and the fused chains' stage by stage (``st_front_t0_`` / ``st_front_qkv_ref_and_bound``,
 ``ffn_ref_and_bound`` for PLAIN / PRE / POST) with ``round_operand`` for a value rounded once as the next operand, and the hook and
-sampler kernels' (``flow_warp_`` / ``flow_to_latent_`` / ``ddim_step_`` / ``timestep_embedding_ref_and_bound``).  Every bound is
+sampler kernels' (``flow_warp_`` / ``flow_to_latent_`` / ``ddim_step_`` / ``timestep_embedding_ref_and_bound``), the flow
+producer's and the face parser's glue kernels' (``pooled_linear_`` / ``channel_gate_ref_and_bound``).  Every bound is
 built from fp64 quantities of the reference alone; test_attention_bound_cpu.py, test_gemm_bound_cpu.py,
 test_transformer_bound_cpu.py and test_hook_bound_cpu.py show that each admits a model of the kernel's rounding points and refuses one-line defects of it.
 Plain functions, nothing collected by pytest."""
@@ -956,3 +957,42 @@ def flow_update_ref(flow, delta=None):
     """``vface_flow_update``: flow32 + delta32[:, :2], one IEEE fp32 sum (``delta`` None: the flow itself); the 16-bit copies are
     its rounding."""
     return flow + delta[:, :2] if delta is not None else flow
+
+
+# ------------------------------------------------------------------------------------------------ the face parser's glue kernels (csrc/parsing.hip)
+# Used by test_parse_gpu.py (synthetic operands, one kernel at a time) and by parse_bounds.check_stage (the engine's own operands).
+def pooled_linear_ref_and_bound(a, w, b, act):
+    """``vface_pooled_linear``: act(a w^T + b) in fp64 on the fp32 ``a [nimg, K]``, ``w [N, K]``, ``b [N]`` (or None); ``act``:
+    "none", "relu" or "sigmoid".  Returns ``(ref [nimg, N], bound)``.  A lane adds ceil(K / 64) products in order, six butterfly
+    levels follow, then the bias: every partial sum is bounded by S = sum |w a| + |b|, so |error| <= (ceil(K / 64) + 8) u S before
+    the activation.  ReLU does not expand it; the sigmoid's slope is <= 1/4 and its own evaluation (expf, a division) is allowed
+    4 x the relative error of torch's fp32 sigmoid on these inputs (``cpu_fp32_rel_error``)."""
+    a64, w64 = a.double(), w.double()
+    K = a64.shape[1]
+    pre, S = a64 @ w64.T, a64.abs() @ w64.abs().T
+    if b is not None:
+        pre, S = pre + b.double(), S + b.double().abs()
+    bound = (-(-K // 64) + 8) * U32 * S
+    if act == "none":
+        return pre, bound
+    if act == "relu":
+        return pre.clamp_min(0), bound
+    assert act == "sigmoid", act
+    ref = torch.sigmoid(pre)
+    return ref, bound / 4 + cpu_fp32_rel_error(torch.sigmoid, pre.float()) * ref
+
+
+def channel_gate_ref_and_bound(x, g, hw, dt, rvec=None, rten=None, add_x=False):
+    """``vface_channel_gate``: y = x g[image] + r in fp64 for the 16-bit ``x [nimg hw, C]``, the fp32 gate ``g [nimg, C]`` and r one
+    of nothing, ``rvec [nimg, C]`` (fp32), ``rten [nimg hw, C]`` (16-bit), ``x`` itself (``add_x``).  The kernel does one fp32 fma
+    (the 16-bit operands and the fp32 gate are exact in it), then one rounding to the storage type: bound = u |ref| + d."""
+    x64 = x.double()
+    ref = x64 * g.double().repeat_interleave(hw, 0)
+    if rvec is not None:
+        ref = ref + rvec.double().repeat_interleave(hw, 0)
+    elif rten is not None:
+        ref = ref + rten.double()
+    elif add_x:
+        ref = ref + x64
+    b0 = U32 * ref.abs()
+    return ref, b0 + 0.5 * ulp(ref.abs() + b0, dt)

@@ -15,7 +15,8 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN, ROOT
-from kernel_bounds import U32, assert_within, cpu_fp32_rel_error, rnd, same_bits, sentinel, ulp
+from kernel_bounds import (U32, assert_within, channel_gate_ref_and_bound, pooled_linear_ref_and_bound, rnd, same_bits, sentinel,
+                           ulp)
 
 sys.path.insert(0, GOLDEN)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -117,7 +118,8 @@ def test_maxpool(dt, H, W, C):
 @pytest.mark.parametrize("inplace", [False, True])
 def test_channel_gate(dt, C, form, inplace):
     """y = x g + r for nimg = 3, hw = 4, all four forms of r, in place and not.  The kernel does one fp32 fma (the 16-bit operands
-    and the fp32 gate are exact in it), then one rounding to the storage type: bound = u |ref| + d."""
+    and the fp32 gate are exact in it), then one rounding to the storage type: bound = u |ref| + d
+    (kernel_bounds.channel_gate_ref_and_bound, which parse_bounds.check_stage applies to the engine's own operands)."""
     h = hip()
     nimg, hw = 3, 4
     M = nimg * hw
@@ -131,16 +133,8 @@ def test_channel_gate(dt, C, form, inplace):
     h.channel_gate(xd[:M], g.to(DEV), yd[:M], M=M, hw=hw, C_=C, rvec=None if rvec is None else rvec.to(DEV),
                    rten=None if rten is None else rten.to(DEV), add_x=form == "x")
     got = yd.cpu()
-    x64 = xh[:M, :C].double()
-    ref = x64 * g.double().repeat_interleave(hw, 0)
-    if form == "vec":
-        ref = ref + rvec.double().repeat_interleave(hw, 0)
-    elif form == "tensor":
-        ref = ref + rten.double()
-    elif form == "x":
-        ref = ref + x64
-    b0 = U32 * ref.abs()
-    assert_within(got[:M, :C], ref, b0 + 0.5 * ulp(ref.abs() + b0, dt), f"channel_gate {form} {dt}")
+    ref, bound = channel_gate_ref_and_bound(xh[:M, :C], g, hw, dt, rvec=rvec, rten=rten, add_x=form == "x")
+    assert_within(got[:M, :C], ref, bound, f"channel_gate {form} {dt}")
     assert same_bits(got[:M, C:], xh[:M, C:]) and same_bits(got[M:], xh[M:]), "stores outside the C channels"
     if not inplace:
         assert same_bits(xd.cpu(), xh)
@@ -169,7 +163,8 @@ def test_pooled_linear(K, N, act, sa):
     with the stride vface_channel_stats leaves (2) or densely.  A lane adds ceil(K / 64) products in order, six butterfly levels
     follow, then the bias: every partial sum is bounded by S = sum |w a| + |b|, so |error| <= (ceil(K / 64) + 8) u S before the
     activation.  ReLU does not expand it; the sigmoid's slope is <= 1/4 and its own evaluation (expf, a division) is allowed
-    4 x the relative error of torch's fp32 sigmoid on these inputs (kernel_bounds.cpu_fp32_rel_error)."""
+    4 x the relative error of torch's fp32 sigmoid on these inputs (kernel_bounds.cpu_fp32_rel_error): all of it is
+    kernel_bounds.pooled_linear_ref_and_bound."""
     h = hip()
     nimg = 3
     g = torch.Generator().manual_seed(K + N)
@@ -179,15 +174,7 @@ def test_pooled_linear(K, N, act, sa):
     out = torch.full((nimg + 1, N + 4), 7.0, device=DEV)
     h.pooled_linear(a.to(DEV), w.to(DEV), b.to(DEV), out[:nimg], nimg=nimg, N=N, K=K, lda=K * sa, sa=sa, act=act)
     got = out.cpu()
-    a64 = a[:, :, 0].double()
-    pre = a64 @ w.double().T + b.double()
-    S = a64.abs() @ w.double().abs().T + b.double().abs()
-    bound = (-(-K // 64) + 8) * U32 * S
-    if act == 1:
-        ref = pre.clamp_min(0)
-    else:
-        ref = torch.sigmoid(pre)
-        bound = bound / 4 + cpu_fp32_rel_error(torch.sigmoid, pre.float()) * ref
+    ref, bound = pooled_linear_ref_and_bound(a[:, :, 0], w, b, "relu" if act == 1 else "sigmoid")
     assert_within(got[:nimg, :N], ref, bound, f"pooled_linear K={K} N={N} act={act}")
     assert bool((got[:nimg, N:] == 7.0).all()) and bool((got[nimg:] == 7.0).all())
     with pytest.raises(h.VFaceHipError):

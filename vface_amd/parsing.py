@@ -15,8 +15,10 @@
     class head is padded 19 -> 32 columns and written in fp32; ``vface_upsample_argmax_u8`` turns it into one byte per pixel.
 
 ``conv_out16`` / ``conv_out32`` and their upsamplings are not run: ``FaceParser.forward`` discards them (``down_seg, _, _``), so the
-result is the same.  Their state-dict keys are accepted and ignored.  No launch splits K by batch size and no kernel uses atomics, so
-a frame's label map does not depend on which frames share its batch.  No CPU fallback: without the HIP library every call raises.
+result is the same.  Their state-dict keys are accepted and ignored.  ``split_k = False`` keeps the ``window`` launches (im2col +
+``vface_gemm``) from splitting K, a choice that is made from M and so from the batch; the 3x3 launches do follow the split-K rules of
+``vface_conv3x3``, which read the per-sample geometry (rows per image, channels) only.  No kernel uses atomics, so a frame's label map
+does not depend on which frames share its batch.  No CPU fallback: without the HIP library every call raises.
 """
 from __future__ import annotations
 
@@ -97,14 +99,26 @@ class ParseEngine(ConvNetEngine):
         """Global average pool: fp32 [nimg, C, 2] whose [..., 0] is the mean (``vface_channel_stats``)."""
         return hip.channel_stats(x, nimg=nimg, hw=hw, C_=C_)
 
-    def _arm(self, arm, x, *, nimg, H, W, cin, rvec=None, rten=None):
-        """AttentionRefinementModule (model.py:82-89) and the add that follows it (:122 / :127), in place in its output."""
+    def _arm(self, arm, x, *, nimg, H, W, cin, rvec=None, rten=None, tap=None):
+        """AttentionRefinementModule (model.py:82-89) and the add that follows it (:122 / :127), in place in its output.  ``tap`` as in
+        ``logits``: ``<arm>.conv``, ``<arm>.conv.act``, ``<arm>.mean``, ``<arm>.conv_atten`` (the gate), ``<arm>.out`` (the gated sum)."""
         hw, M = H * W, nimg * H * W
         feat = self._buf(M, 128)
         self.conv3(f"{arm}.conv.conv", x, feat, nimg=nimg, H=H, W=W, ldx=cin)
+        if tap:
+            tap(f"{arm}.conv", feat)
         self._relu(feat, M=M, hw=hw, C_=128)
-        g = self._pooled(f"{arm}.conv_atten", self._means(feat, nimg=nimg, hw=hw, C_=128), nimg=nimg, lda=256, sa=2, act=hip.ACT_SIGMOID)
+        if tap:
+            tap(f"{arm}.conv.act", feat)
+        m = self._means(feat, nimg=nimg, hw=hw, C_=128)
+        if tap:
+            tap(f"{arm}.mean", m)
+        g = self._pooled(f"{arm}.conv_atten", m, nimg=nimg, lda=256, sa=2, act=hip.ACT_SIGMOID)
+        if tap:
+            tap(f"{arm}.conv_atten", g)
         hip.channel_gate(feat, g, feat, M=M, hw=hw, C_=128, rvec=rvec, rten=rten)
+        if tap:
+            tap(f"{arm}.out", feat)
         return feat
 
     # ---- the network -----------------------------------------------------------------------------------------------------
@@ -114,13 +128,27 @@ class ParseEngine(ConvNetEngine):
             raise hip.VFaceHipError(f"the face parser's input must be a multiple of 32 and at least 64 in both directions; got {H} x {W}")
 
     @torch.no_grad()
-    def logits(self, x8: torch.Tensor, F: int, H: int, W: int) -> torch.Tensor:
-        """Token rows [F*H*W, 8] of the normalised input -> fp32 class logits [F * H/8 * W/8, 32] (columns 19..31 are zero)."""
+    def logits(self, x8: torch.Tensor, F: int, H: int, W: int, tap=None) -> torch.Tensor:
+        """Token rows [F*H*W, 8] of the normalised input -> fp32 class logits [F * H/8 * W/8, 32] (columns 19..31 are zero).
+
+        ``tap(name, tensor)`` (tests; production passes None) is called right after the launch that completes ``tensor``; it changes
+        no launch, buffer or flag.  Buffers are reused and written in place: a tap that keeps must clone.  With r = ``cp.resnet`` and
+        b = ``cp.resnet.layerL.B`` the names are
+          ``x8`` (the input), ``r.conv1`` (after the last frame chunk), ``r.conv1.act``, ``r.maxpool``;
+          ``b.conv1``, ``b.conv1.act``, ``b.conv2``, ``b.downsample.0`` (where present), ``b.sum`` (the ReLU of shortcut + residual),
+          ``b.out`` (what the next block reads: the same rows);
+          ``cp.avg.mean`` (fp32 [F, 512, 2]: [..., 0] is the mean), ``cp.conv_avg`` (fp32 [F, 128]);
+          ``cp.arm32.conv``, ``.conv.act``, ``.mean``, ``.conv_atten``, ``.out``; the same under ``cp.arm16`` (``_arm``);
+          ``cp.conv_head32``, ``cp.conv_head32.act``, ``cp.conv_head16``, ``cp.conv_head16.act`` (the right half of ``cat``);
+          ``ffm.cat`` (all 256 columns), ``ffm.convblk``, ``ffm.convblk.act``, ``ffm.mean``, ``ffm.conv1``, ``ffm.conv2``, ``ffm.out``;
+          ``conv_out.conv``, ``conv_out.conv.act``, ``logits`` (fp32 [M, 32])."""
         self.check_size(H, W)
         if not x8.is_cuda:
             raise hip.VFaceHipError("the face parser runs on the GPU: its input must be a device tensor (no CPU fallback)")
         if x8.dtype != self.dtype or tuple(x8.shape) != (F * H * W, 8) or not x8.is_contiguous():
             raise hip.VFaceHipError(f"logits: input must be contiguous {self.dtype} [{F * H * W}, 8]; got {x8.dtype} {tuple(x8.shape)}")
+        if tap:
+            tap("x8", x8)
         r = "cp.resnet"
         # stem: 7x7 stride 2 (+ folded bn1) -> ReLU -> max-pool.  The window matrix is 392 x 2 bytes per output pixel (51 MB per
         # 512 x 512 frame): built for a bounded number of frames at a time
@@ -132,10 +160,16 @@ class ParseEngine(ConvNetEngine):
             n = min(step, F - f0)
             self.window(f"{r}.conv1", x8[f0 * H * W:(f0 + n) * H * W], x[f0 * h2 * w2:(f0 + n) * h2 * w2], nimg=n, H=H, W=W, C_=8, ldx=8,
                         stride=2)
+        if tap:
+            tap(f"{r}.conv1", x)
         self._relu(x, M=F * h2 * w2, hw=h2 * w2, C_=64)
+        if tap:
+            tap(f"{r}.conv1.act", x)
         h, w = h2 // 2, w2 // 2
         t = self._buf(F * h * w, 64)
         hip.maxpool3x3s2(x, t, nimg=F, H=h2, W=w2, C_=64)
+        if tap:
+            tap(f"{r}.maxpool", t)
         x, cin = t, 64
         feats = {}
         cat = None
@@ -148,9 +182,15 @@ class ParseEngine(ConvNetEngine):
                 M = F * oh * ow
                 t = self._buf(M, cout)
                 self.conv3(f"{b}.conv1", x, t, nimg=F, H=h, W=w, ldx=x.stride(0), stride=st)
+                if tap:
+                    tap(f"{b}.conv1", t)
                 self._relu(t, M=M, hw=oh * ow, C_=cout)
+                if tap:
+                    tap(f"{b}.conv1.act", t)
                 t2 = self._buf(M, cout)
                 self.conv3(f"{b}.conv2", t, t2, nimg=F, H=oh, W=ow, ldx=cout)
+                if tap:
+                    tap(f"{b}.conv2", t2)
                 if li == 2 and bi == 1:      # feat8 is the left half of the fusion module's input [feat8 | feat_cp8]
                     cat = self._buf(M, 256)
                     y = cat[:, :128]
@@ -159,37 +199,76 @@ class ParseEngine(ConvNetEngine):
                 if f"{b}.downsample.0" in self.P:      # relu(bn(conv1x1 stride s (x)) + residual)
                     s = self._buf(M, cout)
                     self.window(f"{b}.downsample.0", x, s, nimg=F, H=h, W=w, C_=c0, ldx=x.stride(0), stride=st)
+                    if tap:
+                        tap(f"{b}.downsample.0", s)
                     self._relu(s, M=M, hw=oh * ow, C_=cout, residual=t2, y=y)
                 else:                                      # relu(x + residual)
                     self._relu(x, M=M, hw=oh * ow, C_=cout, residual=t2, y=y)
+                if tap:
+                    tap(f"{b}.sum", y)
                 x = y
+                if tap:
+                    tap(f"{b}.out", x)
                 h, w = oh, ow
             cin = cout
             feats[li] = (x, h, w)
         (f8, h8, w8), (f16, h16, w16), (f32_, h32, w32) = feats[2], feats[3], feats[4]
         # context path (model.py:110-131)
-        avg = self._pooled("cp.conv_avg.conv", self._means(f32_, nimg=F, hw=h32 * w32, C_=512), nimg=F, lda=1024, sa=2, act=hip.ACT_RELU)
-        s32 = self._arm("cp.arm32", f32_, nimg=F, H=h32, W=w32, cin=512, rvec=avg)            # feat32_arm + avg_up
+        m32 = self._means(f32_, nimg=F, hw=h32 * w32, C_=512)
+        if tap:
+            tap("cp.avg.mean", m32)
+        avg = self._pooled("cp.conv_avg.conv", m32, nimg=F, lda=1024, sa=2, act=hip.ACT_RELU)
+        if tap:
+            tap("cp.conv_avg", avg)
+        s32 = self._arm("cp.arm32", f32_, nimg=F, H=h32, W=w32, cin=512, rvec=avg, tap=tap)   # feat32_arm + avg_up
         up32 = self._buf(F * h16 * w16, 128)
         self.conv3("cp.conv_head32.conv", s32, up32, nimg=F, H=h32, W=w32, ldx=128, upsample=True)
+        if tap:
+            tap("cp.conv_head32", up32)
         self._relu(up32, M=F * h16 * w16, hw=h16 * w16, C_=128)
-        s16 = self._arm("cp.arm16", f16, nimg=F, H=h16, W=w16, cin=256, rten=up32)            # feat16_arm + feat32_up
+        if tap:
+            tap("cp.conv_head32.act", up32)
+        s16 = self._arm("cp.arm16", f16, nimg=F, H=h16, W=w16, cin=256, rten=up32, tap=tap)   # feat16_arm + feat32_up
         M8 = F * h8 * w8
         self.conv3("cp.conv_head16.conv", s16, cat[:, 128:], nimg=F, H=h16, W=w16, ldx=128, upsample=True)
+        if tap:
+            tap("cp.conv_head16", cat[:, 128:])
         hip.channel_norm_act(cat[:, 128:], cat[:, 128:], M=M8, hw=h8 * w8, C_=128, act=hip.ACT_RELU, ldx=256, ldy=256)
+        if tap:
+            tap("cp.conv_head16.act", cat[:, 128:])
+            tap("ffm.cat", cat)
         # feature fusion (:206-216): feat * atten + feat
         feat = self._buf(M8, 256)
         self.window("ffm.convblk.conv", cat, feat, nimg=F, H=h8, W=w8, C_=256, ldx=256)
+        if tap:
+            tap("ffm.convblk", feat)
         self._relu(feat, M=M8, hw=h8 * w8, C_=256)
-        a1 = self._pooled("ffm.conv1", self._means(feat, nimg=F, hw=h8 * w8, C_=256), nimg=F, lda=512, sa=2, act=hip.ACT_RELU)
+        if tap:
+            tap("ffm.convblk.act", feat)
+        m8 = self._means(feat, nimg=F, hw=h8 * w8, C_=256)
+        if tap:
+            tap("ffm.mean", m8)
+        a1 = self._pooled("ffm.conv1", m8, nimg=F, lda=512, sa=2, act=hip.ACT_RELU)
+        if tap:
+            tap("ffm.conv1", a1)
         a2 = self._pooled("ffm.conv2", a1, nimg=F, lda=64, sa=1, act=hip.ACT_SIGMOID)
+        if tap:
+            tap("ffm.conv2", a2)
         hip.channel_gate(feat, a2, feat, M=M8, hw=h8 * w8, C_=256, add_x=True)
+        if tap:
+            tap("ffm.out", feat)
         # head (:50-53): 3x3 + ReLU, then the 1x1 to the classes, fp32
         mid = self._buf(M8, 256)
         self.conv3("conv_out.conv.conv", feat, mid, nimg=F, H=h8, W=w8, ldx=256)
+        if tap:
+            tap("conv_out.conv", mid)
         self._relu(mid, M=M8, hw=h8 * w8, C_=256)
+        if tap:
+            tap("conv_out.conv.act", mid)
         out = torch.empty(M8, HEAD_COLS, dtype=torch.float32, device=self.dev)
         self.window("conv_out.conv_out", mid, out, nimg=F, H=h8, W=w8, C_=256, ldx=256, out32=True)
+        if tap:
+            tap("logits", out)
         return out
 
     @torch.no_grad()
